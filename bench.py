@@ -16,7 +16,8 @@ A step = one SpMV over the whole matrix (+ the exchange of y when N > 1),
 inputs resident in HBM.  value = 2 * nnz_global / step time, in GFLOP/s
 (reference definition, include/utils.h:70-75).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py --full         # + every secondary measurement (below)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
     python bench.py --config 4 [--gpus N --partition nnz]   # nlpkkt160-sized .mtx
     python bench.py --config 2     # 1M banded CSR, 16/row, flushed
@@ -31,10 +32,20 @@ the optional legs added: `config.exchange_ms_alone` + `exchange_alternatives_ms`
 `config.family_variants` (the banded and W = 2^20 members of the family at this N),
 `config.partition_kkt` (even vs nnz-balanced rows on the nlpkkt160-shaped
 matrix), `native` (the library's own multi-GPU path, from a fresh child once
-the ranks have released the devices); at N = 1 `roofline.variants`,
-`cpu_baseline`, `extras`.  The LAST line is the record.  A leg that fails is
-named in `legs_failed`; a leg that hangs is ended by a watchdog with the line
-printed (benchlib/legs.py); nothing after the main measurement can cost it.
+the ranks have released the devices); at N = 1 with `--full`
+`roofline.variants`, `cpu_baseline`, `extras`.  The LAST line is the record.
+A leg that fails is named in `legs_failed`; a leg that hangs is ended by a
+watchdog with the line printed (benchlib/legs.py); nothing after the main
+measurement can cost it.
+
+A plain one-GPU run (no `--full`) is the headline alone: set up, check a few
+hundred rows of y, warm up, time exactly K steps, print ONE line
+(`ms_per_step` = wall time of the K steps / K).  `--full` adds, at N = 1, the
+secondary measurements above and the host-stall retry of the timed steps
+(`host.retry_ms_per_step`); `--config 2 / 4` add `extras` and (config 2)
+`cpu_baseline` with it.  `--dump-outputs DIR` writes the y of the last timed
+step to DIR as .npy (float64; above 32 MB a fixed, seeded sample of its rows
+plus their indices), the same inputs in every run of the same arguments.
 
 This file is the CLI and the process orchestration; the modes live in
 benchlib/: common (workload, result check, roofline records), single

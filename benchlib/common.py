@@ -214,7 +214,53 @@ def parse_args(argv=None):
                          "instead of RCCL collectives (1-GPU test boxes)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="one GPU: besides the headline, also the secondary "
+                         "measurements (roofline.variants, cpu_baseline, "
+                         "extras) and the host-stall retry of the timed "
+                         "steps; --no-cpu-baseline / --no-extras still drop "
+                         "theirs.  Off: set up, check rows of y, warm up, time "
+                         "--steps steps, print the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the y of the last "
+                         "step as DIR/<name>.npy (float64; a fixed, seeded "
+                         "sample of its rows when y is large): two builds "
+                         "run with the same arguments compare output for "
+                         "output")
     return ap.parse_args(argv)
+
+
+# ---- --dump-outputs: what the timed path computed in its last step.  An
+# output of more than half the limit is written as a fixed, seeded sample of
+# its rows -- the same rows in every run of the same arguments -- beside the
+# rows' indices (float64, exact below 2^53).
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_ROWS = 1 << 21
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(directory, arrays):
+    """{name: 1-D array} -> DIR/<name>.npy, or DIR/<name>_sample.npy +
+    DIR/<name>_sample_rows.npy; returns the file names written"""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    files = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if a.nbytes <= DUMP_LIMIT_BYTES // 2:
+            files[name] = a
+            continue
+        rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+        rows = np.sort(rng.choice(len(a), DUMP_SAMPLE_ROWS, replace=False))
+        files[name + "_sample"] = a[rows]
+        files[name + "_sample_rows"] = rows.astype(np.float64)
+    total = sum(v.nbytes for v in files.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes over the %d-byte limit"
+                         % (total, DUMP_LIMIT_BYTES))
+    for fn, v in files.items():
+        np.save(os.path.join(directory, fn + ".npy"), v)
+    return sorted(fn + ".npy" for fn in files)
 
 
 # ---- result check without the oracle: rows regenerated by the host-side C

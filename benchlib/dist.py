@@ -23,10 +23,10 @@ import time
 
 from .common import *  # noqa: F401,F403
 from .common import (FAMILIES, MATRIX_SEED, METRIC, ROOT, ROWS_PER_GPU, X_SEED,
-                     cgroup_cpu_stat, check_rows, config4_file, host_cpus,
-                     kernel_source_ident, measured_traffic, roofline_dict,
-                     secondary_roofline, stat_delta, strong_one_gpu,
-                     strong_speedup_of, workload_name)
+                     cgroup_cpu_stat, check_rows, config4_file, dump_outputs,
+                     host_cpus, kernel_source_ident, measured_traffic,
+                     roofline_dict, secondary_roofline, stat_delta,
+                     strong_one_gpu, strong_speedup_of, workload_name)
 from .cpu import cpu_baseline
 from .legs import LEG_BUDGET_S, LegRunner
 from .single import extra_measurements, single_matrix_bench, window_variants
@@ -448,14 +448,14 @@ class RankJob:
                      "throttled": stat_delta(stat2, self.stat3)}]
         # At N = 1 a step is one launch, so wall / step must equal the
         # event-timed kernel; a gap means the HOST stalled inside the timed
-        # region (round 2: CFS throttling, 4.4 ms/step).  Then -- once, in the
-        # same process -- K steps are timed again AS A DIAGNOSTIC
+        # region (round 2: CFS throttling, 4.4 ms/step).  Then -- with --full,
+        # once, in the same process -- K steps are timed again AS A DIAGNOSTIC
         # (host.retry_ms_per_step, top-level "host_stall_retry": true):
         # `value` always is the FIRST attempt, exactly K timed steps, never a
         # best-of-two (lines must stay comparable across rounds).
         gap = elapsed * 1e3 / a.steps - float(np.mean(kern_ms))
         self.retried = False
-        if (self.world == 1 and not a.force_exchange
+        if (a.full and self.world == 1 and not a.force_exchange
                 and gap > 0.05 * float(np.mean(kern_ms))):
             e2, k2, q2 = self.timed_steps()
             stat4 = cgroup_cpu_stat()
@@ -593,6 +593,9 @@ def run_rank(args, argv, omp_team):
     legs.phase("warm-up + K timed steps")
     job.measure()
     kern_ms = job.kern_ms
+    if args.dump_outputs and job.rank == 0:  # y of the last timed step
+        legs.phase("write --dump-outputs")
+        dump_outputs(args.dump_outputs, {"y": job.y.cpu().numpy()})
     # what joined, on which cards, and every rank's own kernel time
     legs.phase("describe the job + reductions over the ranks")
     rccl = per_rank = None
@@ -752,12 +755,14 @@ def run_rank(args, argv, omp_team):
                    and not os.environ.get("SPMV_BENCH_PARENT_RUNS_NATIVE"))
     if want_native:
         plan.append("native_mgpu")
-    if (single and not a.no_extras and a.family == "random"
+    # one GPU: the secondary measurements only with --full (a plain run is
+    # the headline alone)
+    if (a.full and single and not a.no_extras and a.family == "random"
             and a.window <= 0 and a.format == "hll"):
         plan.append("variants")
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         plan.append("cpu_baseline")
-    if single and not a.no_extras:
+    if a.full and single and not a.no_extras:
         plan.append("extras")
     legs.announce(plan)
 
@@ -803,7 +808,7 @@ def run_rank(args, argv, omp_team):
 
     # ---- the line goes out NOW; whatever happens in a leg, it stands ----
     legs.emit_final = emit  # from here on the watchdog guards LEGS
-    if job.rank == 0:
+    if job.rank == 0 and plan:  # no leg to wait for: the final line only
         emit(provisional=True)
 
     def note(key, value, where=None):
@@ -1341,6 +1346,9 @@ def run_matrix_rank(args, argv, omp_team):
         return single_matrix_bench(args, job.S, job.torch, job.dev)
     if args.config != 4:
         raise SystemExit("--config %d is a single-GPU line" % args.config)
+    if args.dump_outputs:
+        raise SystemExit("--dump-outputs: --config 4 over ranks keeps y in "
+                         "per-rank row ranges; dump it at one GPU")
     job = RankJob(args, omp_team)
     job.init_process_group()
     t0 = time.time()

@@ -76,6 +76,8 @@ def native_mgpu_bench(args, argv, omp_team):
         del y
 
     wall_ms, kms = g.run(kernel, args.warmup, args.steps)
+    if args.dump_outputs:  # y of the last timed step, as device 0 holds it
+        dump_outputs(args.dump_outputs, {"y": g.get_y(0)})
     ngp, _, nnz_global, _ = g.info()
     stored, alg_bytes, layout = g.shard_info(0)
     if args.format == "hll" and kernel == S.HLL_KERNEL_PANELS:

@@ -299,6 +299,8 @@ def single_matrix_bench(args, S, torch, dev):
         torch.cuda.synchronize()
         ms_per_step = (time.perf_counter() - t0) * 1e3 / args.steps
         kern_ms = [a.elapsed_time(b) for a, b in ev]
+    if args.dump_outputs:  # y of the last timed step
+        dump_outputs(args.dump_outputs, {"y": y.cpu().numpy()})
     alg = dA.algorithmic_bytes
     out = {
         "metric": METRIC, "value": round(2.0 * NZ / (ms_per_step * 1e6), 2),
@@ -330,7 +332,7 @@ def single_matrix_bench(args, S, torch, dev):
                  if not flush else None},
         "setup_s": round(t_setup, 2), "rows_checked": len(rows),
     }
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         ex = {}
         for k in (1, 2, 4):
             ms = float(np.median(dA.time(k, x.data_ptr(), y.data_ptr(), 2, 10,
@@ -339,7 +341,7 @@ def single_matrix_bench(args, S, torch, dev):
                 round(ms, 4), round(2.0 * NZ / (ms * 1e6), 1),
                 round(alg / (ms * 1e6) / HBM_PEAK_GBPS, 4)]
         out["extras"] = ex
-    if not args.no_cpu_baseline and args.config == 2:
+    if args.full and not args.no_cpu_baseline and args.config == 2:
         out["cpu_baseline"] = cpu_baseline(
             S, FAMILIES["banded"], M, N, 16, 0,
             args.cpu_csv_dir or os.path.join(ROOT, "gpurun_out", "cpu_baseline"),

@@ -111,6 +111,69 @@ def test_the_single_gpu_line_runs_on_the_runtime_it_was_built_for():
     assert j["config"]["deterministic"] in (True, False)
 
 
+def test_the_plain_line_is_the_headline_alone_and_dumps_its_y(tmp_path):
+    """`python bench.py --steps K --warmup W` (no --full): ONE line, exactly
+    K timed steps, no secondary legs; --dump-outputs writes the y of the last
+    timed step, which the product's host generator reproduces row by row and
+    a second run reproduces value by value (same inputs)"""
+    import numpy as np
+    sys.path.insert(0, S.ROOT)
+    from benchlib.common import FAMILIES, host_row_dots
+    rows_per_gpu = 640000
+    ys = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(S.ROOT, "bench.py"),
+                            "--gpus", "1", "--steps", "4", "--warmup", "1",
+                            "--rows-per-gpu", str(rows_per_gpu),
+                            "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [json.loads(l) for l in r.stdout.splitlines()
+                 if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-3000:]
+        j = lines[0]
+        assert j["steps"] == 4 and j["warmup"] == 1 and j["ms_per_step"] > 0
+        assert len(j["host"]["timing_attempts"]) == 1
+        assert j["legs_s"] == {} and j["legs_failed"] == []
+        for key in ("cpu_baseline", "extras"):
+            assert key not in j, key
+        assert "variants" not in j["roofline"]
+        assert sorted(os.listdir(out)) == ["y.npy"]
+        y = np.load(out / "y.npy")
+        assert y.dtype == np.float64 and y.shape == (rows_per_gpu,)
+        ys.append(y)
+    rows = np.arange(0, rows_per_gpu, 997)
+    want, scale = host_row_dots(S, FAMILIES["random"], rows_per_gpu, 32,
+                                2 * rows_per_gpu, 42, 7, rows)
+    err = np.abs(ys[0][rows] - want) / np.maximum(np.abs(want), 1e-3 * scale)
+    assert err.max() <= 1e-6, err.max()
+    if j["config"]["deterministic"]:
+        assert np.array_equal(ys[0], ys[1])
+    else:
+        assert np.allclose(ys[0], ys[1], rtol=1e-12, atol=0)
+
+
+def test_the_full_line_carries_the_secondary_measurements(tmp_path):
+    """`--full` at one GPU: the provisional line, then the final one with
+    roofline.variants, cpu_baseline and extras (1M rows: the config-2 part
+    of extras runs on the headline's x and y)"""
+    r = subprocess.run([sys.executable, os.path.join(S.ROOT, "bench.py"),
+                        "--full", "--steps", "3", "--warmup", "1",
+                        "--rows-per-gpu", "1000000",
+                        "--cpu-csv-dir", str(tmp_path / "cpu")],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 2 and lines[0]["provisional"] is True
+    assert lines[0]["legs_pending"] == ["variants", "cpu_baseline", "extras"]
+    j = lines[-1]
+    assert j["legs_failed"] == [] and "provisional" not in j
+    assert set(j["legs_s"]) == {"variants", "cpu_baseline", "extras"}
+    assert j["roofline"]["variants"] and j["extras"]
+    assert j["cpu_baseline"]["value"] > 0
+
+
 @pytest.mark.parametrize("args,kernel_prefix", [
     (["--config", "4", "--kkt-n", "24", "--steps", "3", "--warmup", "1"], "csr_"),
     (["--config", "2", "--steps", "5", "--warmup", "1"], "csr_"),
@@ -118,10 +181,12 @@ def test_the_single_gpu_line_runs_on_the_runtime_it_was_built_for():
 def test_bench_lines_of_the_other_configs(args, kernel_prefix, tmp_path):
     """`bench.py --config 4` (generated nlpkkt160-shaped .mtx, here on a 24^3
     grid, through io_load_csr_cached) and `--config 2` (1M banded CSR,
-    flushed) print the same kind of line as the headline."""
+    flushed) print the same kind of line as the headline; `extras` ride on
+    it with --full."""
     env = dict(os.environ, TMPDIR=str(tmp_path))
     r = subprocess.run([sys.executable, os.path.join(S.ROOT, "bench.py"),
-                        "--no-cpu-baseline"] + args, capture_output=True,
+                        "--full", "--no-cpu-baseline"] + args,
+                       capture_output=True,
                        text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

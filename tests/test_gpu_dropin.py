@@ -158,21 +158,27 @@ def test_seam_cache_keeps_the_last_upload_and_notices_a_change():
         y2 = np.full(M, -1.0)  # pages touched before the clock starts
         xp = x.ctypes.data_as(C.POINTER(C.c_double))
         yp = y2.ctypes.data_as(C.POINTER(C.c_double))
+        # one hit before the clock, like the uncached call above: the first
+        # call after the upload has cost 25 ms of host time once in a process
+        # that ran the config-4 test first (launch + sync, SPMV_DEBUG=1)
+        assert S._lib.csr_spmv_hip_stream(A, xp, yp, None) > 0
         reps = 5
-        t0 = time.perf_counter()
+        calls = []
         for _ in range(reps):
+            t0 = time.perf_counter()
             kms = S._lib.csr_spmv_hip_stream(A, xp, yp, None)
-        wall = (time.perf_counter() - t0) * 1e3 / reps
+            calls.append((time.perf_counter() - t0) * 1e3)
+        wall = sum(calls) / reps
         assert kms > 0
         held, h, m = S.seam_cache_stats()
-        assert (held, h - h0, m - m0) == (1, reps, 1)
+        assert (held, h - h0, m - m0) == (1, 1 + reps, 1)
         assert np.array_equal(y0, y1) and np.array_equal(y0, y2)
         assert S._lib.spmv_live_handles() == base + 1
         # other kernels of the same matrix hit too
         for k in (0, 1, 2, 3):
             yk, _ = S.csr_spmv_hip(A, x, kernel=k)
             assert np.allclose(yk, y0, rtol=1e-12, atol=1e-12)
-        assert S.seam_cache_stats()[1] - h0 == reps + 4
+        assert S.seam_cache_stats()[1] - h0 == 1 + reps + 4
         # x changed in another buffer -> uploaded; same buffer, new content
         # at the head -> the fingerprint notices
         x2 = x * 2.0
@@ -211,7 +217,8 @@ def test_seam_cache_keeps_the_last_upload_and_notices_a_change():
     print("seam cache: %.3f ms per call (uncached %.3f), kernel %.4f ms"
           % (wall, wall_uncached, kms))
     # 0.7 vs 6.4 ms on a quiet box; on a busy host both stretch
-    assert wall < 2.5 or wall < 0.6 * wall_uncached, (wall, wall_uncached)
+    assert wall < 2.5 or wall < 0.6 * wall_uncached, (wall, wall_uncached,
+                                                       calls)
 
 
 def test_seam_cache_level_3_cannot_be_stale_and_levels_1_2_say_what_they_miss():

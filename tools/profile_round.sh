@@ -80,8 +80,8 @@ step python3 tools/shard_counters.py "$round" > /dev/null
 # un-profiled lines of the round
 python3 bench.py --strong --gpus 1 --steps 5 --warmup 2 --no-extras --no-cpu-baseline \
     > "profiles/${round}_strong_1gpu.json" 2> gpurun_out/${round}_strong.err || { echo "FAILED strong"; exit 1; }
-python3 bench.py --config 2 --steps 30 > "profiles/${round}_bench_config2.json" 2> /dev/null || exit 1
-python3 bench.py --config 4 --steps 20 > "profiles/${round}_bench_config4.json" 2> /dev/null || exit 1
-python3 bench.py --steps 20 --warmup 5 > "profiles/${round}_bench_full.json" 2> /dev/null || exit 1
+python3 bench.py --full --config 2 --steps 30 > "profiles/${round}_bench_config2.json" 2> /dev/null || exit 1
+python3 bench.py --full --config 4 --steps 20 > "profiles/${round}_bench_config4.json" 2> /dev/null || exit 1
+python3 bench.py --full --steps 20 --warmup 5 > "profiles/${round}_bench_full.json" 2> /dev/null || exit 1
 keep
 echo "== done"
