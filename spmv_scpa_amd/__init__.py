@@ -502,13 +502,7 @@ _sig("spmv_live_handles", C.c_int)
 _sig("spmv_ignored_releases", C.c_long)
 _sig("spmv_set_debug", None, C.c_int)
 _sig("spmv_handle_generation", C.c_uint64, C.c_void_p)
-_sig("spmv_csr_release_checked", None, C.c_void_p, C.c_uint64)
-_sig("spmv_hll_release_checked", None, C.c_void_p, C.c_uint64)
 _sig("spmv_panel_opts_default", None, C.POINTER(PanelOpts))
-_sig("spmv_csr_tune_times", C.c_int, C.c_void_p, _dp, C.c_int)
-_sig("spmv_hll_tune_times", C.c_int, C.c_void_p, _dp, C.c_int)
-_sig("spmv_csr_tune_log", C.c_int, C.c_void_p, C.c_char_p, C.c_size_t)
-_sig("spmv_hll_tune_log", C.c_int, C.c_void_p, C.c_char_p, C.c_size_t)
 _sig("spmv_device_count", C.c_int)
 _sig("spmv_set_device", C.c_int, C.c_int)
 _sig("spmv_get_device", C.c_int)
@@ -527,64 +521,52 @@ _sig("spmv_dev_fill_synth", C.c_int, C.c_void_p, C.c_int64, C.c_uint64,
 _sig("spmv_csr_upload", C.c_int, _CSRp, C.POINTER(C.c_void_p))
 _sig("spmv_csr_generate", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
      C.c_int64, C.c_int64, C.c_uint64, C.POINTER(C.c_void_p))
-_sig("spmv_csr_launch", C.c_int, C.c_void_p, C.c_int, C.POINTER(LaunchOpts),
-     C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("spmv_csr_launch_rows", C.c_int, C.c_void_p, C.c_int,
      C.POINTER(LaunchOpts), C.c_void_p, C.c_void_p, C.c_int, C.c_int,
      C.c_void_p)
-_sig("spmv_csr_panels_info", C.c_int, C.c_void_p, _ip, _ip, _ip,
-     C.POINTER(C.c_int64))
-_sig("spmv_hll_panels_info", C.c_int, C.c_void_p, _ip, _ip, _ip,
-     C.POINTER(C.c_int64))
-_sig("spmv_csr_autotune", C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-     _ip, _dp)
-_sig("spmv_hll_autotune", C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-     _ip, _dp)
 _sig("spmv_set_panel_schedule", C.c_int, C.c_int)
-_sig("spmv_csr_panels_layout", C.c_int, C.c_void_p, C.POINTER(PanelOpts),
-     C.POINTER(C.c_int))
-_sig("spmv_hll_panels_layout", C.c_int, C.c_void_p, C.POINTER(PanelOpts),
-     C.POINTER(C.c_int))
-_sig("spmv_csr_panels_set_waves", C.c_int, C.c_void_p, C.c_int)
-_sig("spmv_hll_panels_set_waves", C.c_int, C.c_void_p, C.c_int)
-_sig("spmv_csr_build_panels_opts", C.c_int, C.c_void_p, C.POINTER(PanelOpts))
-_sig("spmv_hll_build_panels_opts", C.c_int, C.c_void_p, C.POINTER(PanelOpts))
-_sig("spmv_csr_build_panels", C.c_int, C.c_void_p, C.c_int)
-_sig("spmv_csr_panels_describe", C.c_int, C.c_void_p, C.c_char_p, C.c_size_t)
-_sig("spmv_hll_panels_describe", C.c_int, C.c_void_p, C.c_char_p, C.c_size_t)
-_sig("spmv_csr_panels_tile_rows", C.c_int, C.c_void_p)
-_sig("spmv_hll_panels_tile_rows", C.c_int, C.c_void_p)
-_sig("spmv_csr_build_panels_as", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int)
-_sig("spmv_hll_build_panels_as", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int)
-_sig("spmv_csr_release_source", C.c_int, C.c_void_p)
-_sig("spmv_hll_release_source", C.c_int, C.c_void_p)
-_sig("spmv_csr_panels_schedule", C.c_int, C.c_void_p)
-_sig("spmv_hll_panels_schedule", C.c_int, C.c_void_p)
-_sig("spmv_csr_build_panels_like", C.c_int, C.c_void_p, C.c_void_p)
-_sig("spmv_hll_build_panels_like", C.c_int, C.c_void_p, C.c_void_p)
-_sig("spmv_hll_build_panels", C.c_int, C.c_void_p, C.c_int)
 _sig("spmv_csr_shape", C.c_int, C.c_void_p, _ip, _ip, C.POINTER(C.c_int64))
-_sig("spmv_csr_algorithmic_bytes", C.c_int64, C.c_void_p)
 _sig("spmv_csr_download", C.c_int, C.c_void_p, C.POINTER(_CSRp))
-_sig("spmv_csr_release", None, C.c_void_p)
 _sig("spmv_hll_upload", C.c_int, _HLLp, C.c_int, C.POINTER(C.c_void_p))
 _sig("spmv_hll_from_csr", C.c_int, C.c_void_p, C.c_int,
      C.POINTER(C.c_void_p))
-_sig("spmv_hll_launch", C.c_int, C.c_void_p, C.c_int, C.POINTER(LaunchOpts),
-     C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("spmv_hll_launch_blocks", C.c_int, C.c_void_p, C.c_int,
      C.POINTER(LaunchOpts), C.c_void_p, C.c_void_p, C.c_int, C.c_int,
      C.c_void_p)
 _sig("spmv_hll_shape", C.c_int, C.c_void_p, _ip, _ip, C.POINTER(C.c_int64),
      _ip, C.POINTER(C.c_int64), _ip)
-_sig("spmv_hll_algorithmic_bytes", C.c_int64, C.c_void_p)
 _sig("spmv_hll_kernel_bytes", C.c_int64, C.c_void_p, C.c_int)
-_sig("spmv_hll_release", None, C.c_void_p)
-_sig("spmv_csr_time", C.c_int, C.c_void_p, C.c_int, C.POINTER(LaunchOpts),
-     C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, _dp, C.c_void_p)
-_sig("spmv_hll_time", C.c_int, C.c_void_p, C.c_int, C.POINTER(LaunchOpts),
-     C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, _dp, C.c_void_p)
-
+# spmv_csr_<name> and spmv_hll_<name>: the same argument types
+_TWINS = (
+    ("release_checked", None, C.c_void_p, C.c_uint64),
+    ("tune_times", C.c_int, C.c_void_p, _dp, C.c_int),
+    ("tune_log", C.c_int, C.c_void_p, C.c_char_p, C.c_size_t),
+    ("launch", C.c_int,
+     C.c_void_p, C.c_int, C.POINTER(LaunchOpts), C.c_void_p, C.c_void_p,
+     C.c_void_p),
+    ("panels_info", C.c_int, C.c_void_p, _ip, _ip, _ip, C.POINTER(C.c_int64)),
+    ("autotune", C.c_int,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, _ip, _dp),
+    ("panels_layout", C.c_int,
+     C.c_void_p, C.POINTER(PanelOpts), C.POINTER(C.c_int)),
+    ("panels_set_waves", C.c_int, C.c_void_p, C.c_int),
+    ("build_panels_opts", C.c_int, C.c_void_p, C.POINTER(PanelOpts)),
+    ("build_panels", C.c_int, C.c_void_p, C.c_int),
+    ("panels_describe", C.c_int, C.c_void_p, C.c_char_p, C.c_size_t),
+    ("panels_tile_rows", C.c_int, C.c_void_p),
+    ("build_panels_as", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int),
+    ("release_source", C.c_int, C.c_void_p),
+    ("panels_schedule", C.c_int, C.c_void_p),
+    ("build_panels_like", C.c_int, C.c_void_p, C.c_void_p),
+    ("algorithmic_bytes", C.c_int64, C.c_void_p),
+    ("release", None, C.c_void_p),
+    ("time", C.c_int,
+     C.c_void_p, C.c_int, C.POINTER(LaunchOpts), C.c_void_p, C.c_void_p,
+     C.c_int, C.c_int, C.c_size_t, _dp, C.c_void_p),
+)
+for _f in ("csr", "hll"):
+    for _n, _res, *_args in _TWINS:
+        _sig("spmv_%s_%s" % (_f, _n), _res, *_args)
 
 def declared_symbols():
     """Every function name declared in include/*.h (non-inline)."""
@@ -1228,11 +1210,14 @@ def stream_sync(stream=None):
     _check(_lib.spmv_stream_sync(stream), "spmv_stream_sync")
 
 
-class CsrDevice:
-    """A CSR matrix resident in HBM (spmv_engine.h, spmv_csr_dev)."""
+class _Device:
+    """What CsrDevice and HllDevice share: the handle's lifecycle and the
+    spmv_<fmt>_* calls that differ only in the prefix."""
 
     h = None
     _RANK = 1
+    _FMT = None        # "csr" / "hll"
+    _NUM_KERNELS = 0   # kernel ids of tune_times
 
     def __init__(self, handle):
         self.h = handle
@@ -1243,10 +1228,7 @@ class CsrDevice:
             #               silent no-op and the device memory would leak
             raise OSError(9, "spmv_handle_generation: %r is not a live "
                              "handle of this library" % (self.h,))
-        M, N, NZ = C.c_int(), C.c_int(), C.c_int64()
-        _check(_lib.spmv_csr_shape(self.h, C.byref(M), C.byref(N),
-                                   C.byref(NZ)), "spmv_csr_shape")
-        self.M, self.N, self.NZ = M.value, N.value, NZ.value
+        self._read_shape()
         _live.add(self)
 
     def _released(self):
@@ -1254,6 +1236,111 @@ class CsrDevice:
 
     def _release_now(self):
         self.release()
+
+    def _fn(self, name):
+        return getattr(_lib, "spmv_%s_%s" % (self._FMT, name))
+
+    def _call(self, name, *args):
+        return _check(self._fn(name)(self.h, *args),
+                      "spmv_%s_%s" % (self._FMT, name))
+
+    @property
+    def algorithmic_bytes(self):
+        return self._fn("algorithmic_bytes")(self.h)
+
+    def build_panels(self, panel_cols=0, sched=None, tile_rows=0,
+                     sweep_wgs_per_cu=0, reserve_cus=0, lds_min=0,
+                     sweep_layout=None, deterministic=None):
+        """blocked copy in the process default schedule, or in an explicit
+        one ("steps" / "sweep" / "chain"), with explicit build options
+        (spmv_panel_opts).  The experiment knobs SPMV_TILE_ROWS,
+        SPMV_SWEEP_WGS and SPMV_LDS_MIN of tools/README.md are read HERE, in
+        the harness -- the library itself reads no environment."""
+        o = _panel_opts(panel_cols, sched, tile_rows, sweep_wgs_per_cu,
+                        reserve_cus, lds_min, sweep_layout, deterministic)
+        self._call("build_panels_opts", C.byref(o))
+
+    def panels_tile_rows(self):
+        rc = self._fn("panels_tile_rows")(self.h)
+        return None if rc < 0 else rc
+
+    def panels_describe(self):
+        """one line: schedule, geometry, bucket order, launch shape; None
+        when no blocked copy is built"""
+        buf = C.create_string_buffer(256)
+        rc = self._fn("panels_describe")(self.h, buf, 256)
+        return None if rc else buf.value.decode()
+
+    def panels_pin(self):
+        """the layout of the blocked copy (schedule, tile height, orders,
+        waves) as a string that `build_panels_pinned` rebuilds exactly"""
+        return _layout_pin(self._fn("panels_layout"), self.h)
+
+    def build_panels_pinned(self, pin):
+        o, waves = _pinned_opts(pin)
+        self._call("build_panels_opts", C.byref(o))
+        self._call("panels_set_waves", waves)
+
+    def build_panels_like(self, model):
+        self._call("build_panels_like", model.h)
+
+    def panels_schedule(self):
+        """-> "steps" / "sweep" / "chain", or None when not built"""
+        rc = self._fn("panels_schedule")(self.h)
+        return None if rc < 0 else ("steps", "sweep", "chain")[rc]
+
+    def release_source(self):
+        """keep only the blocked copy (frees JA/AS on the device)"""
+        self._call("release_source")
+
+    def panels_info(self):
+        """-> dict(steps, tiles, panels, entries) or None when not built"""
+        a, b, c, n = C.c_int(), C.c_int(), C.c_int(), C.c_int64()
+        rc = self._fn("panels_info")(self.h, C.byref(a), C.byref(b),
+                                     C.byref(c), C.byref(n))
+        return None if rc else dict(steps=a.value, tiles=b.value,
+                                    panels=c.value, entries=n.value)
+
+    def autotune(self, d_x, d_y, allow_panels=True):
+        """-> (kernel id, median ms) of the fastest kernel for this matrix"""
+        k, ms = C.c_int(), C.c_double()
+        self._call("autotune", d_x, d_y, int(allow_panels), C.byref(k),
+                   C.byref(ms))
+        return k.value, ms.value
+
+    def tune_times(self):
+        """per-kernel median ms of the last autotune (0.0: not a candidate)"""
+        ms = (C.c_double * self._NUM_KERNELS)()
+        self._call("tune_times", ms, self._NUM_KERNELS)
+        return list(ms)
+
+    def tune_log(self):
+        """what the last autotune did (text, one line per phase) or None"""
+        buf = C.create_string_buffer(16384)
+        rc = self._fn("tune_log")(self.h, buf, 16384)
+        return None if rc else buf.value.decode()
+
+    def release(self):
+        h, self.h = self.h, None
+        if h and _closed is False and _lib is not None:
+            self._fn("release_checked")(h, self.gen)
+
+    def __del__(self):
+        if _closed is False:  # None / True at or after interpreter shutdown
+            self.release()
+
+
+class CsrDevice(_Device):
+    """A CSR matrix resident in HBM (spmv_engine.h, spmv_csr_dev)."""
+
+    _FMT = "csr"
+    _NUM_KERNELS = NUM_CSR_KERNELS_ALL
+
+    def _read_shape(self):
+        M, N, NZ = C.c_int(), C.c_int(), C.c_int64()
+        _check(_lib.spmv_csr_shape(self.h, C.byref(M), C.byref(N),
+                                   C.byref(NZ)), "spmv_csr_shape")
+        self.M, self.N, self.NZ = M.value, N.value, NZ.value
 
     @classmethod
     def upload(cls, A):
@@ -1267,10 +1354,6 @@ class CsrDevice:
         _check(_lib.spmv_csr_generate(kind, M, N, K, W, row0, seed,
                                       C.byref(h)), "spmv_csr_generate")
         return cls(h)
-
-    @property
-    def algorithmic_bytes(self):
-        return _lib.spmv_csr_algorithmic_bytes(self.h)
 
     def kernel_bytes(self, kernel):
         """CSR stores no padding: every kernel is priced on the same bytes"""
@@ -1296,84 +1379,6 @@ class CsrDevice:
                                   stream), "spmv_csr_time")
         return ms[:iters]
 
-    def build_panels(self, panel_cols=0, sched=None, tile_rows=0,
-                     sweep_wgs_per_cu=0, reserve_cus=0, lds_min=0,
-                     sweep_layout=None, deterministic=None):
-        """blocked copy in the process default schedule, or in an explicit
-        one ("steps" / "sweep" / "chain"), with explicit build options
-        (spmv_panel_opts).  The experiment knobs SPMV_TILE_ROWS,
-        SPMV_SWEEP_WGS and SPMV_LDS_MIN of tools/README.md are read HERE, in
-        the harness -- the library itself reads no environment."""
-        o = _panel_opts(panel_cols, sched, tile_rows, sweep_wgs_per_cu,
-                        reserve_cus, lds_min, sweep_layout, deterministic)
-        _check(_lib.spmv_csr_build_panels_opts(self.h, C.byref(o)),
-               "spmv_csr_build_panels_opts")
-
-    def panels_tile_rows(self):
-        rc = _lib.spmv_csr_panels_tile_rows(self.h)
-        return None if rc < 0 else rc
-
-    def panels_describe(self):
-        """one line: schedule, geometry, bucket order, launch shape; None
-        when no blocked copy is built"""
-        buf = C.create_string_buffer(256)
-        rc = _lib.spmv_csr_panels_describe(self.h, buf, 256)
-        return None if rc else buf.value.decode()
-
-    def panels_pin(self):
-        """the layout of the blocked copy (schedule, tile height, orders,
-        waves) as a string that `build_panels_pinned` rebuilds exactly"""
-        return _layout_pin(_lib.spmv_csr_panels_layout, self.h)
-
-    def build_panels_pinned(self, pin):
-        o, waves = _pinned_opts(pin)
-        _check(_lib.spmv_csr_build_panels_opts(self.h, C.byref(o)),
-               "spmv_csr_build_panels_opts")
-        _check(_lib.spmv_csr_panels_set_waves(self.h, waves),
-               "spmv_csr_panels_set_waves")
-
-    def build_panels_like(self, model):
-        _check(_lib.spmv_csr_build_panels_like(self.h, model.h),
-               "spmv_csr_build_panels_like")
-
-    def panels_schedule(self):
-        """-> "steps" / "sweep" / "chain", or None when not built"""
-        rc = _lib.spmv_csr_panels_schedule(self.h)
-        return None if rc < 0 else ("steps", "sweep", "chain")[rc]
-
-    def release_source(self):
-        """keep only the blocked copy (frees JA/AS on the device)"""
-        _check(_lib.spmv_csr_release_source(self.h), "spmv_csr_release_source")
-
-    def panels_info(self):
-        """-> dict(steps, tiles, panels, entries) or None when not built"""
-        a, b, c, n = C.c_int(), C.c_int(), C.c_int(), C.c_int64()
-        rc = _lib.spmv_csr_panels_info(self.h, C.byref(a), C.byref(b),
-                                       C.byref(c), C.byref(n))
-        return None if rc else dict(steps=a.value, tiles=b.value,
-                                    panels=c.value, entries=n.value)
-
-    def autotune(self, d_x, d_y, allow_panels=True):
-        """-> (kernel id, median ms) of the fastest kernel for this matrix"""
-        k, ms = C.c_int(), C.c_double()
-        _check(_lib.spmv_csr_autotune(self.h, d_x, d_y, int(allow_panels),
-                                      C.byref(k), C.byref(ms)),
-               "spmv_csr_autotune")
-        return k.value, ms.value
-
-    def tune_times(self):
-        """per-kernel median ms of the last autotune (0.0: not a candidate)"""
-        ms = (C.c_double * NUM_CSR_KERNELS_ALL)()
-        _check(_lib.spmv_csr_tune_times(self.h, ms, NUM_CSR_KERNELS_ALL),
-               "spmv_csr_tune_times")
-        return list(ms)
-
-    def tune_log(self):
-        """what the last autotune did (text, one line per phase) or None"""
-        buf = C.create_string_buffer(16384)
-        rc = _lib.spmv_csr_tune_log(self.h, buf, 16384)
-        return None if rc else buf.value.decode()
-
     def download(self):
         p = _CSRp()
         _check(_lib.spmv_csr_download(self.h, C.byref(p)), "spmv_csr_download")
@@ -1385,36 +1390,14 @@ class CsrDevice:
                "spmv_hll_from_csr")
         return HllDevice(h)
 
-    def release(self):
-        h, self.h = self.h, None
-        if h and _closed is False and _lib is not None:
-            _lib.spmv_csr_release_checked(h, self.gen)
 
-    def __del__(self):
-        if _closed is False:  # None / True at or after interpreter shutdown
-            self.release()
-
-
-class HllDevice:
+class HllDevice(_Device):
     """An HLL matrix resident in HBM (spmv_engine.h, spmv_hll_dev)."""
 
-    h = None
-    _RANK = 1
+    _FMT = "hll"
+    _NUM_KERNELS = NUM_HLL_KERNELS_ALL
 
-    def _released(self):
-        return not self.h
-
-    def _release_now(self):
-        self.release()
-
-    def __init__(self, handle):
-        self.h = handle
-        self.gen = _lib.spmv_handle_generation(self.h)
-        if not self.gen:  # not a live handle: release_checked would be a
-            #               silent no-op and the device memory would leak
-            raise OSError(9, "spmv_handle_generation: %r is not a live "
-                             "handle of this library" % (self.h,))
-        _live.add(self)
+    def _read_shape(self):
         M, N, NZ = C.c_int(), C.c_int(), C.c_int64()
         nb, S, cm = C.c_int(), C.c_int64(), C.c_int()
         _check(_lib.spmv_hll_shape(self.h, C.byref(M), C.byref(N),
@@ -1430,88 +1413,6 @@ class HllDevice:
         _check(_lib.spmv_hll_upload(H, int(col_major), C.byref(h)),
                "spmv_hll_upload")
         return cls(h)
-
-    def build_panels(self, panel_cols=0, sched=None, tile_rows=0,
-                     sweep_wgs_per_cu=0, reserve_cus=0, lds_min=0,
-                     sweep_layout=None, deterministic=None):
-        """blocked copy in the process default schedule, or in an explicit
-        one ("steps" / "sweep" / "chain"), with explicit build options
-        (spmv_panel_opts).  The experiment knobs SPMV_TILE_ROWS,
-        SPMV_SWEEP_WGS and SPMV_LDS_MIN of tools/README.md are read HERE, in
-        the harness -- the library itself reads no environment."""
-        o = _panel_opts(panel_cols, sched, tile_rows, sweep_wgs_per_cu,
-                        reserve_cus, lds_min, sweep_layout, deterministic)
-        _check(_lib.spmv_hll_build_panels_opts(self.h, C.byref(o)),
-               "spmv_hll_build_panels_opts")
-
-    def panels_tile_rows(self):
-        rc = _lib.spmv_hll_panels_tile_rows(self.h)
-        return None if rc < 0 else rc
-
-    def panels_describe(self):
-        """one line: schedule, geometry, bucket order, launch shape; None
-        when no blocked copy is built"""
-        buf = C.create_string_buffer(256)
-        rc = _lib.spmv_hll_panels_describe(self.h, buf, 256)
-        return None if rc else buf.value.decode()
-
-    def panels_pin(self):
-        """the layout of the blocked copy (schedule, tile height, orders,
-        waves) as a string that `build_panels_pinned` rebuilds exactly"""
-        return _layout_pin(_lib.spmv_hll_panels_layout, self.h)
-
-    def build_panels_pinned(self, pin):
-        o, waves = _pinned_opts(pin)
-        _check(_lib.spmv_hll_build_panels_opts(self.h, C.byref(o)),
-               "spmv_hll_build_panels_opts")
-        _check(_lib.spmv_hll_panels_set_waves(self.h, waves),
-               "spmv_hll_panels_set_waves")
-
-    def build_panels_like(self, model):
-        _check(_lib.spmv_hll_build_panels_like(self.h, model.h),
-               "spmv_hll_build_panels_like")
-
-    def panels_schedule(self):
-        """-> "steps" / "sweep" / "chain", or None when not built"""
-        rc = _lib.spmv_hll_panels_schedule(self.h)
-        return None if rc < 0 else ("steps", "sweep", "chain")[rc]
-
-    def release_source(self):
-        """keep only the blocked copy (frees JA/AS on the device)"""
-        _check(_lib.spmv_hll_release_source(self.h), "spmv_hll_release_source")
-
-    def panels_info(self):
-        """-> dict(steps, tiles, panels, entries) or None when not built"""
-        a, b, c, n = C.c_int(), C.c_int(), C.c_int(), C.c_int64()
-        rc = _lib.spmv_hll_panels_info(self.h, C.byref(a), C.byref(b),
-                                       C.byref(c), C.byref(n))
-        return None if rc else dict(steps=a.value, tiles=b.value,
-                                    panels=c.value, entries=n.value)
-
-    def autotune(self, d_x, d_y, allow_panels=True):
-        """-> (kernel id, median ms) of the fastest kernel for this matrix"""
-        k, ms = C.c_int(), C.c_double()
-        _check(_lib.spmv_hll_autotune(self.h, d_x, d_y, int(allow_panels),
-                                      C.byref(k), C.byref(ms)),
-               "spmv_hll_autotune")
-        return k.value, ms.value
-
-    def tune_times(self):
-        """per-kernel median ms of the last autotune (0.0: not a candidate)"""
-        ms = (C.c_double * NUM_HLL_KERNELS_ALL)()
-        _check(_lib.spmv_hll_tune_times(self.h, ms, NUM_HLL_KERNELS_ALL),
-               "spmv_hll_tune_times")
-        return list(ms)
-
-    def tune_log(self):
-        """what the last autotune did (text, one line per phase) or None"""
-        buf = C.create_string_buffer(16384)
-        rc = _lib.spmv_hll_tune_log(self.h, buf, 16384)
-        return None if rc else buf.value.decode()
-
-    @property
-    def algorithmic_bytes(self):
-        return _lib.spmv_hll_algorithmic_bytes(self.h)
 
     def kernel_bytes(self, kernel):
         """bytes one launch of `kernel` must move: 12 per STORED slot for the
@@ -1537,15 +1438,6 @@ class HllDevice:
                                   iters, flush_bytes, ms.ctypes.data_as(_dp),
                                   stream), "spmv_hll_time")
         return ms[:iters]
-
-    def release(self):
-        h, self.h = self.h, None
-        if h and _closed is False and _lib is not None:
-            _lib.spmv_hll_release_checked(h, self.gen)
-
-    def __del__(self):
-        if _closed is False:  # None / True at or after interpreter shutdown
-            self.release()
 
 
 # ---------------------------------------------------------------- vectors

@@ -23,6 +23,7 @@
 #include "hip_common.h"
 #include "hip_csr.h"
 #include "hip_hll.h"
+#include "mat_ref.h"
 #include "spmv_synth.h"
 #include "stream_table.h"
 #include "tune_blocked.h"
@@ -196,28 +197,23 @@ uint64_t spmv_handle_generation(const void *handle) {
  * a foreign launch number and a count.  The next launches must not care
  * (epoch_arrive, hip_common.h).  Returns the counters touched, < 0 on error.
  */
+static int stale_arrivals(unsigned long long *cnt, int n, spmv_panels *P) {
+    if (cnt && n > 0)
+        HIP_RET(hipMemset(cnt, 0x01, (size_t)n * sizeof(unsigned long long)));
+    else
+        n = 0;
+    const int p = panels_debug_stale_arrivals(P);
+    return p < 0 ? p : n + p;
+}
+
 int spmv_csr_debug_stale_arrivals(spmv_csr_dev *A) {
     HANDLE_OK(A);
-    int n = 0;
-    if (A->seg_count && A->n_rowblk > 0) {
-        HIP_RET(hipMemset(A->seg_count, 0x01,
-                          (size_t)A->n_rowblk * sizeof(unsigned long long)));
-        n += A->n_rowblk;
-    }
-    const int p = panels_debug_stale_arrivals(A->panels);
-    return p < 0 ? p : n + p;
+    return stale_arrivals(A->seg_count, A->n_rowblk, A->panels);
 }
 
 int spmv_hll_debug_stale_arrivals(spmv_hll_dev *H) {
     HANDLE_OK(H);
-    int n = 0;
-    if (H->wide_cnt && H->n_wide_seg > 0) {
-        HIP_RET(hipMemset(H->wide_cnt, 0x01,
-                          (size_t)H->n_wide_seg * sizeof(unsigned long long)));
-        n += H->n_wide_seg;
-    }
-    const int p = panels_debug_stale_arrivals(H->panels);
-    return p < 0 ? p : n + p;
+    return stale_arrivals(H->wide_cnt, H->n_wide_seg, H->panels);
 }
 
 /* 1..16; 0 (or less) returns to the size-based default above */
@@ -773,7 +769,7 @@ int spmv_dev_fill_synth(double *d_x, int64_t n, uint64_t seed, int64_t first,
 /* CSR handle                                                           */
 /* ------------------------------------------------------------------ */
 
-static void csr_teardown(spmv_csr_dev *d) {
+static void teardown(spmv_csr_dev *d) {
     (void)hipFree(d->irp);
     (void)hipFree(d->ja);
     (void)hipFree(d->as);
@@ -785,16 +781,6 @@ static void csr_teardown(spmv_csr_dev *d) {
     panels_free(d->panels);
     free(d->tune_log);
     free(d);
-}
-
-void spmv_csr_release(spmv_csr_dev *d) {
-    if (d && live_take(d)) /* else: ignored, counted (spmv_ignored_releases) */
-        csr_teardown(d);
-}
-
-void spmv_csr_release_checked(spmv_csr_dev *d, uint64_t generation) {
-    if (d && generation && live_take(d, generation))
-        csr_teardown(d);
 }
 
 static int csr_alloc_dev(int M, int N, int64_t NZ, spmv_csr_dev **out) {
@@ -993,280 +979,11 @@ fail:
     return rc;
 }
 
-int spmv_csr_build_panels(spmv_csr_dev *A, int panel_cols) {
-    HANDLE_OK(A);
-    if (!A->ja && A->NZ > 0)
-        return -ENODATA;
-    panels_free(A->panels);
-    A->panels = NULL;
-    return panels_from_csr(A, panel_cols, -1, 0, &A->panels);
-}
-
-int spmv_hll_build_panels(spmv_hll_dev *H, int panel_cols) {
-    HANDLE_OK(H);
-    if (!H->ja && H->slots > 0)
-        return -ENODATA;
-    panels_free(H->panels);
-    H->panels = NULL;
-    return panels_from_hll(H, panel_cols, -1, 0, &H->panels);
-}
-
-int spmv_csr_build_panels_opts(spmv_csr_dev *A, const spmv_panel_opts *opts) {
-    HANDLE_OK(A);
-    if (!A->ja && A->NZ > 0)
-        return -ENODATA;
-    panels_free(A->panels);
-    A->panels = NULL;
-    return panels_from_csr_opts(A, opts, &A->panels);
-}
-
-int spmv_hll_build_panels_opts(spmv_hll_dev *H, const spmv_panel_opts *opts) {
-    HANDLE_OK(H);
-    if (!H->ja && H->slots > 0)
-        return -ENODATA;
-    panels_free(H->panels);
-    H->panels = NULL;
-    return panels_from_hll_opts(H, opts, &H->panels);
-}
-
-/* same schedule and tile height as `model`'s blocked copy (shards of one
- * matrix: tune one, build the others alike) */
-int spmv_csr_build_panels_like(spmv_csr_dev *A, const spmv_csr_dev *model) {
-    HANDLE_OK(A);
-    HANDLE_OK(model);
-    if (!model->panels)
-        return -EINVAL;
-    if (!A->ja && A->NZ > 0)
-        return -ENODATA;
-    panels_free(A->panels);
-    A->panels = NULL;
-    spmv_panel_opts o;
-    panels_get_opts(model->panels, &o);
-    int rc = panels_from_csr_opts(A, &o, &A->panels);
-    if (!rc)
-        panels_set_waves(A->panels, panels_waves(model->panels));
-    return rc;
-}
-
-int spmv_hll_build_panels_like(spmv_hll_dev *H, const spmv_hll_dev *model) {
-    HANDLE_OK(H);
-    HANDLE_OK(model);
-    if (!model->panels)
-        return -EINVAL;
-    if (!H->ja && H->slots > 0)
-        return -ENODATA;
-    panels_free(H->panels);
-    H->panels = NULL;
-    spmv_panel_opts o;
-    panels_get_opts(model->panels, &o);
-    int rc = panels_from_hll_opts(H, &o, &H->panels);
-    if (!rc)
-        panels_set_waves(H->panels, panels_waves(model->panels));
-    return rc;
-}
-
-static int panels_info(const spmv_panels *P, int *steps, int *tiles,
-                       int *panels, int64_t *entries) {
-    if (!P)
-        return -ENOENT; /* not built */
-    if (steps)
-        *steps = panels_steps(P);
-    if (tiles)
-        *tiles = panels_tiles(P);
-    if (panels)
-        *panels = panels_count(P);
-    if (entries)
-        *entries = panels_nnz(P);
-    return 0;
-}
-
-int spmv_csr_panels_info(const spmv_csr_dev *A, int *steps, int *tiles,
-                         int *panels, int64_t *entries) {
-    HANDLE_OK(A);
-    return panels_info(A->panels, steps, tiles, panels, entries);
-}
-
-/*
- * Keep only the blocked copy: frees JA/AS (12 B per entry), so a handle that
- * runs the blocked path costs the same HBM as the format it came from.
- * Afterwards only the PANELS kernel id can be launched; the direct kernels,
- * download, conversion and further build_panels calls return -ENODATA.
- */
-int spmv_csr_release_source(spmv_csr_dev *A) {
-    HANDLE_OK(A);
-    if (!A->panels)
-        return -ENOENT; /* nothing else could run the matrix */
-    (void)hipFree(A->ja);
-    (void)hipFree(A->as);
-    A->ja = NULL;
-    A->as = NULL;
-    return 0;
-}
-
-int spmv_hll_release_source(spmv_hll_dev *H) {
-    HANDLE_OK(H);
-    if (!H->panels)
-        return -ENOENT;
-    (void)hipFree(H->ja);
-    (void)hipFree(H->as);
-    (void)hipFree(H->padmask);
-    H->ja = NULL;
-    H->as = NULL;
-    H->padmask = NULL;
-    return 0;
-}
-
-static int panels_schedule_of(const spmv_panels *P) {
-    if (!P)
-        return -ENOENT;
-    return panels_is_sweep(P) ? 1 : panels_is_chain(P) ? 2 : 0;
-}
-
-int spmv_csr_panels_schedule(const spmv_csr_dev *A) {
-    HANDLE_OK(A);
-    return panels_schedule_of(A->panels);
-}
-
-int spmv_hll_panels_schedule(const spmv_hll_dev *H) {
-    HANDLE_OK(H);
-    return panels_schedule_of(H->panels);
-}
-
-int spmv_csr_panels_describe(const spmv_csr_dev *A, char *buf, size_t len) {
-    HANDLE_OK(A);
-    return A->panels ? panels_describe(A->panels, buf, len) : -ENOENT;
-}
-
-int spmv_hll_panels_describe(const spmv_hll_dev *H, char *buf, size_t len) {
-    HANDLE_OK(H);
-    return H->panels ? panels_describe(H->panels, buf, len) : -ENOENT;
-}
-
-int spmv_csr_panels_tile_rows(const spmv_csr_dev *A) {
-    HANDLE_OK(A);
-    return A->panels ? panels_tile_rows(A->panels) : -ENOENT;
-}
-
-int spmv_hll_panels_tile_rows(const spmv_hll_dev *H) {
-    HANDLE_OK(H);
-    return H->panels ? panels_tile_rows(H->panels) : -ENOENT;
-}
-
-/* The layout of the blocked copy as build options + the launch's waves hint:
- * build_panels_opts(o) followed by panels_set_waves(waves) on another handle
- * of the same matrix reproduces exactly what the selector settled on (the
- * profiling passes of a workload pin the layout of the un-profiled run this
- * way: under the counters' serialised launches the selector may pick another
- * candidate).  The caller sets o->struct_size = sizeof *o first. */
-static int panels_layout_of(const spmv_panels *P, spmv_panel_opts *o,
-                            int *waves) {
-    if (!o || o->struct_size != (int)sizeof *o)
-        return -EINVAL;
-    if (!P)
-        return -ENOENT;
-    panels_get_opts(P, o);
-    if (waves)
-        *waves = panels_waves(P);
-    return 0;
-}
-
-int spmv_csr_panels_layout(const spmv_csr_dev *A, spmv_panel_opts *o, int *waves) {
-    HANDLE_OK(A);
-    return panels_layout_of(A->panels, o, waves);
-}
-
-int spmv_hll_panels_layout(const spmv_hll_dev *H, spmv_panel_opts *o, int *waves) {
-    HANDLE_OK(H);
-    return panels_layout_of(H->panels, o, waves);
-}
-
-/* waves per workgroup of the blocked launch (0: the kernel's default) */
-int spmv_csr_panels_set_waves(spmv_csr_dev *A, int waves) {
-    HANDLE_OK(A);
-    if (!A->panels)
-        return -ENOENT;
-    if (waves < 0 || waves > 16)
-        return -EINVAL;
-    panels_set_waves(A->panels, waves);
-    return 0;
-}
-
-int spmv_hll_panels_set_waves(spmv_hll_dev *H, int waves) {
-    HANDLE_OK(H);
-    if (!H->panels)
-        return -ENOENT;
-    if (waves < 0 || waves > 16)
-        return -EINVAL;
-    panels_set_waves(H->panels, waves);
-    return 0;
-}
-
-/* explicit schedule (0 steps, 1 sweep, 2 chain) and tile height (0: default;
- * ignored by sweep): ranks of a multi-GPU job build what rank 0 tuned */
-int spmv_csr_build_panels_as(spmv_csr_dev *A, int panel_cols, int sched,
-                             int tile_rows) {
-    HANDLE_OK(A);
-    if (sched < 0 || sched > 2)
-        return -EINVAL;
-    if (!A->ja && A->NZ > 0)
-        return -ENODATA;
-    panels_free(A->panels);
-    A->panels = NULL;
-    return panels_from_csr(A, panel_cols, sched, tile_rows, &A->panels);
-}
-
-int spmv_hll_build_panels_as(spmv_hll_dev *H, int panel_cols, int sched,
-                             int tile_rows) {
-    HANDLE_OK(H);
-    if (sched < 0 || sched > 2)
-        return -EINVAL;
-    if (!H->ja && H->slots > 0)
-        return -ENODATA;
-    panels_free(H->panels);
-    H->panels = NULL;
-    return panels_from_hll(H, panel_cols, sched, tile_rows, &H->panels);
-}
-
-int spmv_hll_panels_info(const spmv_hll_dev *H, int *steps, int *tiles,
-                         int *panels, int64_t *entries) {
-    HANDLE_OK(H);
-    return panels_info(H->panels, steps, tiles, panels, entries);
-}
-
-int spmv_csr_launch_rows(const spmv_csr_dev *A, int kernel,
-                         const spmv_launch_opts *opts, const double *d_x,
-                         double *d_y, int row_begin, int row_end,
-                         void *stream) {
-    HANDLE_OK(A);
-    if (kernel == SPMV_CSR_KERNEL_PANELS) {
-        if (!A->panels || row_begin != 0 || row_end != A->M)
-            return -EINVAL; /* build panels first; whole matrix only */
-        return panels_launch(A->panels, A->M,
-                             opts ? opts->waves_per_block : 0,
-                             opts ? opts->variant : 0, d_x, d_y,
-                             (hipStream_t)stream);
-    }
-    if (!A->ja && A->NZ > 0)
-        return -ENODATA; /* spmv_csr_release_source(): blocked path only */
-    return csr_launch_kernel(A, kernel,
-                             pick_waves(opts, default_waves(g_csr_waves, A->M)),
-                             opts ? opts->group : 0, opts ? opts->variant : 0,
-                             d_x, d_y, row_begin,
-                             row_end, (hipStream_t)stream);
-}
-
-int spmv_csr_launch(const spmv_csr_dev *A, int kernel,
-                    const spmv_launch_opts *opts, const double *d_x,
-                    double *d_y, void *stream) {
-    HANDLE_OK(A);
-    return spmv_csr_launch_rows(A, kernel, opts, d_x, d_y, 0, A->M, stream);
-}
-
 /* ------------------------------------------------------------------ */
 /* HLL handle                                                           */
 /* ------------------------------------------------------------------ */
 
-static void hll_teardown(spmv_hll_dev *d) {
+static void teardown(spmv_hll_dev *d) {
     (void)hipFree(d->ja);
     (void)hipFree(d->as);
     (void)hipFree(d->off);
@@ -1277,16 +994,6 @@ static void hll_teardown(spmv_hll_dev *d) {
     panels_free(d->panels);
     free(d->tune_log);
     free(d);
-}
-
-void spmv_hll_release(spmv_hll_dev *d) {
-    if (d && live_take(d))
-        hll_teardown(d);
-}
-
-void spmv_hll_release_checked(spmv_hll_dev *d, uint64_t generation) {
-    if (d && generation && live_take(d, generation))
-        hll_teardown(d);
 }
 
 static int hll_alloc_dev(int M, int N, int64_t NZ, int nb, int col_major,
@@ -1562,36 +1269,246 @@ int64_t spmv_hll_kernel_bytes(const spmv_hll_dev *H, int kernel) {
            8 * (int64_t)H->N;
 }
 
-int spmv_hll_launch_blocks(const spmv_hll_dev *H, int kernel,
-                           const spmv_launch_opts *opts, const double *d_x,
-                           double *d_y, int blk_begin, int blk_end,
-                           void *stream) {
-    HANDLE_OK(H);
+} /* extern "C" */
+
+/* ------------------------------------------------------------------ */
+/* one body for both handle types                                      */
+/* ------------------------------------------------------------------ */
+
+/* where the two formats differ */
+static bool has_source(const spmv_csr_dev *A) { return A->ja || A->NZ == 0; }
+static bool has_source(const spmv_hll_dev *H) { return H->ja || H->slots == 0; }
+static int units(const spmv_csr_dev *A) { return A->M; }  /* launch ranges: */
+static int units(const spmv_hll_dev *H) { return H->nb; } /* rows / blocks */
+static int blocked_kernel(const spmv_csr_dev *) {
+    return SPMV_CSR_KERNEL_PANELS;
+}
+static int blocked_kernel(const spmv_hll_dev *) {
+    return SPMV_HLL_KERNEL_PANELS;
+}
+static int64_t algorithmic_bytes(const spmv_csr_dev *A) {
+    return spmv_csr_algorithmic_bytes(A);
+}
+static int64_t algorithmic_bytes(const spmv_hll_dev *H) {
+    return spmv_hll_algorithmic_bytes(H);
+}
+static int build_from(const spmv_csr_dev *A, int panel_cols, int sched,
+                      int tile_rows, spmv_panels **out) {
+    return panels_from_csr(A, panel_cols, sched, tile_rows, out);
+}
+static int build_from(const spmv_hll_dev *H, int panel_cols, int sched,
+                      int tile_rows, spmv_panels **out) {
+    return panels_from_hll(H, panel_cols, sched, tile_rows, out);
+}
+static int build_from(const spmv_csr_dev *A, const spmv_panel_opts *o,
+                      spmv_panels **out) {
+    return panels_from_csr_opts(A, o, out);
+}
+static int build_from(const spmv_hll_dev *H, const spmv_panel_opts *o,
+                      spmv_panels **out) {
+    return panels_from_hll_opts(H, o, out);
+}
+static void free_source(spmv_csr_dev *A) {
+    (void)hipFree(A->ja);
+    (void)hipFree(A->as);
+    A->ja = NULL;
+    A->as = NULL;
+}
+static void free_source(spmv_hll_dev *H) {
+    (void)hipFree(H->ja);
+    (void)hipFree(H->as);
+    (void)hipFree(H->padmask);
+    H->ja = NULL;
+    H->as = NULL;
+    H->padmask = NULL;
+}
+static int launch_direct(const spmv_csr_dev *A, int kernel,
+                         const spmv_launch_opts *opts, const double *d_x,
+                         double *d_y, int r0, int r1, hipStream_t s) {
+    return csr_launch_kernel(A, kernel,
+                             pick_waves(opts, default_waves(g_csr_waves, A->M)),
+                             opts ? opts->group : 0, opts ? opts->variant : 0,
+                             d_x, d_y, r0, r1, s);
+}
+static int launch_direct(const spmv_hll_dev *H, int kernel,
+                         const spmv_launch_opts *opts, const double *d_x,
+                         double *d_y, int b0, int b1, hipStream_t s) {
     int waves = pick_waves(opts, default_waves(g_hll_waves, H->M));
-    if (kernel == SPMV_HLL_KERNEL_PANELS) {
-        if (!H->panels || blk_begin != 0 || blk_end != H->nb)
+    if (kernel == 1 && waves > 8)
+        waves = 8; /* 6 KiB of LDS per wavefront, stay under 64 KiB */
+    return hll_launch_kernel(H, kernel, waves, opts ? opts->variant : 0, d_x,
+                             d_y, b0, b1, s);
+}
+
+template <typename D> static void release(D *d) {
+    if (d && live_take(d)) /* else: ignored, counted (spmv_ignored_releases) */
+        teardown(d);
+}
+
+template <typename D> static void release_checked(D *d, uint64_t generation) {
+    if (d && generation && live_take(d, generation))
+        teardown(d);
+}
+
+/* rows (CSR) or hack blocks (HLL) [begin, end) */
+template <typename D>
+static int launch_range(const D *d, int kernel, const spmv_launch_opts *opts,
+                        const double *d_x, double *d_y, int begin, int end,
+                        void *stream) {
+    HANDLE_OK(d);
+    if (kernel == blocked_kernel(d)) {
+        if (!d->panels || begin != 0 || end != units(d))
             return -EINVAL; /* build panels first; whole matrix only */
-        return panels_launch(H->panels, H->M,
+        return panels_launch(d->panels, d->M,
                              opts ? opts->waves_per_block : 0,
                              opts ? opts->variant : 0, d_x, d_y,
                              (hipStream_t)stream);
     }
-    if (!H->ja && H->slots > 0)
-        return -ENODATA; /* spmv_hll_release_source(): blocked path only */
-    if (kernel == 1 && waves > 8)
-        waves = 8; /* 6 KiB of LDS per wavefront, stay under 64 KiB */
-    return hll_launch_kernel(H, kernel, waves, opts ? opts->variant : 0, d_x,
-                             d_y, blk_begin, blk_end, (hipStream_t)stream);
+    if (!has_source(d))
+        return -ENODATA; /* spmv_*_release_source(): blocked path only */
+    return launch_direct(d, kernel, opts, d_x, d_y, begin, end,
+                         (hipStream_t)stream);
 }
 
-int spmv_hll_launch(const spmv_hll_dev *H, int kernel,
-                    const spmv_launch_opts *opts, const double *d_x,
-                    double *d_y, void *stream) {
-    HANDLE_OK(H);
-    return spmv_hll_launch_blocks(H, kernel, opts, d_x, d_y, 0, H->nb, stream);
+template <typename D>
+static int launch(const D *d, int kernel, const spmv_launch_opts *opts,
+                  const double *d_x, double *d_y, void *stream) {
+    HANDLE_OK(d);
+    return launch_range(d, kernel, opts, d_x, d_y, 0, units(d), stream);
 }
 
-} /* extern "C" */
+/* a new blocked copy in place of the old one: `build(&d->panels)` */
+template <typename D, typename Build> static int rebuild(D *d, Build build) {
+    if (!has_source(d))
+        return -ENODATA;
+    panels_free(d->panels);
+    d->panels = NULL;
+    return build(&d->panels);
+}
+
+template <typename D> static int build_panels(D *d, int panel_cols) {
+    HANDLE_OK(d);
+    return rebuild(d, [&](spmv_panels **out) {
+        return build_from(d, panel_cols, -1, 0, out);
+    });
+}
+
+template <typename D>
+static int build_panels_opts(D *d, const spmv_panel_opts *opts) {
+    HANDLE_OK(d);
+    return rebuild(d,
+                   [&](spmv_panels **out) { return build_from(d, opts, out); });
+}
+
+/* explicit schedule (0 steps, 1 sweep, 2 chain) and tile height (0: default;
+ * ignored by sweep): ranks of a multi-GPU job build what rank 0 tuned */
+template <typename D>
+static int build_panels_as(D *d, int panel_cols, int sched, int tile_rows) {
+    HANDLE_OK(d);
+    if (sched < 0 || sched > 2)
+        return -EINVAL;
+    return rebuild(d, [&](spmv_panels **out) {
+        return build_from(d, panel_cols, sched, tile_rows, out);
+    });
+}
+
+/* same schedule and tile height as `model`'s blocked copy (shards of one
+ * matrix: tune one, build the others alike) */
+template <typename D> static int build_panels_like(D *d, const D *model) {
+    HANDLE_OK(d);
+    HANDLE_OK(model);
+    if (!model->panels)
+        return -EINVAL;
+    int rc = rebuild(d, [&](spmv_panels **out) {
+        spmv_panel_opts o;
+        panels_get_opts(model->panels, &o);
+        return build_from(d, &o, out);
+    });
+    if (!rc)
+        panels_set_waves(d->panels, panels_waves(model->panels));
+    return rc;
+}
+
+template <typename D>
+static int info_of(const D *d, int *steps, int *tiles, int *panels,
+                       int64_t *entries) {
+    HANDLE_OK(d);
+    const spmv_panels *P = d->panels;
+    if (!P)
+        return -ENOENT; /* not built */
+    if (steps)
+        *steps = panels_steps(P);
+    if (tiles)
+        *tiles = panels_tiles(P);
+    if (panels)
+        *panels = panels_count(P);
+    if (entries)
+        *entries = panels_nnz(P);
+    return 0;
+}
+
+/*
+ * Keep only the blocked copy: frees JA/AS (12 B per entry), so a handle that
+ * runs the blocked path costs the same HBM as the format it came from.
+ * Afterwards only the PANELS kernel id can be launched; the direct kernels,
+ * download, conversion and further build_panels calls return -ENODATA.
+ */
+template <typename D> static int release_source(D *d) {
+    HANDLE_OK(d);
+    if (!d->panels)
+        return -ENOENT; /* nothing else could run the matrix */
+    free_source(d);
+    return 0;
+}
+
+template <typename D> static int schedule_of(const D *d) {
+    HANDLE_OK(d);
+    if (!d->panels)
+        return -ENOENT;
+    return panels_is_sweep(d->panels) ? 1 : panels_is_chain(d->panels) ? 2 : 0;
+}
+
+template <typename D>
+static int describe_of(const D *d, char *buf, size_t len) {
+    HANDLE_OK(d);
+    return d->panels ? panels_describe(d->panels, buf, len) : -ENOENT;
+}
+
+template <typename D> static int tile_rows_of(const D *d) {
+    HANDLE_OK(d);
+    return d->panels ? panels_tile_rows(d->panels) : -ENOENT;
+}
+
+/* The layout of the blocked copy as build options + the launch's waves hint:
+ * build_panels_opts(o) followed by panels_set_waves(waves) on another handle
+ * of the same matrix reproduces exactly what the selector settled on (the
+ * profiling passes of a workload pin the layout of the un-profiled run this
+ * way: under the counters' serialised launches the selector may pick another
+ * candidate).  The caller sets o->struct_size = sizeof *o first. */
+template <typename D>
+static int layout_of(const D *d, spmv_panel_opts *o, int *waves) {
+    HANDLE_OK(d);
+    if (!o || o->struct_size != (int)sizeof *o)
+        return -EINVAL;
+    if (!d->panels)
+        return -ENOENT;
+    panels_get_opts(d->panels, o);
+    if (waves)
+        *waves = panels_waves(d->panels);
+    return 0;
+}
+
+/* waves per workgroup of the blocked launch (0: the kernel's default) */
+template <typename D> static int set_waves_of(D *d, int waves) {
+    HANDLE_OK(d);
+    if (!d->panels)
+        return -ENOENT;
+    if (waves < 0 || waves > 16)
+        return -EINVAL;
+    panels_set_waves(d->panels, waves);
+    return 0;
+}
+
 
 /* ------------------------------------------------------------------ */
 /* event-timed loops                                                    */
@@ -1663,33 +1580,19 @@ fail:
     return rc;
 }
 
-extern "C" {
-
-int spmv_csr_time(const spmv_csr_dev *A, int kernel,
-                  const spmv_launch_opts *opts, const double *d_x, double *d_y,
-                  int warmup, int iters, size_t flush_bytes, double *ms_each,
-                  void *stream) {
-    HANDLE_OK(A); /* before the scratch buffer of the flush is allocated */
+template <typename D>
+static int time_launches(const D *d, int kernel, const spmv_launch_opts *opts,
+                         const double *d_x, double *d_y, int warmup, int iters,
+                         size_t flush_bytes, double *ms_each, void *stream) {
+    HANDLE_OK(d); /* before the scratch buffer of the flush is allocated */
     if (iters < 0 || warmup < 0 || (iters && !ms_each))
         return -EINVAL;
     return timed_loop(
-        [&]() { return spmv_csr_launch(A, kernel, opts, d_x, d_y, stream); },
+        [&]() { return launch(d, kernel, opts, d_x, d_y, stream); },
         warmup, iters, flush_bytes, ms_each, (hipStream_t)stream,
         opts && (opts->variant & SPMV_VARIANT_FLUSH_RMW));
 }
 
-int spmv_hll_time(const spmv_hll_dev *H, int kernel,
-                  const spmv_launch_opts *opts, const double *d_x, double *d_y,
-                  int warmup, int iters, size_t flush_bytes, double *ms_each,
-                  void *stream) {
-    HANDLE_OK(H);
-    if (iters < 0 || warmup < 0 || (iters && !ms_each))
-        return -EINVAL;
-    return timed_loop(
-        [&]() { return spmv_hll_launch(H, kernel, opts, d_x, d_y, stream); },
-        warmup, iters, flush_bytes, ms_each, (hipStream_t)stream,
-        opts && (opts->variant & SPMV_VARIANT_FLUSH_RMW));
-}
 
 /* ------------------------------------------------------------------ */
 /* kernel selection by measurement                                      */
@@ -1710,28 +1613,91 @@ static size_t tune_flush_bytes(int64_t algorithmic_bytes) {
     return algorithmic_bytes < ((int64_t)512 << 20) ? (size_t)1 << 30 : 0;
 }
 
-int spmv_hll_autotune(spmv_hll_dev *H, const double *d_x, double *d_y,
-                      int allow_panels, int *best_kernel, double *best_ms) {
-    HANDLE_OK(H);
-    if (!best_kernel)
-        return -EINVAL;
-    const int cand_cm[2] = {1, 2}, cand_rm[2] = {3, 0};
-    const int *cand = H->col_major ? cand_cm : cand_rm;
+/* what the phases of one selector run share */
+struct tune_run {
+    const double *d_x;
+    double *d_y;
+    size_t flush;
+    /* ONE scratch buffer for the cache flush of every timed loop (a 1 GiB
+     * hipMalloc + memset + hipFree per loop otherwise) */
+    flush_scratch scratch;
+    std::vector<double> ms = std::vector<double>(5);
     int best = -1;
     double bms = 1e300;
-    std::vector<double> ms(5);
-    const size_t flush = tune_flush_bytes(spmv_hll_algorithmic_bytes(H));
-    int best_order = H->order;
     tune_log log;
     char line[200];
-    const double t_begin = panels_ops::now_s();
-    memset(H->tune_ms, 0, sizeof H->tune_ms);
-    /* ONE scratch buffer for the cache flush of every timed loop below (a
-     * 1 GiB hipMalloc + memset + hipFree per loop otherwise) */
-    flush_scratch scratch;
-    int rc = scratch.reserve(flush);
+    double t_begin;
+    tune_run(const double *x, double *y, size_t f)
+        : d_x(x), d_y(y), flush(f), t_begin(panels_ops::now_s()) {}
+    template <typename Launch> int time(Launch l, int warm, int iters) {
+        return timed_loop(l, warm, iters, flush, ms.data(), NULL, false,
+                          &scratch);
+    }
+};
+
+/* One selector run: the format's direct kernels (`direct`: times them, fills
+ * d->tune_ms, t.best / t.bms and logs its line), then the blocked
+ * candidates, then the result. */
+template <typename D, typename Direct>
+static int autotune(D *d, const double *d_x, double *d_y, int allow_panels,
+                    int *best_kernel, double *best_ms, Direct direct) {
+    HANDLE_OK(d);
+    if (!best_kernel)
+        return -EINVAL;
+    tune_run t(d_x, d_y, tune_flush_bytes(algorithmic_bytes(d)));
+    memset(d->tune_ms, 0, sizeof d->tune_ms);
+    int rc = t.scratch.reserve(t.flush);
     if (rc)
         return rc;
+    rc = direct(d, t);
+    if (rc)
+        return rc;
+    if (allow_panels) {
+        const double stream_ms =
+            (double)algorithmic_bytes(d) / 7.0e9; /* at 7 TB/s */
+        panels_pool_begin(); /* candidates reuse each other's blocks */
+        rc = tune_blocked<spmv_panels, panels_ops>(
+            &d->panels, d->M, d->M > 0 ? (double)d->NZ / d->M : 0.0, stream_ms,
+            &t.bms,
+            [&](int sched, int tile_rows, spmv_panels **out) {
+                return build_from(d, 0, sched, tile_rows, out);
+            },
+            [&](double *m) {
+                int r = t.time(
+                    [&]() {
+                        return launch(d, blocked_kernel(d), NULL, d_x, d_y,
+                                      NULL);
+                    },
+                    1, 5);
+                *m = median_of(t.ms);
+                return r;
+            },
+            [&](const char *l) { t.log(l); }); /* by reference */
+        panels_pool_end();
+        if (rc < 0)
+            return rc;
+        if (rc > 0) {
+            t.best = blocked_kernel(d);
+            d->tune_ms[t.best] = t.bms;
+        }
+    }
+    snprintf(t.line, sizeof t.line, "total %.3f s",
+             panels_ops::now_s() - t.t_begin);
+    t.log(t.line);
+    free(d->tune_log);
+    d->tune_log = t.log.release();
+    *best_kernel = t.best;
+    if (best_ms)
+        *best_ms = t.bms;
+    return 0;
+}
+
+/* HLL candidates: kernels 1 and 2 (col-major) or 3 and 0 (row-major), the
+ * col-major ones in their three workgroup orders */
+static int hll_direct(spmv_hll_dev *H, tune_run &t) {
+    const int cand_cm[2] = {1, 2}, cand_rm[2] = {3, 0};
+    const int *cand = H->col_major ? cand_cm : cand_rm;
+    int best_order = H->order;
     int iters = 5, warm = 1;
     {
         /* probe: ONE launch of the first candidate.  Beyond 10 ms (a hack
@@ -1741,12 +1707,14 @@ int spmv_hll_autotune(spmv_hll_dev *H, const double *d_x, double *d_y,
         spmv_launch_opts o;
         memset(&o, 0, sizeof o);
         o.variant = 1;
-        rc = timed_loop(
-            [&]() { return spmv_hll_launch(H, cand[0], &o, d_x, d_y, NULL); }, 0,
-            1, flush, ms.data(), NULL, false, &scratch);
+        int rc = t.time(
+            [&]() {
+                return spmv_hll_launch(H, cand[0], &o, t.d_x, t.d_y, NULL);
+            },
+            0, 1);
         if (rc)
             return rc;
-        if (ms[0] > 10.0) {
+        if (t.ms[0] > 10.0) {
             iters = 1;
             warm = 0;
         }
@@ -1761,66 +1729,33 @@ int spmv_hll_autotune(spmv_hll_dev *H, const double *d_x, double *d_y,
             /* 5 launches each -- 1 once a launch has run beyond 10 ms (a hack
              * block as wide as a hub row of 10^5 entries: 40-60 ms per
              * launch, 1.8 s for the six combinations otherwise) */
-            rc = timed_loop(
-                [&]() { return spmv_hll_launch(H, cand[k], &o, d_x, d_y, NULL); },
-                warm, iters, flush, ms.data(), NULL, false, &scratch);
+            int rc = t.time(
+                [&]() {
+                    return spmv_hll_launch(H, cand[k], &o, t.d_x, t.d_y, NULL);
+                },
+                warm, iters);
             if (rc)
                 return rc;
-            double m = median_of(std::vector<double>(ms.begin(), ms.begin() + iters));
+            double m = median_of(
+                std::vector<double>(t.ms.begin(), t.ms.begin() + iters));
             if (m > 10.0)
                 iters = 1;
             if (H->tune_ms[cand[k]] == 0.0 || m < H->tune_ms[cand[k]])
                 H->tune_ms[cand[k]] = m;
             /* another order has to win by 2 % over hardware order */
-            if (m < (order == 0 || best != cand[k] ? bms : 0.98 * bms)) {
-                bms = m;
-                best = cand[k];
+            if (m < (order == 0 || t.best != cand[k] ? t.bms : 0.98 * t.bms)) {
+                t.bms = m;
+                t.best = cand[k];
                 best_order = order;
             }
         }
     H->order = best_order;
-    snprintf(line, sizeof line,
+    snprintf(t.line, sizeof t.line,
              "direct kernels: %.3f s; slots / nnz = %.3f (padding of the "
              "format), widest hack block %d",
-             panels_ops::now_s() - t_begin,
+             panels_ops::now_s() - t.t_begin,
              H->NZ > 0 ? (double)H->slots / (double)H->NZ : 0.0, H->max_width);
-    log(line);
-    if (allow_panels) {
-        const double stream_ms =
-            (double)spmv_hll_algorithmic_bytes(H) / 7.0e9; /* at 7 TB/s */
-        panels_pool_begin(); /* candidates reuse each other's blocks */
-        rc = tune_blocked<spmv_panels, panels_ops>(
-            &H->panels, H->M, H->M > 0 ? (double)H->NZ / H->M : 0.0, stream_ms,
-            &bms,
-            [&](int sched, int tile_rows, spmv_panels **out) {
-                return panels_from_hll(H, 0, sched, tile_rows, out);
-            },
-            [&](double *m) {
-                int r = timed_loop(
-                    [&]() {
-                        return spmv_hll_launch(H, SPMV_HLL_KERNEL_PANELS, NULL,
-                                               d_x, d_y, NULL);
-                    },
-                    1, 5, flush, ms.data(), NULL, false, &scratch);
-                *m = median_of(ms);
-                return r;
-            },
-            [&](const char *l) { log(l); }); /* by reference */
-        panels_pool_end();
-        if (rc < 0)
-            return rc;
-        if (rc > 0) {
-            best = SPMV_HLL_KERNEL_PANELS;
-            H->tune_ms[SPMV_HLL_KERNEL_PANELS] = bms;
-        }
-    }
-    snprintf(line, sizeof line, "total %.3f s", panels_ops::now_s() - t_begin);
-    log(line);
-    free(H->tune_log);
-    H->tune_log = log.release();
-    *best_kernel = best;
-    if (best_ms)
-        *best_ms = bms;
+    t.log(t.line);
     return 0;
 }
 
@@ -1839,25 +1774,10 @@ int spmv_hll_autotune(spmv_hll_dev *H, const double *d_x, double *d_y,
  *                    there when that runs beyond 20x the best so far.
  * profiles/r04_autotune_irregular.txt records what wins where.
  */
-int spmv_csr_autotune(spmv_csr_dev *A, const double *d_x, double *d_y,
-                      int allow_panels, int *best_kernel, double *best_ms) {
-    HANDLE_OK(A);
-    if (!best_kernel)
-        return -EINVAL;
+static int csr_direct(spmv_csr_dev *A, tune_run &t) {
     const double mean = A->M > 0 ? (double)A->NZ / A->M : 0.0;
     const int cand[5] = {4, 2, 1, 0, 3}; /* stream first: it is never the slow one */
-    int best = -1;
-    double bms = 1e300;
-    std::vector<double> ms(5);
-    const size_t flush = tune_flush_bytes(spmv_csr_algorithmic_bytes(A));
-    tune_log log;
-    char line[200];
-    const double t_begin = panels_ops::now_s();
-    memset(A->tune_ms, 0, sizeof A->tune_ms);
-    flush_scratch scratch;
-    int rc = scratch.reserve(flush);
-    if (rc)
-        return rc;
+    int rc = 0;
     /* 5 launches per configuration -- 1 once any launch has run beyond 10 ms
      * (a hub row of 10^5 entries under the sub-wave kernel: 46 ms x 3 orders
      * x 6 launches was most of a 1.2 s selector run) */
@@ -1867,10 +1787,12 @@ int spmv_csr_autotune(spmv_csr_dev *A, const double *d_x, double *d_y,
         memset(&o, 0, sizeof o);
         o.variant = variant;
         iters = std::min(iters, iters_cap);
-        int r = timed_loop(
-            [&]() { return spmv_csr_launch(A, kernel, &o, d_x, d_y, NULL); }, 1,
-            iters, flush, ms.data(), NULL, false, &scratch);
-        *m = median_of(std::vector<double>(ms.begin(), ms.begin() + iters));
+        int r = t.time(
+            [&]() {
+                return spmv_csr_launch(A, kernel, &o, t.d_x, t.d_y, NULL);
+            },
+            1, iters);
+        *m = median_of(std::vector<double>(t.ms.begin(), t.ms.begin() + iters));
         if (*m > 10.0)
             iters_cap = 1;
         return r;
@@ -1911,7 +1833,7 @@ int spmv_csr_autotune(spmv_csr_dev *A, const double *d_x, double *d_y,
              * rows, or one lane walking a row of 10^5 entries, can be orders
              * of magnitude off -- then one sample is the answer */
             rc = time_k(cand[k], 0, 1, &m);
-            if (!rc && m < 20.0 * bms)
+            if (!rc && m < 20.0 * t.bms)
                 rc = time_k(cand[k], 0, cand[k] == 3 ? 2 : 5, &m);
             if (rc)
                 return rc;
@@ -1921,96 +1843,118 @@ int spmv_csr_autotune(spmv_csr_dev *A, const double *d_x, double *d_y,
                 return rc;
         }
         A->tune_ms[cand[k]] = m;
-        if (m < bms) {
-            bms = m;
-            best = cand[k];
+        if (m < t.bms) {
+            t.bms = m;
+            t.best = cand[k];
         }
     }
-    snprintf(line, sizeof line,
+    snprintf(t.line, sizeof t.line,
              "direct kernels: %.3f s; mean row %.2f, longest %d; ms: "
              "thread_row %.4f wave_row %.4f subwave_row %.4f block_row %.4f "
              "stream %.4f (0 = not a candidate)",
-             panels_ops::now_s() - t_begin, mean, A->max_row_len,
+             panels_ops::now_s() - t.t_begin, mean, A->max_row_len,
              A->tune_ms[0], A->tune_ms[1], A->tune_ms[2], A->tune_ms[3],
              A->tune_ms[4]);
-    log(line);
-    if (allow_panels) {
-        const double stream_ms = (double)spmv_csr_algorithmic_bytes(A) / 7.0e9;
-        panels_pool_begin(); /* candidates reuse each other's blocks */
-        rc = tune_blocked<spmv_panels, panels_ops>(
-            &A->panels, A->M, mean, stream_ms, &bms,
-            [&](int sched, int tile_rows, spmv_panels **out) {
-                return panels_from_csr(A, 0, sched, tile_rows, out);
-            },
-            [&](double *m) {
-                int r = timed_loop(
-                    [&]() {
-                        return spmv_csr_launch(A, SPMV_CSR_KERNEL_PANELS, NULL,
-                                               d_x, d_y, NULL);
-                    },
-                    1, 5, flush, ms.data(), NULL, false, &scratch);
-                *m = median_of(ms);
-                return r;
-            },
-            [&](const char *l) { log(l); }); /* by reference */
-        panels_pool_end();
-        if (rc < 0)
-            return rc;
-        if (rc > 0) {
-            best = SPMV_CSR_KERNEL_PANELS;
-            A->tune_ms[SPMV_CSR_KERNEL_PANELS] = bms;
-        }
-    }
-    snprintf(line, sizeof line, "total %.3f s", panels_ops::now_s() - t_begin);
-    log(line);
-    free(A->tune_log);
-    A->tune_log = log.release();
-    *best_kernel = best;
-    if (best_ms)
-        *best_ms = bms;
+    t.log(t.line);
     return 0;
 }
 
 /* per-kernel medians of the last spmv_*_autotune (ms; 0 = not a candidate),
  * kernel ids 0 .. n-1 */
-int spmv_csr_tune_times(const spmv_csr_dev *A, double *ms, int n) {
-    HANDLE_OK(A);
+template <typename D> static int tune_times(const D *d, double *ms, int n) {
+    HANDLE_OK(d);
     if (!ms || n < 0)
         return -EINVAL;
     for (int k = 0; k < n; ++k)
-        ms[k] = k < 8 ? A->tune_ms[k] : 0.0;
-    return 0;
-}
-
-int spmv_hll_tune_times(const spmv_hll_dev *H, double *ms, int n) {
-    HANDLE_OK(H);
-    if (!ms || n < 0)
-        return -EINVAL;
-    for (int k = 0; k < n; ++k)
-        ms[k] = k < 8 ? H->tune_ms[k] : 0.0;
-    return 0;
-}
-
-static int copy_log(const char *log, char *buf, size_t len) {
-    if (!buf || !len)
-        return -EINVAL;
-    if (!log)
-        return -ENOENT; /* never tuned */
-    snprintf(buf, len, "%s", log);
+        ms[k] = k < 8 ? d->tune_ms[k] : 0.0;
     return 0;
 }
 
 /* what the last spmv_*_autotune did, one line per phase with host-clock
  * seconds (build / timing per blocked candidate); -ENOENT before any */
-int spmv_csr_tune_log(const spmv_csr_dev *A, char *buf, size_t len) {
-    HANDLE_OK(A);
-    return copy_log(A->tune_log, buf, len);
+template <typename D>
+static int copy_tune_log(const D *d, char *buf, size_t len) {
+    HANDLE_OK(d);
+    if (!buf || !len)
+        return -EINVAL;
+    if (!d->tune_log)
+        return -ENOENT; /* never tuned */
+    snprintf(buf, len, "%s", d->tune_log);
+    return 0;
 }
 
-int spmv_hll_tune_log(const spmv_hll_dev *H, char *buf, size_t len) {
-    HANDLE_OK(H);
-    return copy_log(H->tune_log, buf, len);
-}
+/* The exported twins (include/spmv_engine.h): spmv_csr_* and spmv_hll_*
+ * forward to the one body above; `range` names the partial launch
+ * (launch_rows: rows, launch_blocks: hack blocks) */
+#define HANDLE_API(fmt, D, range)                                              \
+    void spmv_##fmt##_release(D *d) { release(d); }                            \
+    void spmv_##fmt##_release_checked(D *d, uint64_t generation) {             \
+        release_checked(d, generation);                                        \
+    }                                                                          \
+    int spmv_##fmt##_launch(const D *d, int kernel,                            \
+                            const spmv_launch_opts *opts, const double *d_x,   \
+                            double *d_y, void *stream) {                       \
+        return launch(d, kernel, opts, d_x, d_y, stream);                      \
+    }                                                                          \
+    int spmv_##fmt##_##range(const D *d, int kernel,                           \
+                             const spmv_launch_opts *opts, const double *d_x,  \
+                             double *d_y, int begin, int end, void *stream) {  \
+        return launch_range(d, kernel, opts, d_x, d_y, begin, end, stream);    \
+    }                                                                          \
+    int spmv_##fmt##_time(const D *d, int kernel,                              \
+                          const spmv_launch_opts *opts, const double *d_x,     \
+                          double *d_y, int warmup, int iters,                  \
+                          size_t flush_bytes, double *ms_each, void *stream) { \
+        return time_launches(d, kernel, opts, d_x, d_y, warmup, iters,         \
+                             flush_bytes, ms_each, stream);                    \
+    }                                                                          \
+    int spmv_##fmt##_build_panels(D *d, int panel_cols) {                      \
+        return build_panels(d, panel_cols);                                    \
+    }                                                                          \
+    int spmv_##fmt##_build_panels_opts(D *d, const spmv_panel_opts *opts) {    \
+        return build_panels_opts(d, opts);                                     \
+    }                                                                          \
+    int spmv_##fmt##_build_panels_as(D *d, int panel_cols, int sched,          \
+                                     int tile_rows) {                          \
+        return build_panels_as(d, panel_cols, sched, tile_rows);               \
+    }                                                                          \
+    int spmv_##fmt##_build_panels_like(D *d, const D *model) {                 \
+        return build_panels_like(d, model);                                    \
+    }                                                                          \
+    int spmv_##fmt##_panels_info(const D *d, int *steps, int *tiles,           \
+                                 int *panels, int64_t *entries) {              \
+        return info_of(d, steps, tiles, panels, entries);                      \
+    }                                                                          \
+    int spmv_##fmt##_release_source(D *d) { return release_source(d); }        \
+    int spmv_##fmt##_panels_schedule(const D *d) { return schedule_of(d); }    \
+    int spmv_##fmt##_panels_describe(const D *d, char *buf, size_t len) {      \
+        return describe_of(d, buf, len);                                       \
+    }                                                                          \
+    int spmv_##fmt##_panels_tile_rows(const D *d) { return tile_rows_of(d); }  \
+    int spmv_##fmt##_panels_layout(const D *d, spmv_panel_opts *o,             \
+                                   int *waves) {                               \
+        return layout_of(d, o, waves);                                         \
+    }                                                                          \
+    int spmv_##fmt##_panels_set_waves(D *d, int waves) {                       \
+        return set_waves_of(d, waves);                                         \
+    }                                                                          \
+    int spmv_##fmt##_autotune(D *d, const double *d_x, double *d_y,            \
+                              int allow_panels, int *best_kernel,              \
+                              double *best_ms) {                               \
+        return autotune(d, d_x, d_y, allow_panels, best_kernel, best_ms,       \
+                        fmt##_direct);                                         \
+    }                                                                          \
+    int spmv_##fmt##_tune_times(const D *d, double *ms, int n) {               \
+        return tune_times(d, ms, n);                                           \
+    }                                                                          \
+    int spmv_##fmt##_tune_log(const D *d, char *buf, size_t len) {             \
+        return copy_tune_log(d, buf, len);                                     \
+    }
+
+extern "C" {
+
+HANDLE_API(csr, spmv_csr_dev, launch_rows)
+HANDLE_API(hll, spmv_hll_dev, launch_blocks)
 
 /* ------------------------------------------------------------------ */
 /* one-shot entry points: the reference's seam (hip_csr.h / hip_hll.h)  */
@@ -2038,8 +1982,7 @@ struct seam_slot {
                               uncached path and the reference's seam always
                               use the current device) */
     uint64_t print;        /* fingerprint of the matrix */
-    spmv_csr_dev *csr;
-    spmv_hll_dev *hll;
+    mat_ref dev;           /* the device copy */
     double *d_x, *d_y;
     int M, N;
     const double *x_host;  /* level 2: the x that d_x holds */
@@ -2150,15 +2093,13 @@ static uint64_t fp_level(uint64_t h, const void *p, size_t n, size_t item);
 /* releases what the slot holds, with the device that owns it current */
 static void seam_drop(seam_slot *c) {
     int cur = -1;
-    const bool held = c->csr || c->hll || c->d_x || c->d_y;
+    const bool held = c->dev || c->d_x || c->d_y;
     if (held && hipGetDevice(&cur) == hipSuccess && cur != c->device)
         (void)hipSetDevice(c->device);
     else
         cur = -1;
-    if (c->csr)
-        spmv_csr_release(c->csr);
-    if (c->hll)
-        spmv_hll_release(c->hll);
+    if (c->dev)
+        c->dev.release();
     (void)hipFree(c->d_x);
     (void)hipFree(c->d_y);
     if (cur >= 0)
@@ -2191,7 +2132,7 @@ int spmv_seam_cache_invalidate(const void *host) {
     std::lock_guard<std::mutex> g(g_seam.mu);
     int n = 0;
     for (seam_slot &c : g_seam.slot) {
-        if (!(c.csr || c.hll))
+        if (!c.dev)
             continue;
         if (!host || c.host == host) {
             seam_drop(&c);
@@ -2212,7 +2153,7 @@ int spmv_seam_cache_stats(long *hits, long *misses) {
         *misses = g_seam.misses;
     int held = 0;
     for (const seam_slot &c : g_seam.slot)
-        held += c.csr || c.hll;
+        held += c.dev ? 1 : 0;
     return held;
 }
 
@@ -2240,7 +2181,7 @@ static int seam_acquire(int which, const void *host, uint64_t print, int M,
     seam_slot *c = &g_seam.slot[which];
     int dev = 0;
     HIP_RET(hipGetDevice(&dev));
-    const bool hit = (c->csr || c->hll) && c->host == host && c->print == print &&
+    const bool hit = c->dev && c->host == host && c->print == print &&
                      c->M == M && c->N == N && c->device == dev;
     if (!hit) {
         seam_drop(c);
@@ -2285,10 +2226,17 @@ fail:
     return rc;
 }
 
-static double csr_one_shot(const sparse_csr *A, const double *x, double *y,
-                           void *arg, int kernel) {
-    if (!A || !x || !y)
-        return -EINVAL;
+} /* extern "C" */
+
+/* a seam call once its arguments are checked: with the cache on (the
+ * caller's `fingerprint` of the matrix, under g_seam.mu) the device copy of
+ * slot `which`, else an upload -> vectors -> one timed launch -> y download
+ * -> release of its own.  `what` names the format in the spmv_set_debug
+ * timing line of the cached call (NULL: no line). */
+template <typename D, typename Print, typename Upload>
+static double one_shot(int which, const void *host, int M, int N,
+                       const double *x, double *y, void *arg, int kernel,
+                       Print fingerprint, Upload upload, const char *what) {
     const spmv_launch_opts *opts = (const spmv_launch_opts *)arg;
     double ms = 0.0;
     int rc = 0;
@@ -2296,60 +2244,75 @@ static double csr_one_shot(const sparse_csr *A, const double *x, double *y,
         std::unique_lock<std::mutex> g(g_seam.mu);
         if (g_seam.level > 0) {
             const double t0s = panels_ops::now_s();
-            uint64_t fp = fp_mix(fp_mix(fp_mix(0x637372, (uint64_t)A->M),
-                                        (uint64_t)A->N), (uint64_t)A->NZ);
-            fp = fp_level(fp, A->IRP, (size_t)A->M + 1, sizeof(int));
-            fp = fp_level(fp, A->JA, (size_t)A->NZ, sizeof(int));
-            fp = fp_level(fp, A->AS, (size_t)A->NZ, sizeof(double));
+            const uint64_t fp = fingerprint();
             seam_slot *c = NULL;
             const double t1 = panels_ops::now_s();
-            rc = seam_acquire(0, A, fp, A->M, A->N, x,
+            rc = seam_acquire(which, host, fp, M, N, x,
                               [&](seam_slot *s) {
-                                  return spmv_csr_upload(A, &s->csr);
+                                  D *d = NULL;
+                                  const int r = upload(&d);
+                                  s->dev = mat_ref::of(d);
+                                  return r;
                               },
                               &c);
             const double t2 = panels_ops::now_s();
             if (!rc)
-                rc = spmv_csr_time(c->csr, kernel, opts, c->d_x, c->d_y, 0, 1, 0,
-                                   &ms, NULL);
+                rc = time_launches((const D *)c->dev.h, kernel, opts, c->d_x,
+                                   c->d_y, 0, 1, 0, &ms, NULL);
             const double t3 = panels_ops::now_s();
-            if (!rc && A->M > 0)
-                rc = spmv_copy_d2h(y, c->d_y, (size_t)A->M * sizeof(double));
-            if (live().debug) /* where a cached call spends its host time */
+            if (!rc && M > 0)
+                rc = spmv_copy_d2h(y, c->d_y, (size_t)M * sizeof(double));
+            /* where a cached call spends its host time */
+            if (what && live().debug)
                 fprintf(stderr,
-                        "spmv seam cache (csr): fingerprint %.3f ms, acquire "
+                        "spmv seam cache (%s): fingerprint %.3f ms, acquire "
                         "%.3f, launch + sync %.3f, y download %.3f\n",
-                        (t1 - t0s) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3,
-                        (panels_ops::now_s() - t3) * 1e3);
+                        what, (t1 - t0s) * 1e3, (t2 - t1) * 1e3,
+                        (t3 - t2) * 1e3, (panels_ops::now_s() - t3) * 1e3);
             return rc ? (double)rc : ms;
         }
     }
-    spmv_csr_dev *d = NULL;
+    D *d = NULL;
     double *d_x = NULL, *d_y = NULL;
-    rc = spmv_csr_upload(A, &d);
+    rc = upload(&d);
     if (rc)
         return rc;
-    rc = one_shot_vectors(A->M, A->N, x, &d_x, &d_y);
+    rc = one_shot_vectors(M, N, x, &d_x, &d_y);
     if (!rc)
-        rc = spmv_csr_time(d, kernel, opts, d_x, d_y, 0, 1, 0, &ms, NULL);
-    if (!rc && A->M > 0)
-        rc = spmv_copy_d2h(y, d_y, (size_t)A->M * sizeof(double));
+        rc = time_launches(d, kernel, opts, d_x, d_y, 0, 1, 0, &ms, NULL);
+    if (!rc && M > 0)
+        rc = spmv_copy_d2h(y, d_y, (size_t)M * sizeof(double));
     (void)hipFree(d_x);
     (void)hipFree(d_y);
-    spmv_csr_release(d);
+    release(d);
     return rc ? (double)rc : ms;
+}
+
+extern "C" {
+
+static double csr_one_shot(const sparse_csr *A, const double *x, double *y,
+                           void *arg, int kernel) {
+    if (!A || !x || !y)
+        return -EINVAL;
+    return one_shot<spmv_csr_dev>(
+        0, A, A->M, A->N, x, y, arg, kernel,
+        [&]() {
+            uint64_t fp = fp_mix(fp_mix(fp_mix(0x637372, (uint64_t)A->M),
+                                        (uint64_t)A->N), (uint64_t)A->NZ);
+            fp = fp_level(fp, A->IRP, (size_t)A->M + 1, sizeof(int));
+            fp = fp_level(fp, A->JA, (size_t)A->NZ, sizeof(int));
+            return fp_level(fp, A->AS, (size_t)A->NZ, sizeof(double));
+        },
+        [&](spmv_csr_dev **out) { return spmv_csr_upload(A, out); }, "csr");
 }
 
 static double hll_one_shot(const sparse_hll *H, const double *x, double *y,
                            void *arg, int kernel, int col_major) {
     if (!H || !x || !y)
         return -EINVAL;
-    const spmv_launch_opts *opts = (const spmv_launch_opts *)arg;
-    double ms = 0.0;
-    int rc = 0;
-    {
-        std::unique_lock<std::mutex> g(g_seam.mu);
-        if (g_seam.level > 0) {
+    return one_shot<spmv_hll_dev>(
+        col_major ? 2 : 1, H, H->M, H->N, x, y, arg, kernel,
+        [&]() {
             uint64_t fp = fp_mix(fp_mix(fp_mix(0x686c6c, (uint64_t)H->M),
                                         (uint64_t)H->N), (uint64_t)H->NZ);
             fp = fp_mix(fp, (uint64_t)H->num_blocks);
@@ -2374,34 +2337,10 @@ static double hll_one_shot(const sparse_hll *H, const double *x, double *y,
                     fp = fp_array(fp, b->AS, n, sizeof(double));
                 }
             }
-            seam_slot *c = NULL;
-            rc = seam_acquire(col_major ? 2 : 1, H, fp, H->M, H->N, x,
-                              [&](seam_slot *s) {
-                                  return spmv_hll_upload(H, col_major, &s->hll);
-                              },
-                              &c);
-            if (!rc)
-                rc = spmv_hll_time(c->hll, kernel, opts, c->d_x, c->d_y, 0, 1, 0,
-                                   &ms, NULL);
-            if (!rc && H->M > 0)
-                rc = spmv_copy_d2h(y, c->d_y, (size_t)H->M * sizeof(double));
-            return rc ? (double)rc : ms;
-        }
-    }
-    spmv_hll_dev *d = NULL;
-    double *d_x = NULL, *d_y = NULL;
-    rc = spmv_hll_upload(H, col_major, &d);
-    if (rc)
-        return rc;
-    rc = one_shot_vectors(H->M, H->N, x, &d_x, &d_y);
-    if (!rc)
-        rc = spmv_hll_time(d, kernel, opts, d_x, d_y, 0, 1, 0, &ms, NULL);
-    if (!rc && H->M > 0)
-        rc = spmv_copy_d2h(y, d_y, (size_t)H->M * sizeof(double));
-    (void)hipFree(d_x);
-    (void)hipFree(d_y);
-    spmv_hll_release(d);
-    return rc ? (double)rc : ms;
+            return fp;
+        },
+        [&](spmv_hll_dev **out) { return spmv_hll_upload(H, col_major, out); },
+        NULL);
 }
 
 double csr_spmv_hip_thread_row(const sparse_csr *A, const double *x, double *y,
@@ -2495,3 +2434,61 @@ double hll_spmv_cuda_halfwarp_row(const sparse_hll *H, const double *x,
 }
 
 } /* extern "C" */
+
+/* ------------------------------------------------------------------ */
+/* mat_ref (mat_ref.h): either format through the same bodies          */
+/* ------------------------------------------------------------------ */
+
+template <typename F> static auto on(const mat_ref &m, F f) {
+    return m.is_hll ? f(m.hll()) : f(m.csr());
+}
+
+int64_t mat_ref::algorithmic_bytes() const {
+    return on(*this, [&](auto *d) { return ::algorithmic_bytes(d); });
+}
+int mat_ref::launch(int kernel, const double *d_x, double *d_y,
+                    void *stream) const {
+    return on(*this, [&](auto *d) {
+        return ::launch(d, kernel, NULL, d_x, d_y, stream);
+    });
+}
+int mat_ref::launch_rows(int kernel, const double *d_x, double *d_y, int r0,
+                         int r1, void *stream) const {
+    if (is_hll)
+        return launch_range(hll(), kernel, NULL, d_x, d_y, r0 / HACK_SIZE,
+                            (r1 + HACK_SIZE - 1) / HACK_SIZE, stream);
+    return launch_range(csr(), kernel, NULL, d_x, d_y, r0, r1, stream);
+}
+int mat_ref::autotune(const double *d_x, double *d_y, int allow_panels,
+                      int *best_kernel, double *best_ms) const {
+    if (is_hll)
+        return ::autotune(hll(), d_x, d_y, allow_panels, best_kernel,
+                          best_ms, hll_direct);
+    return ::autotune(csr(), d_x, d_y, allow_panels, best_kernel, best_ms,
+                      csr_direct);
+}
+int mat_ref::build_panels_opts(const spmv_panel_opts *opts) const {
+    return on(*this, [&](auto *d) { return ::build_panels_opts(d, opts); });
+}
+int mat_ref::build_panels_like(mat_ref model) const {
+    if (model.is_hll != is_hll)
+        return -EINVAL;
+    return on(*this, [&](auto *d) {
+        return ::build_panels_like(d, (decltype(d))model.h);
+    });
+}
+int mat_ref::panels_layout(spmv_panel_opts *o, int *waves) const {
+    return on(*this, [&](auto *d) { return layout_of(d, o, waves); });
+}
+int mat_ref::panels_schedule(void) const {
+    return on(*this, [&](auto *d) { return schedule_of(d); });
+}
+int mat_ref::panels_tile_rows(void) const {
+    return on(*this, [&](auto *d) { return tile_rows_of(d); });
+}
+int mat_ref::panels_describe(char *buf, size_t len) const {
+    return on(*this, [&](auto *d) { return describe_of(d, buf, len); });
+}
+void mat_ref::release(void) const {
+    on(*this, [&](auto *d) { ::release(d); });
+}

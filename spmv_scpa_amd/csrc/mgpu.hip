@@ -21,24 +21,25 @@
 
 #include "err.h"
 #include "hip_common.h"
+#include "mat_ref.h"
 #include "spmv_mgpu.h"
 
 struct spmv_mgpu {
     int n;
     int rows_per_gpu; /* equal shards, multiple of 32 (last one padded) */
     int M, N;         /* global shape */
-    int is_hll;
+    int is_hll; /* the shards' format: col-major HLL, else CSR */
     std::vector<int> dev;
     std::vector<hipStream_t> stream;
     std::vector<ncclComm_t> comm;
-    std::vector<spmv_csr_dev *> csr; /* [device]: the shard -- with logical */
-    std::vector<spmv_hll_dev *> hll; /* shards, logical shard 0 of the device */
     /* LOGICAL SHARDS (spmv_mgpu_set_logical_shards): a device's rows as L
      * matrices of rows / L rows each (global columns, local rows), so that a
      * kernel that runs whole matrices only -- the blocked path -- still
      * overlaps: logical shard c of every device is all-gathered on the second
      * stream while shard c+1 computes (the staged pipeline, chunk = shard).
-     * Shards 1 .. L-1 of device r live at [r * (L - 1) + c - 1]. */
+     * Shard c of device r lives at [r * L + c] (shard_at); L = 1: the
+     * device's shard */
+    std::vector<mat_ref> shards;
     int L, want_L, reserve_cus;
     /* exchange ENGINE: 0 = RCCL collectives (kernels on the CUs), 1 = the
      * copy engines -- every device PUSHES its fragment into its peers' y with
@@ -48,8 +49,6 @@ struct spmv_mgpu {
      * shard c run under the kernel of c + 1 without any staging buffer.
      * Rehearsal handles always run this engine (same-device copies). */
     int engine;
-    std::vector<spmv_csr_dev *> xcsr;
-    std::vector<spmv_hll_dev *> xhll;
     std::vector<double *> x, y;
     /* overlapped exchange (spmv_mgpu_set_exchange): the shard's rows in
      * `chunks` equal pieces; chunk c of every device is written into the
@@ -146,56 +145,63 @@ struct device_guard {
     }
 };
 
-/* logical shard c of device r (c = 0: the device's own slot) */
-static spmv_csr_dev *&csr_at(spmv_mgpu *g, int r, int c) {
-    return c == 0 ? g->csr[(size_t)r] : g->xcsr[(size_t)r * (g->L - 1) + c - 1];
+/* logical shard c of device r (L = 1: c = 0, the device's shard) */
+static mat_ref &shard_at(spmv_mgpu *g, int r, int c = 0) {
+    return g->shards[(size_t)r * g->L + c];
 }
-static spmv_hll_dev *&hll_at(spmv_mgpu *g, int r, int c) {
-    return c == 0 ? g->hll[(size_t)r] : g->xhll[(size_t)r * (g->L - 1) + c - 1];
+static const mat_ref &shard_at(const spmv_mgpu *g, int r, int c = 0) {
+    return g->shards[(size_t)r * g->L + c];
+}
+
+/* n x L empty shards of the handle's format */
+static void clear_shards(spmv_mgpu *g) {
+    g->shards.assign((size_t)g->n * g->L, mat_ref{g->is_hll != 0, NULL});
 }
 
 /* shards and vectors of a previous load / generate on this handle */
 static void drop_shards(spmv_mgpu *g) {
     for (int r = 0; r < g->n; ++r) {
         (void)hipSetDevice(g->dev[r]);
-        for (int c = 1; c < g->L; ++c) {
-            if (csr_at(g, r, c))
-                spmv_csr_release(csr_at(g, r, c));
-            if (hll_at(g, r, c))
-                spmv_hll_release(hll_at(g, r, c));
-        }
-        if (g->csr[r])
-            spmv_csr_release(g->csr[r]);
-        if (g->hll[r])
-            spmv_hll_release(g->hll[r]);
+        for (int c = 0; c < g->L; ++c)
+            if (shard_at(g, r, c))
+                shard_at(g, r, c).release();
         (void)hipFree(g->x[r]);
         (void)hipFree(g->y[r]);
         (void)hipFree(g->stage[r]);
         (void)hipFree(g->pad[r]);
-        g->csr[r] = NULL;
-        g->hll[r] = NULL;
         g->x[r] = g->y[r] = g->stage[r] = g->pad[r] = NULL;
     }
     g->rows_per_gpu = g->M = g->N = 0;
     g->ragged = g->longest = 0;
     g->start.assign((size_t)g->n + 1, 0);
-    g->xcsr.clear();
-    g->xhll.clear();
     g->L = 1;
+    clear_shards(g);
 }
 
 /* the logical shards asked for take effect now (a load / generate): needs the
  * even partition with rows per device = L shards of whole hack blocks */
 static int adopt_logical_shards(spmv_mgpu *g) {
     g->L = 1;
-    if (g->want_L <= 1)
-        return 0;
-    if (g->ragged || !g->even || g->rows_per_gpu % (g->want_L * HACK_SIZE))
-        return -EINVAL;
-    g->L = g->want_L;
-    g->xcsr.assign((size_t)g->n * (g->L - 1), NULL);
-    g->xhll.assign((size_t)g->n * (g->L - 1), NULL);
+    if (g->want_L > 1) {
+        if (g->ragged || !g->even || g->rows_per_gpu % (g->want_L * HACK_SIZE))
+            return -EINVAL;
+        g->L = g->want_L;
+    }
+    clear_shards(g);
     return 0;
+}
+
+/* a shard built as CSR becomes the handle's format: col-major HLL or as is */
+static int set_shard(spmv_mgpu *g, int r, int c, spmv_csr_dev *A) {
+    if (!g->is_hll) {
+        shard_at(g, r, c) = mat_ref::of(A);
+        return 0;
+    }
+    spmv_hll_dev *H = NULL;
+    const int rc = spmv_hll_from_csr(A, 1, &H);
+    spmv_csr_release(A);
+    shard_at(g, r, c) = mat_ref::of(H);
+    return rc;
 }
 
 /* a load / generate has succeeded on this handle (vectors exist) */
@@ -203,7 +209,7 @@ static bool mg_loaded(const spmv_mgpu *g) {
     if (!g->y[0] || !g->x[0])
         return false;
     for (int r = 0; r < g->n; ++r)
-        if (g->csr[(size_t)r] || g->hll[(size_t)r])
+        if (shard_at(g, r))
             return true;
     return false;
 }
@@ -262,8 +268,7 @@ static int create(int ngpus, int loopback, spmv_mgpu **out) {
     g->dev.resize(ngpus);
     g->stream.assign(ngpus, NULL);
     g->comm.assign(ngpus, NULL);
-    g->csr.assign(ngpus, NULL);
-    g->hll.assign(ngpus, NULL);
+    g->shards.assign(ngpus, mat_ref{false, NULL});
     g->x.assign(ngpus, NULL);
     g->y.assign(ngpus, NULL);
     g->stage.assign(ngpus, NULL);
@@ -409,12 +414,10 @@ int spmv_mgpu_load_csr_part(spmv_mgpu *g, const sparse_csr *A, int as_hll,
                 rc = PTR_ERR(S);
                 break;
             }
-            rc = spmv_csr_upload(S, &csr_at(g, r, c));
-            if (!rc && as_hll) {
-                rc = spmv_hll_from_csr(csr_at(g, r, c), 1, &hll_at(g, r, c));
-                spmv_csr_release(csr_at(g, r, c));
-                csr_at(g, r, c) = NULL;
-            }
+            spmv_csr_dev *d = NULL;
+            rc = spmv_csr_upload(S, &d);
+            if (!rc)
+                rc = set_shard(g, r, c, d);
             csr_free(S);
         }
     }
@@ -464,14 +467,12 @@ int spmv_mgpu_generate_part(spmv_mgpu *g, int kind, int rows_per_gpu, int K,
             continue;
         const int per = (starts[r + 1] - starts[r]) / g->L;
         for (int c = 0; c < g->L && !rc; ++c) {
+            spmv_csr_dev *d = NULL;
             rc = spmv_csr_generate(kind, per, g->N, K, W,
                                    (int64_t)starts[r] + (int64_t)c * per, seed,
-                                   &csr_at(g, r, c));
-            if (!rc && as_hll) {
-                rc = spmv_hll_from_csr(csr_at(g, r, c), 1, &hll_at(g, r, c));
-                spmv_csr_release(csr_at(g, r, c));
-                csr_at(g, r, c) = NULL;
-            }
+                                   &d);
+            if (!rc)
+                rc = set_shard(g, r, c, d);
         }
     }
     if (!rc)
@@ -535,9 +536,10 @@ int spmv_mgpu_autotune(spmv_mgpu *g, int *kernel) {
         return -EINVAL;
     int rc = 0, pick = -1;
     device_guard keep;
-    const int blocked = g->is_hll ? SPMV_HLL_KERNEL_PANELS : SPMV_CSR_KERNEL_PANELS;
-    if (!g->hll[0] && !g->csr[0])
+    if (!shard_at(g, 0))
         return -EINVAL; /* nothing loaded */
+    const mat_ref model = shard_at(g, 0);
+    const int blocked = model.blocked_kernel();
     {
         /* one host thread per device: the selectors run side by side (a
          * handle per device, a device per thread -- the concurrency the engine
@@ -553,13 +555,11 @@ int spmv_mgpu_autotune(spmv_mgpu *g, int *kernel) {
             double *yfrag = g->y[r] + (size_t)g->start[r];
             int k = -1;
             rcs[(size_t)r] =
-                g->is_hll
-                    ? spmv_hll_autotune(g->hll[r], g->x[r], yfrag, 1, &k, NULL)
-                    : spmv_csr_autotune(g->csr[r], g->x[r], yfrag, 1, &k, NULL);
+                shard_at(g, r).autotune(g->x[r], yfrag, 1, &k, NULL);
             picks[(size_t)r] = k;
         };
         for (int r = 0; r < g->n; ++r) {
-            if (!g->hll[r] && !g->csr[r])
+            if (!shard_at(g, r))
                 continue; /* an empty range */
             try {
                 th.emplace_back(tune, r);
@@ -584,34 +584,24 @@ int spmv_mgpu_autotune(spmv_mgpu *g, int *kernel) {
         int waves = 0;
         spmv_panel_opts_default(&o); /* struct_size: the layout call checks it */
         HIP_TRY(hipSetDevice(g->dev[0]));
-        rc = g->is_hll ? spmv_hll_panels_layout(g->hll[0], &o, &waves)
-                       : spmv_csr_panels_layout(g->csr[0], &o, &waves);
+        rc = model.panels_layout(&o, &waves);
         if (!rc && o.sched == 1) {
             o.reserve_cus = g->reserve_cus;
-            rc = g->is_hll ? spmv_hll_build_panels_opts(g->hll[0], &o)
-                           : spmv_csr_build_panels_opts(g->csr[0], &o);
+            rc = model.build_panels_opts(&o);
         }
     }
     for (int r = 0; r < g->n && !rc && pick == blocked; ++r) {
         HIP_TRY(hipSetDevice(g->dev[r]));
         for (int c = 0; c < g->L && !rc; ++c) {
-            if ((r == 0 && c == 0) || (!hll_at(g, r, c) && !csr_at(g, r, c)))
+            const mat_ref m = shard_at(g, r, c);
+            if ((r == 0 && c == 0) || !m)
                 continue;
-            bool same = false;
-            if (c == 0 && g->L == 1)
-                same = g->is_hll
-                           ? (spmv_hll_panels_schedule(g->hll[r]) ==
-                                  spmv_hll_panels_schedule(g->hll[0]) &&
-                              spmv_hll_panels_tile_rows(g->hll[r]) ==
-                                  spmv_hll_panels_tile_rows(g->hll[0]))
-                           : (spmv_csr_panels_schedule(g->csr[r]) ==
-                                  spmv_csr_panels_schedule(g->csr[0]) &&
-                              spmv_csr_panels_tile_rows(g->csr[r]) ==
-                                  spmv_csr_panels_tile_rows(g->csr[0]));
+            const bool same =
+                c == 0 && g->L == 1 &&
+                m.panels_schedule() == model.panels_schedule() &&
+                m.panels_tile_rows() == model.panels_tile_rows();
             if (!same)
-                rc = g->is_hll
-                         ? spmv_hll_build_panels_like(hll_at(g, r, c), g->hll[0])
-                         : spmv_csr_build_panels_like(csr_at(g, r, c), g->csr[0]);
+                rc = m.build_panels_like(model);
         }
     }
     if (!rc)
@@ -630,10 +620,8 @@ int spmv_mgpu_build_panels(spmv_mgpu *g, const spmv_panel_opts *opts) {
     for (int r = 0; r < g->n && !rc; ++r) {
         HIP_TRY(hipSetDevice(g->dev[r]));
         for (int c = 0; c < g->L && !rc; ++c) {
-            if (!hll_at(g, r, c) && !csr_at(g, r, c))
-                continue;
-            rc = g->is_hll ? spmv_hll_build_panels_opts(hll_at(g, r, c), opts)
-                           : spmv_csr_build_panels_opts(csr_at(g, r, c), opts);
+            if (shard_at(g, r, c))
+                rc = shard_at(g, r, c).build_panels_opts(opts);
         }
     }
 fail:
@@ -714,7 +702,7 @@ __global__ void k_unstage(int world, int k, int ch, const double *stage,
 /* does this launch use the staged pipeline?  direct kernels only (the blocked
  * path runs whole shards), rows divisible into chunks of whole hack blocks */
 static bool staged(const spmv_mgpu *g, int kernel) {
-    const int blocked = g->is_hll ? SPMV_HLL_KERNEL_PANELS : SPMV_CSR_KERNEL_PANELS;
+    const int blocked = shard_at(g, 0).blocked_kernel();
     if (g->engine == 1) /* the copy engine needs no staging: rows in place */
         return false;
     /* logical shards: the shard is the chunk, whatever the kernel */
@@ -749,20 +737,11 @@ static int step_staged(spmv_mgpu *g, int kernel, hipEvent_t *kernels_done) {
             double *slot = g->stage[r] + ((size_t)c * g->n + r) * ch;
             double *ybase = slot - (size_t)c * ch;
             if (g->L > 1) /* a logical shard is a whole matrix: its row 0 */
-                rc = g->is_hll
-                         ? spmv_hll_launch(hll_at(g, r, c), kernel, NULL,
-                                           g->x[r], slot, g->stream[r])
-                         : spmv_csr_launch(csr_at(g, r, c), kernel, NULL,
-                                           g->x[r], slot, g->stream[r]);
+                rc = shard_at(g, r, c).launch(kernel, g->x[r], slot,
+                                              g->stream[r]);
             else
-            rc = g->is_hll
-                     ? spmv_hll_launch_blocks(g->hll[r], kernel, NULL, g->x[r],
-                                              ybase, c * ch / HACK_SIZE,
-                                              (c + 1) * ch / HACK_SIZE,
-                                              g->stream[r])
-                     : spmv_csr_launch_rows(g->csr[r], kernel, NULL, g->x[r],
-                                            ybase, c * ch, (c + 1) * ch,
-                                            g->stream[r]);
+                rc = shard_at(g, r).launch_rows(kernel, g->x[r], ybase, c * ch,
+                                                (c + 1) * ch, g->stream[r]);
             if (rc)
                 break;
             hipEvent_t e = g->ev_k[(size_t)r * MG_MAX_CHUNKS + c];
@@ -804,19 +783,14 @@ fail:
 
 static int launch_shard(spmv_mgpu *g, int r, int kernel) {
     double *yfrag = g->y[r] + (size_t)g->start[r];
-    if (!g->hll[r] && !g->csr[r])
+    if (!shard_at(g, r))
         return 0; /* an empty range */
     if (g->L > 1) { /* logical shards, one after the other, in row order */
         const size_t per = (size_t)g->rows_per_gpu / g->L;
         const bool push = g->engine == 1 && (g->n > 1 || g->force_exchange);
         for (int c = 0; c < g->L; ++c) {
-            int rc =
-                g->is_hll ? spmv_hll_launch(hll_at(g, r, c), kernel, NULL,
-                                            g->x[r], yfrag + c * per,
-                                            g->stream[r])
-                          : spmv_csr_launch(csr_at(g, r, c), kernel, NULL,
-                                            g->x[r], yfrag + c * per,
-                                            g->stream[r]);
+            int rc = shard_at(g, r, c).launch(kernel, g->x[r], yfrag + c * per,
+                                              g->stream[r]);
             /* copy engine: shard c travels while shard c + 1 computes */
             if (!rc && push)
                 rc = push_rows(g, r, g->start[r] + (int)(c * per),
@@ -826,10 +800,7 @@ static int launch_shard(spmv_mgpu *g, int r, int kernel) {
         }
         return 0;
     }
-    return g->is_hll ? spmv_hll_launch(g->hll[r], kernel, NULL, g->x[r], yfrag,
-                                       g->stream[r])
-                     : spmv_csr_launch(g->csr[r], kernel, NULL, g->x[r], yfrag,
-                                       g->stream[r]);
+    return shard_at(g, r).launch(kernel, g->x[r], yfrag, g->stream[r]);
 }
 
 /*
@@ -1083,10 +1054,8 @@ int spmv_mgpu_partition(const spmv_mgpu *g, int *starts, int64_t *entries) {
         starts[r] = g->start[r];
     for (int r = 0; r < g->n && entries; ++r) {
         int64_t nz = 0;
-        spmv_mgpu *m = const_cast<spmv_mgpu *>(g);
         for (int c = 0; c < g->L; ++c)
-            nz += hll_at(m, r, c) ? hll_at(m, r, c)->NZ
-                                  : (csr_at(m, r, c) ? csr_at(m, r, c)->NZ : 0);
+            nz += shard_at(g, r, c) ? shard_at(g, r, c).nz() : 0;
         entries[r] = nz;
     }
     return g->ragged;
@@ -1216,19 +1185,16 @@ int spmv_mgpu_device_bus_id(const spmv_mgpu *g, int rank, char *buf,
 int spmv_mgpu_shard_info(const spmv_mgpu *g, int rank, int64_t *stored,
                          int64_t *alg_bytes, char *layout, size_t len) {
     MG_OK(g);
-    if (!g || rank < 0 || rank >= g->n || (!g->hll[rank] && !g->csr[rank]))
+    if (!g || rank < 0 || rank >= g->n || !shard_at(g, rank))
         return -EINVAL;
     {
         /* summed over the device's logical shards */
-        spmv_mgpu *m = const_cast<spmv_mgpu *>(g);
         int64_t st = 0, by = 0;
         for (int c = 0; c < g->L; ++c) {
-            if (hll_at(m, rank, c)) {
-                st += hll_at(m, rank, c)->slots;
-                by += spmv_hll_algorithmic_bytes(hll_at(m, rank, c));
-            } else if (csr_at(m, rank, c)) {
-                st += csr_at(m, rank, c)->NZ;
-                by += spmv_csr_algorithmic_bytes(csr_at(m, rank, c));
+            const mat_ref m = shard_at(g, rank, c);
+            if (m) {
+                st += m.stored();
+                by += m.algorithmic_bytes();
             }
         }
         if (stored)
@@ -1238,9 +1204,7 @@ int spmv_mgpu_shard_info(const spmv_mgpu *g, int rank, int64_t *stored,
     }
     if (layout && len) {
         layout[0] = 0;
-        const int rc = g->hll[rank]
-                           ? spmv_hll_panels_describe(g->hll[rank], layout, len)
-                           : spmv_csr_panels_describe(g->csr[rank], layout, len);
+        const int rc = shard_at(g, rank).panels_describe(layout, len);
         if (rc && rc != -ENOENT)
             return rc;
     }
@@ -1267,16 +1231,13 @@ int spmv_mgpu_info(const spmv_mgpu *g, int *ngpus, int *rows_per_gpu,
     if (!g)
         return -EINVAL;
     int64_t nz = 0, by = 0;
-    spmv_mgpu *m = const_cast<spmv_mgpu *>(g);
     for (int r = 0; r < g->n; ++r) {
         int64_t b = 0;
         for (int c = 0; c < g->L; ++c) {
-            if (hll_at(m, r, c)) {
-                nz += hll_at(m, r, c)->NZ;
-                b += spmv_hll_algorithmic_bytes(hll_at(m, r, c));
-            } else if (csr_at(m, r, c)) {
-                nz += csr_at(m, r, c)->NZ;
-                b += spmv_csr_algorithmic_bytes(csr_at(m, r, c));
+            const mat_ref m = shard_at(g, r, c);
+            if (m) {
+                nz += m.nz();
+                b += m.algorithmic_bytes();
             }
         }
         if (b > by) /* the heaviest device bounds the step */
