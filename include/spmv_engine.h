@@ -21,9 +21,15 @@
  *         block b at slot offset off[b]; off int64[nb+1]; pads rewritten
  *         (hip_hll.h).  Row- or col-major inside a block, chosen at upload.
  *
+ * Value type of a handle: f64 (AS as above) or f32 (AS stored as float[NZ] /
+ * float[S], spmv_*_upload_f32 / spmv_csr_to_f32): 8 instead of 12 bytes per
+ * entry.  x, y, every product and every sum stay fp64, in the same order: the
+ * result is that of the fp32-rounded matrix, computed in fp64.
+ *
  * Algorithmic bytes per launch (used for roofline.achieved):
  *   CSR   12*NZ + 4*(M+1) + 8*M + 8*N
  *   HLL   12*S + 12*nb + 8*M + 8*N
+ *   f32 handles: 8*NZ + 4*(M+1) + 8*M + 8*N  /  8*S + 12*nb + 8*M + 8*N
  */
 #ifndef SPMV_ENGINE_H
 #define SPMV_ENGINE_H
@@ -144,8 +150,9 @@ typedef struct spmv_panel_opts {
                              having the library read past it.  ABI: the struct
                              grew in library versions 0.3 (bucket_order),
                              0.4 (this field, first) and 0.5 (deterministic,
-                             last; 0.6: its values 0 / 1 / 2); spmv_version() tells
-                             which library is loaded.  Fill the struct with
+                             last; 0.6: its values 0 / 1 / 2; 0.7 added
+                             functions only: the f32 handles); spmv_version()
+                             tells which library is loaded.  Fill the struct with
                              spmv_panel_opts_default() and then set fields */
     int sched;            /* -1 process default, 0 steps, 1 sweep, 2 chain */
     int panel_cols;       /* columns per panel (rounded down to 2^k); 0: 2^18 */
@@ -210,6 +217,25 @@ void spmv_panel_opts_default(spmv_panel_opts *opts);
 typedef struct spmv_csr_dev spmv_csr_dev;
 
 int spmv_csr_upload(const sparse_csr *A, spmv_csr_dev **out);
+/*
+ * f32 handles (library version 0.7): the values are stored as fp32, converted
+ * with the C cast (IEEE round to nearest even) -- on the host by the uploads,
+ * on the device by spmv_csr_to_f32 (a new handle with the same pattern; the
+ * f64 source stays valid; how a spmv_csr_generate()d matrix gets there;
+ * -EINVAL on an f32 source).  A finite value that rounds to +-inf: -ERANGE,
+ * nothing is created.  NaN and +-inf pass through; values below FLT_MIN
+ * become fp32 subnormals and are read back as such (no flush to zero).
+ * Every direct kernel id, launch_rows / launch_blocks, the timed loops,
+ * graph capture, download (widened back) and autotune (direct kernels only,
+ * allow_panels ignored, one line in the tune log says so) work on an f32
+ * handle; spmv_hll_from_csr of an f32 CSR handle gives an f32 HLL handle.
+ * The blocked path does not: spmv_*_build_panels* return -ENOTSUP, and the
+ * PANELS kernel id -EINVAL as on any handle without a copy.  The one-shot
+ * seam, the reference ABI names and spmv_mgpu.h create f64 handles only.
+ */
+int spmv_csr_upload_f32(const sparse_csr *A, spmv_csr_dev **out);
+int spmv_csr_to_f32(const spmv_csr_dev *A, spmv_csr_dev **out);
+int spmv_csr_value_bytes(const spmv_csr_dev *A); /* 8 or 4 */
 /* Build a synthetic matrix (spmv_synth.h) directly in device memory. */
 int spmv_csr_generate(int kind, int M, int N, int K, int64_t W, int64_t row0,
                       uint64_t seed, spmv_csr_dev **out);
@@ -273,8 +299,13 @@ void spmv_csr_release(spmv_csr_dev *A);
 typedef struct spmv_hll_dev spmv_hll_dev;
 
 int spmv_hll_upload(const sparse_hll *H, int is_col_major, spmv_hll_dev **out);
+/* values stored as fp32 (see spmv_csr_upload_f32) */
+int spmv_hll_upload_f32(const sparse_hll *H, int is_col_major,
+                        spmv_hll_dev **out);
+int spmv_hll_value_bytes(const spmv_hll_dev *H); /* 8 or 4 */
 /* CSR -> HLL conversion on the device (reference hll.c:19-95 semantics,
- * pads already rewritten); the CSR handle stays valid. */
+ * pads already rewritten); the CSR handle stays valid.  The HLL handle has
+ * the CSR handle's value type. */
 int spmv_hll_from_csr(const spmv_csr_dev *A, int is_col_major,
                       spmv_hll_dev **out);
 /* kernel = 0..3 (hip_hll.h); the handle's layout must match the kernel
@@ -313,7 +344,7 @@ int spmv_hll_shape(const spmv_hll_dev *H, int *M, int *N, int64_t *NZ,
                    int *num_blocks, int64_t *slots, int *is_col_major);
 int64_t spmv_hll_algorithmic_bytes(const spmv_hll_dev *H);
 /* bytes one launch of `kernel` must move: spmv_hll_algorithmic_bytes (12 per
- * STORED slot) for the direct kernels; for SPMV_HLL_KERNEL_PANELS, whose
+ * STORED slot, 8 in an f32 handle) for the direct kernels; for SPMV_HLL_KERNEL_PANELS, whose
  * copy stores no padding, 12 per true entry (+ 12 nb + 8 M + 8 N as before).
  * Equal when the format pads nothing (the headline matrix). */
 int64_t spmv_hll_kernel_bytes(const spmv_hll_dev *H, int kernel);

@@ -519,6 +519,8 @@ _sig("spmv_stream_sync", C.c_int, C.c_void_p)
 _sig("spmv_dev_fill_synth", C.c_int, C.c_void_p, C.c_int64, C.c_uint64,
      C.c_int64, C.c_void_p)
 _sig("spmv_csr_upload", C.c_int, _CSRp, C.POINTER(C.c_void_p))
+_sig("spmv_csr_upload_f32", C.c_int, _CSRp, C.POINTER(C.c_void_p))
+_sig("spmv_csr_to_f32", C.c_int, C.c_void_p, C.POINTER(C.c_void_p))
 _sig("spmv_csr_generate", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
      C.c_int64, C.c_int64, C.c_uint64, C.POINTER(C.c_void_p))
 _sig("spmv_csr_launch_rows", C.c_int, C.c_void_p, C.c_int,
@@ -528,6 +530,7 @@ _sig("spmv_set_panel_schedule", C.c_int, C.c_int)
 _sig("spmv_csr_shape", C.c_int, C.c_void_p, _ip, _ip, C.POINTER(C.c_int64))
 _sig("spmv_csr_download", C.c_int, C.c_void_p, C.POINTER(_CSRp))
 _sig("spmv_hll_upload", C.c_int, _HLLp, C.c_int, C.POINTER(C.c_void_p))
+_sig("spmv_hll_upload_f32", C.c_int, _HLLp, C.c_int, C.POINTER(C.c_void_p))
 _sig("spmv_hll_from_csr", C.c_int, C.c_void_p, C.c_int,
      C.POINTER(C.c_void_p))
 _sig("spmv_hll_launch_blocks", C.c_int, C.c_void_p, C.c_int,
@@ -559,6 +562,7 @@ _TWINS = (
     ("panels_schedule", C.c_int, C.c_void_p),
     ("build_panels_like", C.c_int, C.c_void_p, C.c_void_p),
     ("algorithmic_bytes", C.c_int64, C.c_void_p),
+    ("value_bytes", C.c_int, C.c_void_p),
     ("release", None, C.c_void_p),
     ("time", C.c_int,
      C.c_void_p, C.c_int, C.POINTER(LaunchOpts), C.c_void_p, C.c_void_p,
@@ -1210,6 +1214,12 @@ def stream_sync(stream=None):
     _check(_lib.spmv_stream_sync(stream), "spmv_stream_sync")
 
 
+def _upload_fn(fmt, values):
+    if values not in ("f64", "f32"):
+        raise ValueError("values=%r: \"f64\" or \"f32\"" % (values,))
+    return "spmv_%s_upload%s" % (fmt, "_f32" if values == "f32" else "")
+
+
 class _Device:
     """What CsrDevice and HllDevice share: the handle's lifecycle and the
     spmv_<fmt>_* calls that differ only in the prefix."""
@@ -1247,6 +1257,12 @@ class _Device:
     @property
     def algorithmic_bytes(self):
         return self._fn("algorithmic_bytes")(self.h)
+
+    @property
+    def value_bytes(self):
+        """8 (fp64 values) or 4 (stored as fp32; products and sums stay
+        fp64)"""
+        return self._call("value_bytes")
 
     def build_panels(self, panel_cols=0, sched=None, tile_rows=0,
                      sweep_wgs_per_cu=0, reserve_cus=0, lds_min=0,
@@ -1343,10 +1359,21 @@ class CsrDevice(_Device):
         self.M, self.N, self.NZ = M.value, N.value, NZ.value
 
     @classmethod
-    def upload(cls, A):
+    def upload(cls, A, values="f64"):
+        """values="f32": the matrix values are rounded to fp32 and stored so
+        (8 instead of 12 bytes per entry; OSError(ERANGE) when a finite value
+        overflows); x, y, products and sums stay fp64"""
+        name = _upload_fn("csr", values)
         h = C.c_void_p()
-        _check(_lib.spmv_csr_upload(A, C.byref(h)), "spmv_csr_upload")
+        _check(getattr(_lib, name)(A, C.byref(h)), name)
         return cls(h)
+
+    def to_f32(self):
+        """a new handle with this one's pattern and its values rounded to
+        fp32 on the device; this handle stays valid"""
+        h = C.c_void_p()
+        _check(_lib.spmv_csr_to_f32(self.h, C.byref(h)), "spmv_csr_to_f32")
+        return CsrDevice(h)
 
     @classmethod
     def generate(cls, kind, M, N, K, W, row0=0, seed=42):
@@ -1385,6 +1412,7 @@ class CsrDevice(_Device):
         return p
 
     def to_hll(self, col_major):
+        """device conversion; the HLL handle has this handle's value type"""
         h = C.c_void_p()
         _check(_lib.spmv_hll_from_csr(self.h, int(col_major), C.byref(h)),
                "spmv_hll_from_csr")
@@ -1408,15 +1436,16 @@ class HllDevice(_Device):
         self.col_major = bool(cm.value)
 
     @classmethod
-    def upload(cls, H, col_major):
+    def upload(cls, H, col_major, values="f64"):
+        name = _upload_fn("hll", values)
         h = C.c_void_p()
-        _check(_lib.spmv_hll_upload(H, int(col_major), C.byref(h)),
-               "spmv_hll_upload")
+        _check(getattr(_lib, name)(H, int(col_major), C.byref(h)), name)
         return cls(h)
 
     def kernel_bytes(self, kernel):
-        """bytes one launch of `kernel` must move: 12 per STORED slot for the
-        direct kernels, 12 per true entry for the blocked copy (no padding)"""
+        """bytes one launch of `kernel` must move: 12 per STORED slot (8 with
+        fp32 values) for the direct kernels, 12 per true entry for the blocked
+        copy (no padding)"""
         return _lib.spmv_hll_kernel_bytes(self.h, kernel)
 
     def launch(self, kernel, d_x, d_y, waves_per_block=0, stream=None,

@@ -1,5 +1,8 @@
 /*
- * csr_kernels.hip -- fp64 CSR SpMV kernels for gfx950 (wave64).
+ * csr_kernels.hip -- fp64 CSR SpMV kernels for gfx950 (wave64).  Every kernel
+ * is a template over the STORED value type V of the handle (double, or float
+ * for an f32 handle: 8 B per entry instead of 12); x, y, every product and
+ * every sum are fp64 either way, in the same order.
  *
  * Five kernels fill the five slots of the reference's driver table
  * (reference cuda_csr.cu:19-178, main.c:259-263); the designs are new:
@@ -27,6 +30,7 @@
  * do not evict x from L2 / Infinity Cache.
  */
 #include <algorithm>
+#include <type_traits>
 #include "hip_common.h"
 
 template <typename T> __device__ __forceinline__ T ld_stream(const T *p) {
@@ -71,10 +75,11 @@ template <int G> __device__ __forceinline__ double group_sum(double v) {
  * they are left to k_csr_long_seg, launched right after on the same stream
  * (one lane / wavefront / workgroup walking a hub row of 10^5 entries was
  * 6-130 ms of an otherwise 0.05-3 ms launch) */
+template <typename V>
 __global__ void k_csr_thread_row(int r0, int r1, int lrow,
                                  const int *__restrict__ irp,
                                  const int *__restrict__ ja,
-                                 const double *__restrict__ as,
+                                 const V *__restrict__ as,
                                  const double *__restrict__ x,
                                  double *__restrict__ y) {
     int row = r0 + blockIdx.x * blockDim.x + threadIdx.x;
@@ -88,10 +93,11 @@ __global__ void k_csr_thread_row(int r0, int r1, int lrow,
 }
 
 /* ------------------------------------------------------------------ */
+template <typename V>
 __global__ void k_csr_wave_row(int r0, int r1, int lrow,
                                const int *__restrict__ irp,
                                const int *__restrict__ ja,
-                               const double *__restrict__ as,
+                               const V *__restrict__ as,
                                const double *__restrict__ x,
                                double *__restrict__ y) {
     const int lane = threadIdx.x & (WAVE - 1);
@@ -142,11 +148,11 @@ __device__ __forceinline__ int xcd_grouped(int bid) {
  * is three dependent latencies (IRP -> JA/AS -> x): config 2 (1M x 16,
  * flushed, 256-lane workgroups) 0.0494 -> 0.0447 ms; banded 10M x 32 0.872 ->
  * 0.859; no change beyond noise on matrices whose launch is long. */
-template <int G, int P, int ORDER, bool UNI>
+template <int G, int P, int ORDER, bool UNI, typename V>
 __global__ void k_csr_subwave_row(int r0, int r1, int ulen, int lrow,
                                   const int *__restrict__ irp,
                                   const int *__restrict__ ja,
-                                  const double *__restrict__ as,
+                                  const V *__restrict__ as,
                                   const double *__restrict__ x,
                                   double *__restrict__ y) {
     constexpr int RPP = WAVE / G; /* rows per pass */
@@ -181,22 +187,24 @@ __global__ void k_csr_subwave_row(int r0, int r1, int ulen, int lrow,
         }
     }
     int c[P];
-    double a[P], acc[P];
+    V a[P];
+    double acc[P];
 #pragma unroll
     for (int p = 0; p < P; ++p) {
         /* offsets relative to the row's first entry: beg + sub (+ G below)
          * must not be formed in 32 bits next to INT32_MAX */
         const bool has = sub < end[p] - beg[p];
         c[p] = has ? ld_stream(ja + beg[p] + sub) : -1;
-        a[p] = has ? ld_stream(as + beg[p] + sub) : 0.0;
+        a[p] = has ? ld_stream(as + beg[p] + sub) : V(0);
     }
 #pragma unroll
     for (int p = 0; p < P; ++p)
-        acc[p] = c[p] >= 0 ? a[p] * x[c[p]] : 0.0;
+        acc[p] = c[p] >= 0 ? widen(a[p]) * x[c[p]] : 0.0;
 #pragma unroll
     for (int p = 0; p < P; ++p)
         for (int k = sub + G, n = end[p] - beg[p]; k < n; k += G)
-            acc[p] += ld_stream(as + beg[p] + k) * x[ld_stream(ja + beg[p] + k)];
+            acc[p] += widen(ld_stream(as + beg[p] + k)) *
+                      x[ld_stream(ja + beg[p] + k)];
 #pragma unroll
     for (int p = 0; p < P; ++p) {
         acc[p] = group_sum<G>(acc[p]);
@@ -207,10 +215,11 @@ __global__ void k_csr_subwave_row(int r0, int r1, int ulen, int lrow,
 }
 
 /* ------------------------------------------------------------------ */
+template <typename V>
 __global__ void k_csr_block_row(int r0, int r1, int lrow,
                                 const int *__restrict__ irp,
                                 const int *__restrict__ ja,
-                                const double *__restrict__ as,
+                                const V *__restrict__ as,
                                 const double *__restrict__ x,
                                 double *__restrict__ y) {
     __shared__ double part[16];
@@ -225,9 +234,9 @@ __global__ void k_csr_block_row(int r0, int r1, int lrow,
         /* relative to the row: beg + k + blockDim.x must not be formed in 32
          * bits next to INT32_MAX (the entry count's limit) */
         const int *rj = ja + beg;
-        const double *ra = as + beg;
+        const V *ra = as + beg;
         for (int k = threadIdx.x, n = end - beg; k < n; k += blockDim.x)
-            acc += ld_stream(ra + k) * x[ld_stream(rj + k)];
+            acc += widen(ld_stream(ra + k)) * x[ld_stream(rj + k)];
 #pragma unroll
         for (int d = WAVE / 2; d > 0; d >>= 1)
             acc += __shfl_down(acc, d, WAVE);
@@ -272,9 +281,9 @@ __global__ void k_csr_block_row(int r0, int r1, int lrow,
 #define TSKEW(k) ((k) + ((k) >> 5))
 #define STREAM_LDS (STREAM_NNZ + STREAM_NNZ / 32 + 1)
 
-template <int T>
+template <int T, typename LV>
 __device__ __forceinline__ void stream_rows(int tid, int rows, const int *rowptr,
-                                            const int *s_ja, const double *s_val,
+                                            const int *s_ja, const LV *s_val,
                                             const double *__restrict__ x,
                                             double *__restrict__ y_range) {
     const int sub = tid % T;
@@ -290,7 +299,7 @@ __device__ __forceinline__ void stream_rows(int tid, int rows, const int *rowptr
             const int c2 = s_ja[TSKEW(k + 2 * T)], c3 = s_ja[TSKEW(k + 3 * T)];
             const double v0 = s_val[TSKEW(k)], v1 = s_val[TSKEW(k + T)];
             const double v2 = s_val[TSKEW(k + 2 * T)];
-            const double v3 = s_val[TSKEW(k + 3 * T)];
+            const double v3 = s_val[TSKEW(k + 3 * T)]; /* fp32: widened here */
             const double x0 = x[c0], x1 = x[c1], x2 = x[c2], x3 = x[c3];
             acc += v0 * x0;
             acc += v1 * x1;
@@ -298,7 +307,7 @@ __device__ __forceinline__ void stream_rows(int tid, int rows, const int *rowptr
             acc += v3 * x3;
         }
         for (; k < rz; k += T)
-            acc += s_val[TSKEW(k)] * x[s_ja[TSKEW(k)]];
+            acc += (double)s_val[TSKEW(k)] * x[s_ja[TSKEW(k)]];
     }
     acc = group_sum<T>(acc); /* a team's lanes run the same trip count */
     if (sub == 0)
@@ -308,22 +317,38 @@ __device__ __forceinline__ void stream_rows(int tid, int rows, const int *rowptr
 
 typedef int s_v4i __attribute__((ext_vector_type(4)));
 typedef double s_v2d __attribute__((ext_vector_type(2)));
+typedef float s_v4f __attribute__((ext_vector_type(4)));
+
+/* how the transposed modes see the LDS value buffer: as the stored type.  An
+ * fp32 handle's values lie in the low half of the (double) product buffer of
+ * the cooperative mode -- a range runs one mode or the other, never both */
+template <typename V> struct lds_val {
+    typedef double type;
+};
+template <> struct lds_val<float> {
+    typedef float __attribute__((may_alias)) type;
+};
 
 /* WIDE: ranges in transposed mode fetch JA / AS with 16-byte loads from the
  * 16-byte boundary below the range's first entry (a wavefront instruction
  * covers 1 KiB of whole lines: 6 load instructions per lane instead of 16);
  * the LDS transposition absorbs the shift and the fact that a lane's JA and
  * AS elements are different entries.  The device arrays carry 2056 entries
- * of slack so the last range may read past NZ. */
-template <bool WIDE>
+ * of slack so the last range may read past NZ.  With fp32 values the AS
+ * fetch has the shape of the JA fetch: two 16-byte loads per lane from the
+ * same boundary, the same shift, a lane's JA and AS elements the SAME entries
+ * (4 load instructions per lane). */
+template <bool WIDE, typename V>
 __global__ void __launch_bounds__(STREAM_THREADS)
     k_csr_stream(int n_rowblk, int grouped, const int2 *__restrict__ rowblk,
                  const unsigned char *__restrict__ mode,
                  const int *__restrict__ irp, const int *__restrict__ ja,
-                 const double *__restrict__ as, const double *__restrict__ x,
+                 const V *__restrict__ as, const double *__restrict__ x,
                  double *__restrict__ y, double *seg_partial,
                  unsigned long long *seg_count, unsigned epoch) {
-    __shared__ double s_val[STREAM_LDS]; /* AS (transposed) or products */
+    __shared__ double s_prod[STREAM_LDS]; /* AS (transposed) or products */
+    typedef typename lds_val<V>::type LV;
+    LV *s_val = reinterpret_cast<LV *>(s_prod);
     __shared__ int s_ja[STREAM_LDS];
     __shared__ double part[STREAM_THREADS / WAVE];
     __shared__ int rowptr[STREAM_ROWS + 1]; /* this range's slice of IRP */
@@ -401,9 +426,13 @@ __global__ void __launch_bounds__(STREAM_THREADS)
     if (WIDE && md == 0 && cnt + (beg & 3) <= STREAM_NNZ) {
         const int d = beg & 3; /* entries between the 16-B boundary and beg */
         const int *ja_al = ja + (beg - d);
-        const double *as_al = as + (beg - d);
+        const V *as_al = as + (beg - d);
+        constexpr bool F32 = sizeof(V) == 4;
+        typedef typename std::conditional<F32, s_v4f, s_v2d>::type vecV;
+        constexpr int NA = F32 ? 2 : 4;  /* 16-byte AS loads per lane */
+        constexpr int PA = F32 ? 4 : 2;  /* entries per load */
         s_v4i cj[2];
-        s_v2d ca[4];
+        vecV ca[NA];
         for (int r = tid; r < rows; r += STREAM_THREADS)
             rowptr[r] = irp[row_a + r] - beg;
         if (tid == 0)
@@ -412,8 +441,8 @@ __global__ void __launch_bounds__(STREAM_THREADS)
         for (int i = 0; i < 2; ++i)
             cj[i] = ld_stream((const s_v4i *)(ja_al + (i * STREAM_THREADS + tid) * 4));
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-            ca[i] = ld_stream((const s_v2d *)(as_al + (i * STREAM_THREADS + tid) * 2));
+        for (int i = 0; i < NA; ++i)
+            ca[i] = ld_stream((const vecV *)(as_al + (i * STREAM_THREADS + tid) * PA));
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -423,10 +452,10 @@ __global__ void __launch_bounds__(STREAM_THREADS)
                     s_ja[TSKEW(k)] = cj[i][j];
             }
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < NA; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int k = (i * STREAM_THREADS + tid) * 2 + j - d;
+            for (int j = 0; j < PA; ++j) {
+                const int k = (i * STREAM_THREADS + tid) * PA + j - d;
                 if (k >= 0 && k < cnt)
                     s_val[TSKEW(k)] = ca[i][j];
             }
@@ -444,7 +473,7 @@ __global__ void __launch_bounds__(STREAM_THREADS)
      * together) and of its row offsets */
     constexpr int E = STREAM_NNZ / STREAM_THREADS;
     int c[E];
-    double a[E];
+    V a[E];
     for (int r = tid; r < rows; r += STREAM_THREADS) /* <= STREAM_ROWS rows */
         rowptr[r] = irp[row_a + r] - beg;
     if (tid == 0)
@@ -454,7 +483,7 @@ __global__ void __launch_bounds__(STREAM_THREADS)
         const int k = tid + e * STREAM_THREADS;
         const bool has = k < cnt;
         c[e] = has ? ld_stream(ja + beg + k) : -1;
-        a[e] = has ? ld_stream(as + beg + k) : 0.0;
+        a[e] = has ? ld_stream(as + beg + k) : V(0);
     }
 
     if (md == 0) { /* ---- transposed ---- */
@@ -484,7 +513,7 @@ __global__ void __launch_bounds__(STREAM_THREADS)
 #pragma unroll
     for (int e = 0; e < E; ++e)
         if (c[e] >= 0)
-            s_val[tid + e * STREAM_THREADS] = a[e] * x[c[e]];
+            s_prod[tid + e * STREAM_THREADS] = widen(a[e]) * x[c[e]];
     __syncthreads();
     int g = 1;
     while (g < WAVE && g * rows * 2 <= cnt)
@@ -498,7 +527,7 @@ __global__ void __launch_bounds__(STREAM_THREADS)
         if (live) {
             const int ra = rowptr[r], rz = rowptr[r + 1];
             for (int k = ra + sub; k < rz; k += g)
-                acc += s_val[k];
+                acc += s_prod[k];
         }
         for (int d = g >> 1; d > 0; d >>= 1)
             acc += __shfl_down(acc, d, WAVE);
@@ -518,12 +547,13 @@ __global__ void __launch_bounds__(STREAM_THREADS)
  * power-law matrices have hundreds of such rows.  Rows outside [r0, r1) belong
  * to another launch of a chunked exchange.
  */
+template <typename V>
 __global__ void __launch_bounds__(STREAM_THREADS)
     k_csr_long_seg(int r0, int r1, const int *__restrict__ long_rb,
                    const int2 *__restrict__ rowblk,
                    const unsigned char *__restrict__ mode,
                    const int *__restrict__ irp,
-                   const int *__restrict__ ja, const double *__restrict__ as,
+                   const int *__restrict__ ja, const V *__restrict__ as,
                    const double *__restrict__ x, double *__restrict__ y,
                    double *seg_partial, unsigned long long *seg_count,
                    unsigned epoch) {
@@ -569,6 +599,15 @@ __global__ void __launch_bounds__(STREAM_THREADS)
 }
 
 /* ------------------------------------------------------------------ */
+/* the handle's value array as the type the kernels are instantiated for */
+template <typename V> static const V *values_of(const spmv_csr_dev *A);
+template <> const double *values_of<double>(const spmv_csr_dev *A) {
+    return A->as;
+}
+template <> const float *values_of<float>(const spmv_csr_dev *A) {
+    return A->as32;
+}
+
 static int pick_group(const spmv_csr_dev *A, int group) {
     if (group >= 2 && group <= 32 && (group & (group - 1)) == 0)
         return group;
@@ -579,7 +618,7 @@ static int pick_group(const spmv_csr_dev *A, int group) {
     return g;
 }
 
-template <int G, int P, bool UNI>
+template <typename V, int G, int P, bool UNI>
 static void launch_subwave_u(int r0, int r1, int threads, int order,
                              const spmv_csr_dev *A, const double *x, double *y,
                              hipStream_t s) {
@@ -590,55 +629,56 @@ static void launch_subwave_u(int r0, int r1, int threads, int order,
     const int ulen = A->uniform_len;
     const int lrow = A->n_long_rb > 0 ? STREAM_NNZ : 0;
     if (order == 1)
-        hipLaunchKernelGGL((k_csr_subwave_row<G, P, 1, UNI>), dim3(grid),
+        hipLaunchKernelGGL((k_csr_subwave_row<G, P, 1, UNI, V>), dim3(grid),
                            dim3(threads), 0, s, r0, r1, ulen, lrow, A->irp,
-                           A->ja, A->as, x, y);
+                           A->ja, values_of<V>(A), x, y);
     else if (order == 2)
-        hipLaunchKernelGGL((k_csr_subwave_row<G, P, 2, UNI>),
+        hipLaunchKernelGGL((k_csr_subwave_row<G, P, 2, UNI, V>),
                            dim3((grid + 8 * CSR_GROUP - 1) / (8 * CSR_GROUP) *
                                 8 * CSR_GROUP),
                            dim3(threads), 0, s, r0, r1, ulen, lrow, A->irp,
-                           A->ja, A->as, x, y);
+                           A->ja, values_of<V>(A), x, y);
     else
-        hipLaunchKernelGGL((k_csr_subwave_row<G, P, 0, UNI>), dim3(grid),
+        hipLaunchKernelGGL((k_csr_subwave_row<G, P, 0, UNI, V>), dim3(grid),
                            dim3(threads), 0, s, r0, r1, ulen, lrow, A->irp,
-                           A->ja, A->as, x, y);
+                           A->ja, values_of<V>(A), x, y);
 }
 
 /* order bit 8 (0x100) set by the caller: the matrix has a constant row
  * length and the launch may use it */
-template <int G, int P>
+template <typename V, int G, int P>
 static void launch_subwave_p(int r0, int r1, int threads, int order,
                              const spmv_csr_dev *A, const double *x, double *y,
                              hipStream_t s) {
     if (order & 0x100)
-        launch_subwave_u<G, P, true>(r0, r1, threads, order & 0xff, A, x, y, s);
+        launch_subwave_u<V, G, P, true>(r0, r1, threads, order & 0xff, A, x, y, s);
     else
-        launch_subwave_u<G, P, false>(r0, r1, threads, order & 0xff, A, x, y, s);
+        launch_subwave_u<V, G, P, false>(r0, r1, threads, order & 0xff, A, x, y, s);
 }
 
 /* passes: independent row groups per wavefront (tuning, variant bits 2-3;
  * carried per launch -- the launch path keeps no process-global state) */
-template <int G>
+template <typename V, int G>
 static void launch_subwave(int passes, int r0, int r1, int threads, int remap,
                            const spmv_csr_dev *A, const double *x, double *y,
                            hipStream_t s) {
     switch (passes) {
     case 2:
-        launch_subwave_p<G, 2>(r0, r1, threads, remap, A, x, y, s);
+        launch_subwave_p<V, G, 2>(r0, r1, threads, remap, A, x, y, s);
         break;
     case 4:
-        launch_subwave_p<G, 4>(r0, r1, threads, remap, A, x, y, s);
+        launch_subwave_p<V, G, 4>(r0, r1, threads, remap, A, x, y, s);
         break;
     default: /* 8 passes: 0.79 ms vs 0.83 ms (4) on banded 10M x 32 */
-        launch_subwave_p<G, 8>(r0, r1, threads, remap, A, x, y, s);
+        launch_subwave_p<V, G, 8>(r0, r1, threads, remap, A, x, y, s);
         break;
     }
 }
 
-int csr_launch_kernel(const spmv_csr_dev *A, int kernel, int waves, int group,
-                      int variant, const double *x, double *y, int r0, int r1,
-                      hipStream_t s) {
+template <typename V>
+static int csr_launch_t(const spmv_csr_dev *A, int kernel, int waves, int group,
+                        int variant, const double *x, double *y, int r0, int r1,
+                        hipStream_t s) {
     (void)hipGetLastError(); /* an earlier caller's unread error is not ours */
     if (!A || !x || !y || r0 < 0 || r1 > A->M || r0 > r1)
         return -EINVAL;
@@ -677,40 +717,40 @@ int csr_launch_kernel(const spmv_csr_dev *A, int kernel, int waves, int group,
         kernel = 2;
     switch (kernel) {
     case 0:
-        hipLaunchKernelGGL(k_csr_thread_row,
+        hipLaunchKernelGGL(k_csr_thread_row<V>,
                            dim3((rows + threads - 1) / threads), dim3(threads),
-                           0, s, r0, r1, lrow, A->irp, A->ja, A->as, x, y);
+                           0, s, r0, r1, lrow, A->irp, A->ja, values_of<V>(A), x, y);
         break;
     case 1:
-        hipLaunchKernelGGL(k_csr_wave_row,
+        hipLaunchKernelGGL(k_csr_wave_row<V>,
                            dim3(std::min((rows + waves - 1) / waves,
                                          (int)(0xFFFFFFFFu / (unsigned)threads))),
                            dim3(threads), 0, s, r0, r1, lrow, A->irp, A->ja,
-                           A->as, x, y);
+                           values_of<V>(A), x, y);
         break;
     case 2:
         switch (pick_group(A, group)) {
         case 2:
-            launch_subwave<2>(passes, r0, r1, threads, remap, A, x, y, s);
+            launch_subwave<V, 2>(passes, r0, r1, threads, remap, A, x, y, s);
             break;
         case 4:
-            launch_subwave<4>(passes, r0, r1, threads, remap, A, x, y, s);
+            launch_subwave<V, 4>(passes, r0, r1, threads, remap, A, x, y, s);
             break;
         case 8:
-            launch_subwave<8>(passes, r0, r1, threads, remap, A, x, y, s);
+            launch_subwave<V, 8>(passes, r0, r1, threads, remap, A, x, y, s);
             break;
         case 16:
-            launch_subwave<16>(passes, r0, r1, threads, remap, A, x, y, s);
+            launch_subwave<V, 16>(passes, r0, r1, threads, remap, A, x, y, s);
             break;
         default:
-            launch_subwave<32>(passes, r0, r1, threads, remap, A, x, y, s);
+            launch_subwave<V, 32>(passes, r0, r1, threads, remap, A, x, y, s);
             break;
         }
         break;
     case 3: {
         int grid = rows < 65536 * 16 ? rows : 65536 * 16;
-        hipLaunchKernelGGL(k_csr_block_row, dim3(grid), dim3(threads), 0, s,
-                           r0, r1, lrow, A->irp, A->ja, A->as, x, y);
+        hipLaunchKernelGGL(k_csr_block_row<V>, dim3(grid), dim3(threads), 0, s,
+                           r0, r1, lrow, A->irp, A->ja, values_of<V>(A), x, y);
         break;
     }
     case 4: {
@@ -765,16 +805,16 @@ int csr_launch_kernel(const spmv_csr_dev *A, int kernel, int waves, int group,
                                  (8 * CSR_GROUP) * 8 * CSR_GROUP)
                     : (unsigned)A->n_rowblk;
             if (variant & 16) /* tuning: 4- / 8-byte loads only */
-                hipLaunchKernelGGL(k_csr_stream<false>, dim3(grid),
+                hipLaunchKernelGGL((k_csr_stream<false, V>), dim3(grid),
                                    dim3(STREAM_THREADS), 0, s, A->n_rowblk, grp,
                                    (const int2 *)A->rowblk, A->rowblk_mode,
-                                   A->irp, A->ja, A->as, x, y, A->seg_partial,
+                                   A->irp, A->ja, values_of<V>(A), x, y, A->seg_partial,
                                    A->seg_count, epoch);
             else
-                hipLaunchKernelGGL(k_csr_stream<true>, dim3(grid),
+                hipLaunchKernelGGL((k_csr_stream<true, V>), dim3(grid),
                                    dim3(STREAM_THREADS), 0, s, A->n_rowblk, grp,
                                    (const int2 *)A->rowblk, A->rowblk_mode,
-                                   A->irp, A->ja, A->as, x, y, A->seg_partial,
+                                   A->irp, A->ja, values_of<V>(A), x, y, A->seg_partial,
                                    A->seg_count, epoch);
         }
         break;
@@ -783,10 +823,21 @@ int csr_launch_kernel(const spmv_csr_dev *A, int kernel, int waves, int group,
         return -EINVAL;
     }
     if (kernel != 4 && lrow > 0)
-        hipLaunchKernelGGL(k_csr_long_seg, dim3(A->n_long_rb),
+        hipLaunchKernelGGL(k_csr_long_seg<V>, dim3(A->n_long_rb),
                            dim3(STREAM_THREADS), 0, s, r0, r1, A->long_rb,
                            (const int2 *)A->rowblk, A->rowblk_mode, A->irp,
-                           A->ja, A->as, x, y, A->seg_partial, A->seg_count,
+                           A->ja, values_of<V>(A), x, y, A->seg_partial, A->seg_count,
                            epoch);
     return hip_errno(hipGetLastError());
+}
+
+/* dispatch on the handle's value type (hip_common.h: value_bytes) */
+int csr_launch_kernel(const spmv_csr_dev *A, int kernel, int waves, int group,
+                      int variant, const double *x, double *y, int r0, int r1,
+                      hipStream_t s) {
+    if (A && A->value_bytes == 4)
+        return csr_launch_t<float>(A, kernel, waves, group, variant, x, y, r0,
+                                   r1, s);
+    return csr_launch_t<double>(A, kernel, waves, group, variant, x, y, r0, r1,
+                                s);
 }

@@ -8,6 +8,7 @@
  * entry point returns -ENODEV.
  */
 #include <algorithm>
+#include <cmath>
 #include <functional>
 #include <mutex>
 #include <stdio.h>
@@ -146,8 +147,10 @@ struct tune_log {
 extern "C" {
 
 /* 0.3: spmv_panel_opts.bucket_order; 0.4: spmv_panel_opts.struct_size (first
- * field), spmv_*_release_checked, handle checks on every entry point */
-const char *spmv_version(void) { return "spmv_scpa_amd 0.6 gfx950"; }
+ * field), spmv_*_release_checked, handle checks on every entry point;
+ * 0.7: fp32-stored values (spmv_*_upload_f32, spmv_csr_to_f32,
+ * spmv_*_value_bytes) */
+const char *spmv_version(void) { return "spmv_scpa_amd 0.7 gfx950"; }
 
 /* HIP_VERSION of the headers this library was compiled against, and of the
  * runtime it is bound to now (hipRuntimeGetVersion; needs no device).  The
@@ -541,10 +544,11 @@ __global__ void k_block_width(int M, const int *irp, int *width) {
  * conversion).  Blocks beyond HLL_FILL_WIDE columns are filled a lane per
  * SLOT instead (grid: wide blocks x chunks) -- same slots, same pad rule */
 #define HLL_FILL_WIDE 2048
+template <typename V>
 __global__ void k_hll_fill_wide(int M, int col_major, const int *wide_blocks,
                                 const int *irp, const int *cja,
-                                const double *cas, const int64_t *off, int *ja,
-                                double *as, unsigned *padmask) {
+                                const V *cas, const int64_t *off, int *ja,
+                                V *as, unsigned *padmask) {
     const int b = wide_blocks[blockIdx.x];
     const int rows = min(32, M - b * 32);
     const int64_t o = off[b];
@@ -561,7 +565,7 @@ __global__ void k_hll_fill_wide(int M, int col_major, const int *wide_blocks,
             as[t] = cas[beg + j];
         } else { /* pad -> the row's last valid column, or 0 (hip_hll.h) */
             ja[t] = len > 0 ? cja[beg + len - 1] : 0;
-            as[t] = 0.0;
+            as[t] = V(0);
             atomicOr(padmask + (t >> 5), 1u << (t & 31));
         }
     }
@@ -583,10 +587,11 @@ __global__ void k_hll_fill_wide(int M, int col_major, const int *wide_blocks,
  */
 #define HLL_FILL_BLOCKS 4
 #define HLL_FILL_SKEW 5
+template <typename V>
 __global__ void __launch_bounds__(256)
     k_hll_fill(int M, int nb, int col_major, const int *__restrict__ irp,
-               const int *__restrict__ cja, const double *__restrict__ cas,
-               const int64_t *__restrict__ off, int *ja, double *as,
+               const int *__restrict__ cja, const V *__restrict__ cas,
+               const int64_t *__restrict__ off, int *ja, V *as,
                unsigned *padmask, int cap) {
     extern __shared__ double fill_lds[];
     __shared__ int s_irp[HLL_FILL_BLOCKS * 32 + 1];
@@ -599,7 +604,7 @@ __global__ void __launch_bounds__(256)
     const int beg0 = s_irp[0];
     const int total = s_irp[r1 - r0] - beg0;
     const bool staged = total <= cap;
-    double *vals = fill_lds;
+    V *vals = (V *)fill_lds; /* the budget is sized for 8-byte values */
     int *cols = (int *)(fill_lds + SYNTH_AT(cap, HLL_FILL_SKEW) + 1);
     if (staged) {
         for (int p = (int)threadIdx.x; p < total; p += 256) {
@@ -629,7 +634,7 @@ __global__ void __launch_bounds__(256)
                 pad = j >= len;
                 const int p = rb + (pad ? len - 1 : j);
                 int c = 0;
-                double v = 0.0;
+                V v = V(0);
                 if (p >= rb) { /* len > 0 */
                     c = staged ? cols[SYNTH_AT(p, HLL_FILL_SKEW)] : cja[beg0 + p];
                     if (!pad)
@@ -655,6 +660,64 @@ __global__ void __launch_bounds__(256)
             }
         }
     }
+}
+
+/*
+ * fp64 -> fp32 of a matrix's values: the C cast, i.e. IEEE round to nearest
+ * even in the default rounding mode.  A value below FLT_MIN becomes an fp32
+ * SUBNORMAL (gradual underflow: hipcc compiles gfx950 kernels with fp32
+ * denormals on, .amdhsa_float_denorm_mode_32 = 3, so v_cvt_f32_f64 writes
+ * them and the SpMV kernels' v_cvt_f64_f32 reads them back); NaN and +-inf
+ * pass through.  A FINITE value that rounds to +-inf raises `*overflow` (an
+ * ordinary global atomic): the caller answers -ERANGE.
+ */
+__global__ void k_narrow_f32(const double *__restrict__ src,
+                             float *__restrict__ dst, size_t n,
+                             unsigned *overflow) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    bool over = false;
+    for (; i < n; i += stride) {
+        const double v = src[i];
+        const float f = (float)v;
+        dst[i] = f;
+        over |= isinf(f) && isfinite(v);
+    }
+    if (over)
+        atomicOr(overflow, 1u);
+}
+
+/* the same conversion on the host (uploads); -ERANGE as above */
+static int narrow_values(const double *src, size_t n, float *dst) {
+    bool over = false;
+    for (size_t i = 0; i < n; ++i) {
+        const float f = (float)src[i];
+        dst[i] = f;
+        over |= std::isinf(f) && std::isfinite(src[i]);
+    }
+    return over ? -ERANGE : 0;
+}
+
+/* n host values into a handle's value array at entry `at`: as they are
+ * (as64) or narrowed (as32) */
+static int put_values(double *as64, float *as32, int64_t at, const double *src,
+                      size_t n) {
+    if (!n)
+        return 0;
+    if (as64) {
+        HIP_RET(hipMemcpy(as64 + at, src, n * sizeof(double),
+                          hipMemcpyHostToDevice));
+        return 0;
+    }
+    float *tmp = (float *)malloc(n * sizeof(float));
+    if (!tmp)
+        return -ENOMEM;
+    int rc = narrow_values(src, n, tmp);
+    if (!rc)
+        rc = hip_errno(hipMemcpy(as32 + at, tmp, n * sizeof(float),
+                                 hipMemcpyHostToDevice));
+    free(tmp);
+    return rc;
 }
 
 /* scratch sweep used to push a small working set out of the Infinity Cache:
@@ -773,6 +836,7 @@ static void teardown(spmv_csr_dev *d) {
     (void)hipFree(d->irp);
     (void)hipFree(d->ja);
     (void)hipFree(d->as);
+    (void)hipFree(d->as32);
     (void)hipFree(d->rowblk);
     (void)hipFree(d->rowblk_mode);
     (void)hipFree(d->seg_partial);
@@ -783,7 +847,8 @@ static void teardown(spmv_csr_dev *d) {
     free(d);
 }
 
-static int csr_alloc_dev(int M, int N, int64_t NZ, spmv_csr_dev **out) {
+static int csr_alloc_dev(int M, int N, int64_t NZ, int value_bytes,
+                         spmv_csr_dev **out) {
     int rc = 0;
     spmv_csr_dev *d = (spmv_csr_dev *)calloc(1, sizeof *d);
     if (!d)
@@ -792,6 +857,7 @@ static int csr_alloc_dev(int M, int N, int64_t NZ, spmv_csr_dev **out) {
     d->M = M;
     d->N = N;
     d->NZ = NZ;
+    d->value_bytes = value_bytes;
     /* workgroup orders before tuning (csr_kernels.hip): grouped runs for
      * matrices of >= 2M rows (banded 10M x 32: stream kernel 0.652 ms
      * grouped / 0.683 hardware, sub-wave 0.843 / 0.905 / 0.885 contiguous),
@@ -804,7 +870,39 @@ static int csr_alloc_dev(int M, int N, int64_t NZ, spmv_csr_dev **out) {
     /* + slack: the stream kernel's 16-byte loads of the last range may read
      * up to 2048 + 3 entries past NZ (never used) */
     HIP_TRY(hipMalloc((void **)&d->ja, ((size_t)NZ + 2056) * sizeof(int)));
-    HIP_TRY(hipMalloc((void **)&d->as, ((size_t)NZ + 2056) * sizeof(double)));
+    if (value_bytes == 4) /* the slack holds for the fp32 array too */
+        HIP_TRY(hipMalloc((void **)&d->as32, ((size_t)NZ + 2056) * sizeof(float)));
+    else
+        HIP_TRY(hipMalloc((void **)&d->as, ((size_t)NZ + 2056) * sizeof(double)));
+    *out = d;
+    return 0;
+fail:
+    spmv_csr_release(d);
+    return rc;
+}
+
+static int csr_upload(const sparse_csr *A, int value_bytes, spmv_csr_dev **out) {
+    if (!A || !out || A->M < 0 || A->NZ < 0)
+        return -EINVAL;
+    *out = NULL;
+    if (spmv_device_count() == 0)
+        return -ENODEV;
+    spmv_csr_dev *d = NULL;
+    int rc = csr_alloc_dev(A->M, A->N, A->NZ, value_bytes, &d);
+    if (rc)
+        return rc;
+    HIP_TRY(hipMemcpy(d->irp, A->IRP, ((size_t)A->M + 1) * sizeof(int),
+                      hipMemcpyHostToDevice));
+    if (A->NZ > 0) {
+        HIP_TRY(hipMemcpy(d->ja, A->JA, (size_t)A->NZ * sizeof(int),
+                          hipMemcpyHostToDevice));
+        rc = put_values(d->as, d->as32, 0, A->AS, (size_t)A->NZ);
+        if (rc)
+            goto fail;
+    }
+    rc = finish_csr_handle(d, A->IRP);
+    if (rc)
+        goto fail;
     *out = d;
     return 0;
 fail:
@@ -813,29 +911,55 @@ fail:
 }
 
 int spmv_csr_upload(const sparse_csr *A, spmv_csr_dev **out) {
-    if (!A || !out || A->M < 0 || A->NZ < 0)
+    return csr_upload(A, 8, out);
+}
+
+int spmv_csr_upload_f32(const sparse_csr *A, spmv_csr_dev **out) {
+    return csr_upload(A, 4, out);
+}
+
+/* a new handle with the pattern of A and its values narrowed on the device */
+int spmv_csr_to_f32(const spmv_csr_dev *A, spmv_csr_dev **out) {
+    if (!A || !out)
         return -EINVAL;
     *out = NULL;
     if (spmv_device_count() == 0)
-        return -ENODEV;
+        return -ENODEV; /* no handle can be live: the more useful answer */
+    HANDLE_OK(A);
+    if (A->value_bytes == 4)
+        return -EINVAL;
+    if (!A->ja && A->NZ > 0)
+        return -ENODATA; /* spmv_csr_release_source() */
     spmv_csr_dev *d = NULL;
-    int rc = csr_alloc_dev(A->M, A->N, A->NZ, &d);
+    unsigned *d_over = NULL, over = 0;
+    int rc = csr_alloc_dev(A->M, A->N, A->NZ, 4, &d);
     if (rc)
         return rc;
-    HIP_TRY(hipMemcpy(d->irp, A->IRP, ((size_t)A->M + 1) * sizeof(int),
-                      hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d->irp, A->irp, ((size_t)A->M + 1) * sizeof(int),
+                      hipMemcpyDeviceToDevice));
     if (A->NZ > 0) {
-        HIP_TRY(hipMemcpy(d->ja, A->JA, (size_t)A->NZ * sizeof(int),
-                          hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d->as, A->AS, (size_t)A->NZ * sizeof(double),
-                          hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d->ja, A->ja, (size_t)A->NZ * sizeof(int),
+                          hipMemcpyDeviceToDevice));
+        HIP_TRY(hipMalloc((void **)&d_over, sizeof(unsigned)));
+        HIP_TRY(hipMemset(d_over, 0, sizeof(unsigned)));
+        hipLaunchKernelGGL(k_narrow_f32, dim3(4096), dim3(256), 0, 0, A->as,
+                           d->as32, (size_t)A->NZ, d_over);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(&over, d_over, sizeof(unsigned),
+                          hipMemcpyDeviceToHost));
+        if (over) {
+            rc = -ERANGE;
+            goto fail;
+        }
     }
-    rc = finish_csr_handle(d, A->IRP);
+    rc = finish_csr_handle(d, NULL);
     if (rc)
         goto fail;
+    (void)hipFree(d_over);
     *out = d;
     return 0;
 fail:
+    (void)hipFree(d_over);
     spmv_csr_release(d);
     return rc;
 }
@@ -871,7 +995,7 @@ int spmv_csr_generate(int kind, int M, int N, int K, int64_t W, int64_t row0,
             return -EOVERFLOW;
         irp[(size_t)i + 1] = (int)nz;
     }
-    rc = csr_alloc_dev(M, N, nz, &d);
+    rc = csr_alloc_dev(M, N, nz, 8, &d);
     if (rc)
         return rc;
     HIP_TRY(hipMemcpy(d->irp, irp.data(), ((size_t)M + 1) * sizeof(int),
@@ -948,8 +1072,8 @@ int spmv_csr_shape(const spmv_csr_dev *A, int *M, int *N, int64_t *NZ) {
 
 int64_t spmv_csr_algorithmic_bytes(const spmv_csr_dev *A) {
     HANDLE_OK(A);
-    return 12 * A->NZ + 4 * ((int64_t)A->M + 1) + 8 * (int64_t)A->M +
-           8 * (int64_t)A->N;
+    return (4 + A->value_bytes) * A->NZ + 4 * ((int64_t)A->M + 1) +
+           8 * (int64_t)A->M + 8 * (int64_t)A->N;
 }
 
 int spmv_csr_download(const spmv_csr_dev *A, sparse_csr **out) {
@@ -969,8 +1093,16 @@ int spmv_csr_download(const spmv_csr_dev *A, sparse_csr **out) {
     if (A->NZ > 0) {
         HIP_TRY(hipMemcpy(h->JA, A->ja, (size_t)A->NZ * sizeof(int),
                           hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(h->AS, A->as, (size_t)A->NZ * sizeof(double),
-                          hipMemcpyDeviceToHost));
+        if (A->value_bytes == 4) { /* widened back: exact */
+            std::vector<float> f((size_t)A->NZ);
+            HIP_TRY(hipMemcpy(f.data(), A->as32, (size_t)A->NZ * sizeof(float),
+                              hipMemcpyDeviceToHost));
+            for (size_t k = 0; k < (size_t)A->NZ; ++k)
+                h->AS[k] = (double)f[k];
+        } else {
+            HIP_TRY(hipMemcpy(h->AS, A->as, (size_t)A->NZ * sizeof(double),
+                              hipMemcpyDeviceToHost));
+        }
     }
     *out = h;
     return 0;
@@ -986,6 +1118,7 @@ fail:
 static void teardown(spmv_hll_dev *d) {
     (void)hipFree(d->ja);
     (void)hipFree(d->as);
+    (void)hipFree(d->as32);
     (void)hipFree(d->off);
     (void)hipFree(d->padmask);
     (void)hipFree(d->wide_seg);
@@ -997,7 +1130,8 @@ static void teardown(spmv_hll_dev *d) {
 }
 
 static int hll_alloc_dev(int M, int N, int64_t NZ, int nb, int col_major,
-                         const int64_t *host_off, spmv_hll_dev **out) {
+                         int value_bytes, const int64_t *host_off,
+                         spmv_hll_dev **out) {
     int rc = 0;
     spmv_hll_dev *d = (spmv_hll_dev *)calloc(1, sizeof *d);
     if (!d)
@@ -1007,6 +1141,7 @@ static int hll_alloc_dev(int M, int N, int64_t NZ, int nb, int col_major,
     d->N = N;
     d->NZ = NZ;
     d->nb = nb;
+    d->value_bytes = value_bytes;
     d->col_major = col_major ? 1 : 0;
     d->slots = host_off[nb];
     /* before tuning: grouped order for matrices of >= 2M rows (banded
@@ -1035,7 +1170,10 @@ static int hll_alloc_dev(int M, int N, int64_t NZ, int nb, int col_major,
     HIP_TRY(hipGetDevice(&d->device));
     /* +64 slots of slack: vector loads of the last chunk stay in bounds */
     HIP_TRY(hipMalloc((void **)&d->ja, ((size_t)d->slots + 64) * sizeof(int)));
-    HIP_TRY(hipMalloc((void **)&d->as, ((size_t)d->slots + 64) * sizeof(double)));
+    if (value_bytes == 4)
+        HIP_TRY(hipMalloc((void **)&d->as32, ((size_t)d->slots + 64) * sizeof(float)));
+    else
+        HIP_TRY(hipMalloc((void **)&d->as, ((size_t)d->slots + 64) * sizeof(double)));
     HIP_TRY(hipMalloc((void **)&d->off, ((size_t)nb + 1) * sizeof(int64_t)));
     {
         const size_t words = ((size_t)d->slots + 31) / 32 + 1;
@@ -1083,8 +1221,8 @@ fail:
     return rc;
 }
 
-int spmv_hll_upload(const sparse_hll *H, int is_col_major,
-                    spmv_hll_dev **out) {
+static int hll_upload(const sparse_hll *H, int is_col_major, int value_bytes,
+                      spmv_hll_dev **out) {
     if (!H || !out || H->hack_size != HACK_SIZE)
         return -EINVAL;
     *out = NULL;
@@ -1099,7 +1237,8 @@ int spmv_hll_upload(const sparse_hll *H, int is_col_major,
         maxw = std::max(maxw, H->blocks[b].max_NZ);
     }
     spmv_hll_dev *d = NULL;
-    int rc = hll_alloc_dev(H->M, H->N, H->NZ, nb, is_col_major, off.data(), &d);
+    int rc = hll_alloc_dev(H->M, H->N, H->NZ, nb, is_col_major, value_bytes,
+                           off.data(), &d);
     if (rc)
         return rc;
     d->max_width = maxw;
@@ -1108,9 +1247,10 @@ int spmv_hll_upload(const sparse_hll *H, int is_col_major,
             HIP_TRY(hipMemcpy(d->ja, H->blocks[0].JA,
                               (size_t)d->slots * sizeof(int),
                               hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(d->as, H->blocks[0].AS,
-                              (size_t)d->slots * sizeof(double),
-                              hipMemcpyHostToDevice));
+            rc = put_values(d->as, d->as32, 0, H->blocks[0].AS,
+                            (size_t)d->slots);
+            if (rc)
+                goto fail;
         } else {
             /* blocks allocated one by one (the reference's csr_to_hll): pack
              * them into two host slabs in parallel, then two copies -- a copy
@@ -1123,11 +1263,12 @@ int spmv_hll_upload(const sparse_hll *H, int is_col_major,
                 hipError_t e = hipMemcpy(d->ja, pj, (size_t)d->slots * sizeof(int),
                                          hipMemcpyHostToDevice);
                 if (e == hipSuccess)
-                    e = hipMemcpy(d->as, pa, (size_t)d->slots * sizeof(double),
-                                  hipMemcpyHostToDevice);
+                    rc = put_values(d->as, d->as32, 0, pa, (size_t)d->slots);
                 free(pj);
                 free(pa);
                 HIP_TRY(e);
+                if (rc)
+                    goto fail;
             } else {
                 free(pj);
                 free(pa);
@@ -1137,9 +1278,9 @@ int spmv_hll_upload(const sparse_hll *H, int is_col_major,
                         continue;
                     HIP_TRY(hipMemcpy(d->ja + off[b], H->blocks[b].JA,
                                       n * sizeof(int), hipMemcpyHostToDevice));
-                    HIP_TRY(hipMemcpy(d->as + off[b], H->blocks[b].AS,
-                                      n * sizeof(double),
-                                      hipMemcpyHostToDevice));
+                    rc = put_values(d->as, d->as32, off[b], H->blocks[b].AS, n);
+                    if (rc)
+                        goto fail;
                 }
             }
         }
@@ -1155,8 +1296,22 @@ fail:
     return rc;
 }
 
-int spmv_hll_from_csr(const spmv_csr_dev *A, int is_col_major,
-                      spmv_hll_dev **out) {
+int spmv_hll_upload(const sparse_hll *H, int is_col_major,
+                    spmv_hll_dev **out) {
+    return hll_upload(H, is_col_major, 8, out);
+}
+
+int spmv_hll_upload_f32(const sparse_hll *H, int is_col_major,
+                        spmv_hll_dev **out) {
+    return hll_upload(H, is_col_major, 4, out);
+}
+
+} /* extern "C" */
+
+/* V = the value type of BOTH handles: the conversion carries it along */
+template <typename V>
+static int hll_from_csr(const spmv_csr_dev *A, const V *A_as, int is_col_major,
+                        spmv_hll_dev **out) {
     HANDLE_OK(A);
     if (!out)
         return -EINVAL;
@@ -1182,11 +1337,13 @@ int spmv_hll_from_csr(const spmv_csr_dev *A, int is_col_major,
         off[(size_t)b + 1] = off[b] + (int64_t)rows * w[b];
         maxw = std::max(maxw, w[b]);
     }
-    rc = hll_alloc_dev(M, A->N, A->NZ, nb, is_col_major, off.data(), &d);
+    rc = hll_alloc_dev(M, A->N, A->NZ, nb, is_col_major, (int)sizeof(V),
+                       off.data(), &d);
     if (rc)
         goto fail;
     d->max_width = maxw;
     if (M > 0) {
+        V *d_as = sizeof(V) == 4 ? (V *)d->as32 : (V *)d->as;
         {
             /* LDS budget of a group of 128 rows: mean row length + 25 % + 8
              * per row, 2048..12288 entries; heavier groups read global */
@@ -1197,12 +1354,12 @@ int spmv_hll_from_csr(const spmv_csr_dev *A, int is_col_major,
             const size_t lds = ((size_t)SYNTH_AT(cap, HLL_FILL_SKEW) + 1) * 12 + 16;
             if (lds > 64 * 1024)
                 HIP_TRY(hipFuncSetAttribute(
-                    (const void *)k_hll_fill,
+                    (const void *)k_hll_fill<V>,
                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(k_hll_fill,
+            hipLaunchKernelGGL(k_hll_fill<V>,
                                dim3((nb + HLL_FILL_BLOCKS - 1) / HLL_FILL_BLOCKS),
                                dim3(256), lds, 0, M, nb, d->col_major, A->irp,
-                               A->ja, A->as, d->off, d->ja, d->as, d->padmask,
+                               A->ja, A_as, d->off, d->ja, d_as, d->padmask,
                                cap);
         }
         HIP_TRY(hipGetLastError());
@@ -1216,10 +1373,10 @@ int spmv_hll_from_csr(const spmv_csr_dev *A, int is_col_major,
                               hipMemcpyHostToDevice));
             const int64_t most = (int64_t)32 * maxw;
             const int chunks = (int)std::min<int64_t>(1024, (most + 8191) / 8192);
-            hipLaunchKernelGGL(k_hll_fill_wide,
+            hipLaunchKernelGGL(k_hll_fill_wide<V>,
                                dim3((unsigned)wide.size(), chunks), dim3(256), 0,
-                               0, M, d->col_major, d_w, A->irp, A->ja, A->as,
-                               d->off, d->ja, d->as, d->padmask);
+                               0, M, d->col_major, d_w, A->irp, A->ja, A_as,
+                               d->off, d->ja, d_as, d->padmask);
             HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipDeviceSynchronize());
@@ -1231,6 +1388,16 @@ fail:
     (void)hipFree(d_w);
     spmv_hll_release(d);
     return rc;
+}
+
+extern "C" {
+
+int spmv_hll_from_csr(const spmv_csr_dev *A, int is_col_major,
+                      spmv_hll_dev **out) {
+    HANDLE_OK(A);
+    if (A->value_bytes == 4)
+        return hll_from_csr(A, (const float *)A->as32, is_col_major, out);
+    return hll_from_csr(A, (const double *)A->as, is_col_major, out);
 }
 
 int spmv_hll_shape(const spmv_hll_dev *H, int *M, int *N, int64_t *NZ,
@@ -1253,8 +1420,8 @@ int spmv_hll_shape(const spmv_hll_dev *H, int *M, int *N, int64_t *NZ,
 
 int64_t spmv_hll_algorithmic_bytes(const spmv_hll_dev *H) {
     HANDLE_OK(H);
-    return 12 * H->slots + 12 * (int64_t)H->nb + 8 * (int64_t)H->M +
-           8 * (int64_t)H->N;
+    return (4 + H->value_bytes) * H->slots + 12 * (int64_t)H->nb +
+           8 * (int64_t)H->M + 8 * (int64_t)H->N;
 }
 
 /* what ONE launch of `kernel` has to move at least: the direct kernels read
@@ -1265,8 +1432,8 @@ int64_t spmv_hll_kernel_bytes(const spmv_hll_dev *H, int kernel) {
     HANDLE_OK(H);
     if (kernel != SPMV_HLL_KERNEL_PANELS)
         return spmv_hll_algorithmic_bytes(H);
-    return 12 * H->NZ + 12 * (int64_t)H->nb + 8 * (int64_t)H->M +
-           8 * (int64_t)H->N;
+    return (4 + H->value_bytes) * H->NZ + 12 * (int64_t)H->nb +
+           8 * (int64_t)H->M + 8 * (int64_t)H->N;
 }
 
 } /* extern "C" */
@@ -1311,15 +1478,19 @@ static int build_from(const spmv_hll_dev *H, const spmv_panel_opts *o,
 static void free_source(spmv_csr_dev *A) {
     (void)hipFree(A->ja);
     (void)hipFree(A->as);
+    (void)hipFree(A->as32);
     A->ja = NULL;
     A->as = NULL;
+    A->as32 = NULL;
 }
 static void free_source(spmv_hll_dev *H) {
     (void)hipFree(H->ja);
     (void)hipFree(H->as);
+    (void)hipFree(H->as32);
     (void)hipFree(H->padmask);
     H->ja = NULL;
     H->as = NULL;
+    H->as32 = NULL;
     H->padmask = NULL;
 }
 static int launch_direct(const spmv_csr_dev *A, int kernel,
@@ -1379,6 +1550,8 @@ static int launch(const D *d, int kernel, const spmv_launch_opts *opts,
 
 /* a new blocked copy in place of the old one: `build(&d->panels)` */
 template <typename D, typename Build> static int rebuild(D *d, Build build) {
+    if (d->value_bytes == 4)
+        return -ENOTSUP; /* the blocked copy's 12-byte entries hold fp64 values */
     if (!has_source(d))
         return -ENODATA;
     panels_free(d->panels);
@@ -1459,6 +1632,11 @@ template <typename D> static int release_source(D *d) {
         return -ENOENT; /* nothing else could run the matrix */
     free_source(d);
     return 0;
+}
+
+template <typename D> static int value_bytes_of(const D *d) {
+    HANDLE_OK(d);
+    return d->value_bytes;
 }
 
 template <typename D> static int schedule_of(const D *d) {
@@ -1652,6 +1830,11 @@ static int autotune(D *d, const double *d_x, double *d_y, int allow_panels,
     rc = direct(d, t);
     if (rc)
         return rc;
+    if (d->value_bytes == 4) {
+        t.log("blocked path: not available for f32 values (direct kernels "
+              "only)");
+        allow_panels = 0;
+    }
     if (allow_panels) {
         const double stream_ms =
             (double)algorithmic_bytes(d) / 7.0e9; /* at 7 TB/s */
@@ -1926,6 +2109,7 @@ static int copy_tune_log(const D *d, char *buf, size_t len) {
         return info_of(d, steps, tiles, panels, entries);                      \
     }                                                                          \
     int spmv_##fmt##_release_source(D *d) { return release_source(d); }        \
+    int spmv_##fmt##_value_bytes(const D *d) { return value_bytes_of(d); }     \
     int spmv_##fmt##_panels_schedule(const D *d) { return schedule_of(d); }    \
     int spmv_##fmt##_panels_describe(const D *d, char *buf, size_t len) {      \
         return describe_of(d, buf, len);                                       \

@@ -104,7 +104,10 @@ struct spmv_csr_dev {
     int device;
     int *irp;   /* [M+1] */
     int *ja;    /* [NZ]  */
-    double *as; /* [NZ]  */
+    double *as; /* [NZ]  (value_bytes 8; NULL in an f32 handle) */
+    float *as32; /* [NZ] (value_bytes 4: the values rounded to fp32; every
+                    product and sum stays fp64; NULL in an f64 handle) */
+    int value_bytes; /* 8 or 4: which of the two arrays the handle owns */
     /* stream kernel: workgroup k owns rows [rowblk[2k], rowblk[2k+2]),
      * entries [rowblk[2k+1], rowblk[2k+3]) */
     int *rowblk;
@@ -147,7 +150,9 @@ struct spmv_hll_dev {
     int64_t slots; /* S */
     int max_width; /* largest max_NZ */
     int *ja;       /* [S] pads already rewritten */
-    double *as;    /* [S] */
+    double *as;    /* [S] (value_bytes 8; NULL in an f32 handle) */
+    float *as32;   /* [S] (value_bytes 4; NULL in an f64 handle) */
+    int value_bytes; /* 8 or 4 */
     int64_t *off;  /* [nb+1] slot offset of each block */
     int order; /* kernels 1 / 2, which blocks a workgroup runs: 0 = hardware
                   order (eight XCDs advancing through ONE region of the
@@ -288,15 +293,35 @@ __device__ __forceinline__ int hack_block_width(const int64_t *__restrict__ off,
     return rows == HACK_SIZE ? (int)(n >> 5) : (int)(n / (unsigned)rows);
 }
 
+/*
+ * A stored matrix value as the fp64 factor of its product.  The fp32 form is
+ * ONE v_cvt_f64_f32 that stays where it is written, at the product.  Written
+ * as `(double)v` the compiler folds the conversion into the predicated load
+ * that produced v (the phi of "loaded value" and "0 for a lane without an
+ * entry") and then has to wait for that load before it may issue the next
+ * one: the P independent passes of the sub-wave kernel ran one memory latency
+ * after the other (banded 10M x 32: 0.839 ms against 0.784 for fp64 values
+ * that are half as many bytes again).  Denormal inputs are kept (the kernels
+ * run with fp32 denormals on).
+ */
+__device__ __forceinline__ double widen(double v) { return v; }
+__device__ __forceinline__ double widen(float v) {
+    double d;
+    asm("v_cvt_f64_f32_e32 %0, %1" : "=v"(d) : "v"(v));
+    return d;
+}
+
 /* Thread `tid` of NT sums as[k] * x[ja[k]] over k = beg + tid, + NT, ... < end
  * in THAT order (one accumulator: the bits do not depend on U), with the loads
  * of U entries in flight at a time.  The plain loop is two dependent memory
  * round trips per entry -- 4 us per 8 entries on a busy chip -- and a long
  * row's segment is 4-32 entries per thread: the side launches of the long
- * rows were latency, not bandwidth.  Entries stream past (non-temporal). */
-template <int NT, int U>
+ * rows were latency, not bandwidth.  Entries stream past (non-temporal).
+ * V = double or float, the handle's stored value type: a float is widened in
+ * the lane and the product is fp64 either way. */
+template <int NT, int U, typename V>
 __device__ __forceinline__ double strided_dot(const int *__restrict__ ja,
-                                              const double *__restrict__ as,
+                                              const V *__restrict__ as,
                                               const double *__restrict__ x,
                                               int beg, int end, int tid) {
     double acc = 0.0;
@@ -308,7 +333,8 @@ __device__ __forceinline__ double strided_dot(const int *__restrict__ ja,
     int k = tid;
     for (; k + (U - 1) * NT < end; k += U * NT) {
         int c[U];
-        double v[U], xv[U];
+        V v[U];
+        double xv[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             c[u] = __builtin_nontemporal_load(ja + k + u * NT);
@@ -319,16 +345,17 @@ __device__ __forceinline__ double strided_dot(const int *__restrict__ ja,
             xv[u] = x[c[u]];
 #pragma unroll
         for (int u = 0; u < U; ++u)
-            acc += v[u] * xv[u];
+            acc += widen(v[u]) * xv[u];
     }
     if (k < end) { /* fewer than U left: one predicated batch */
         int c[U];
-        double v[U], xv[U];
+        V v[U];
+        double xv[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const bool on = k + u * NT < end;
             c[u] = on ? __builtin_nontemporal_load(ja + k + u * NT) : -1;
-            v[u] = on ? __builtin_nontemporal_load(as + k + u * NT) : 0.0;
+            v[u] = on ? __builtin_nontemporal_load(as + k + u * NT) : V(0);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u)
@@ -336,7 +363,7 @@ __device__ __forceinline__ double strided_dot(const int *__restrict__ ja,
 #pragma unroll
         for (int u = 0; u < U; ++u)
             if (c[u] >= 0)
-                acc += v[u] * xv[u];
+                acc += widen(v[u]) * xv[u];
     }
     return acc;
 }

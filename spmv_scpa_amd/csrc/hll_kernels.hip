@@ -1,6 +1,7 @@
 /*
  * hll_kernels.hip -- fp64 HLL (hacked ELLPACK, hack = 32) SpMV kernels for
- * gfx950 (wave64).
+ * gfx950 (wave64).  Templates over the handle's STORED value type V (double,
+ * or float: 8 B per slot instead of 12); x, y, products and sums are fp64.
  *
  * Four kernels fill the four slots of the reference's driver table
  * (reference cuda_hll.cu:19-152, main.c:310-315); the designs are new.
@@ -38,6 +39,7 @@ template <typename T> __device__ __forceinline__ T ld_stream(const T *p) {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef double v2d __attribute__((ext_vector_type(2)));
+typedef float v4f __attribute__((ext_vector_type(4)));
 
 /* ------------------------------------------------------------------ */
 /* pad rewrite on the device (reference cuda_hll.cu:173-195 does it on  */
@@ -86,10 +88,11 @@ int hll_fix_pads_dev(spmv_hll_dev *H, hipStream_t s) {
 /* `wide` > 0 (kernels 0-3): the matrix has hack blocks of more than `wide`
  * columns; they are left to k_hll_wide, launched right after on the same
  * stream */
+template <typename V>
 __global__ void k_hll_row_major(int M, int b0, int b1, int wide,
                                 const int64_t *__restrict__ off,
                                 const int *__restrict__ ja,
-                                const double *__restrict__ as,
+                                const V *__restrict__ as,
                                 const double *__restrict__ x,
                                 double *__restrict__ y) {
     long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -104,7 +107,7 @@ __global__ void k_hll_row_major(int M, int b0, int b1, int wide,
     if (wide > 0 && w > wide)
         return;
     const int *rj = ja + o + (int64_t)i * w;
-    const double *ra = as + o + (int64_t)i * w;
+    const V *ra = as + o + (int64_t)i * w;
     /* the row's slots in order, four loads in flight (hip_common.h) */
     y[(int64_t)b * HACK + i] = strided_dot<1, 4>(rj, ra, x, 0, w, 0);
 }
@@ -125,11 +128,11 @@ __global__ void k_hll_row_major(int M, int b0, int b1, int wide,
  * DESIGN.md section 4).  The launch has 8 x (longest range) workgroups; the
  * surplus ones of shorter ranges exit.
  */
-template <int U, int ORDER, int ABL = 0> /* ABL 1: all gathers read x[0] */
+template <typename V, int U, int ORDER, int ABL = 0> /* ABL 1: all gathers read x[0] */
 __global__ void k_hll_col_direct(int M, int b0, int b1, int wide, xcd_ranges xr,
                                  const int64_t *__restrict__ off,
                                  const int *__restrict__ ja,
-                                 const double *__restrict__ as,
+                                 const V *__restrict__ as,
                                  const double *__restrict__ x,
                                  double *__restrict__ y) {
     int b, i;
@@ -162,10 +165,10 @@ __global__ void k_hll_col_direct(int M, int b0, int b1, int wide, xcd_ranges xr,
     if (wide > 0 && w > wide)
         return;
     const int *cj = ja + o + i;
-    const double *ca = as + o + i;
+    const V *ca = as + o + i;
     double acc = 0.0;
     int cJ[U];
-    double cA[U];
+    V cA[U];
     const int nfull = w / U;
     if (nfull > 0) {
 #pragma unroll
@@ -175,7 +178,8 @@ __global__ void k_hll_col_direct(int M, int b0, int b1, int wide, xcd_ranges xr,
         }
     }
     for (int c = 0; c < nfull; ++c) {
-        double xv[U], av[U];
+        double xv[U];
+        V av[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             xv[u] = (ABL & 1) ? x[cJ[u] & 1] : x[cJ[u]];
@@ -183,7 +187,7 @@ __global__ void k_hll_col_direct(int M, int b0, int b1, int wide, xcd_ranges xr,
         }
         if (c + 1 < nfull) {
             const int *nj = cj + (size_t)(c + 1) * U * rows;
-            const double *na = ca + (size_t)(c + 1) * U * rows;
+            const V *na = ca + (size_t)(c + 1) * U * rows;
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 cJ[u] = ld_stream(nj + u * rows);
@@ -192,10 +196,10 @@ __global__ void k_hll_col_direct(int M, int b0, int b1, int wide, xcd_ranges xr,
         }
 #pragma unroll
         for (int u = 0; u < U; ++u)
-            acc += av[u] * xv[u];
+            acc += widen(av[u]) * xv[u];
     }
     for (int j = nfull * U; j < w; ++j)
-        acc += ld_stream(ca + (size_t)j * rows) *
+        acc += widen(ld_stream(ca + (size_t)j * rows)) *
                x[ld_stream(cj + (size_t)j * rows)];
     __builtin_nontemporal_store(acc, y + (int64_t)b * HACK + i);
 }
@@ -208,14 +212,21 @@ __global__ void k_hll_col_direct(int M, int b0, int b1, int wide, xcd_ranges xr,
 #define CH 8                     /* columns per staged chunk */
 #define CH_SLOTS (CH * HACK)     /* 256 slots: 1 KiB of JA, 2 KiB of AS */
 
-struct hll_chunk {
+template <typename V> struct hll_chunk;
+template <> struct hll_chunk<double> {
     v4i jA, jB;
     v2d aA0, aA1, aB0, aB1;
+};
+/* fp32 values: a chunk's 256 values are 1 KiB like its 256 indices -- one
+ * 16 B/lane load per block, a lane's four values the slots of its indices */
+template <> struct hll_chunk<float> {
+    v4i jA, jB;
+    v4f aA, aB;
 };
 
 /* coalesced 16 B/lane loads of slots [s0, s0+256) of the wavefront's two
  * blocks (predicated past the end of each block) */
-__device__ __forceinline__ void hll_chunk_load(hll_chunk &c, int s0, int lane,
+__device__ __forceinline__ void hll_chunk_load(hll_chunk<double> &c, int s0, int lane,
                                                const int *gjA, const int *gjB,
                                                const double *gaA,
                                                const double *gaB, int nA,
@@ -232,20 +243,49 @@ __device__ __forceinline__ void hll_chunk_load(hll_chunk &c, int s0, int lane,
     c.aB1 = sa + 128 < nB ? ld_stream((const v2d *)(gaB + sa + 128)) : zd;
 }
 
-template <int ORDER>
+__device__ __forceinline__ void hll_chunk_load(hll_chunk<float> &c, int s0, int lane,
+                                               const int *gjA, const int *gjB,
+                                               const float *gaA,
+                                               const float *gaB, int nA,
+                                               int nB) {
+    const int sj = s0 + 4 * lane; /* 4 ints, 4 floats */
+    const v4i zi = {0, 0, 0, 0};
+    const v4f zf = {0, 0, 0, 0};
+    c.jA = sj < nA ? ld_stream((const v4i *)(gjA + sj)) : zi;
+    c.jB = sj < nB ? ld_stream((const v4i *)(gjB + sj)) : zi;
+    c.aA = sj < nA ? ld_stream((const v4f *)(gaA + sj)) : zf;
+    c.aB = sj < nB ? ld_stream((const v4f *)(gaB + sj)) : zf;
+}
+
+/* a chunk's values into the wavefront's LDS slice (two blocks x CH_SLOTS) */
+__device__ __forceinline__ void hll_chunk_store(const hll_chunk<double> &c,
+                                                double *s_as, int lane) {
+    *(v2d *)(s_as + 2 * lane) = c.aA0;
+    *(v2d *)(s_as + 128 + 2 * lane) = c.aA1;
+    *(v2d *)(s_as + CH_SLOTS + 2 * lane) = c.aB0;
+    *(v2d *)(s_as + CH_SLOTS + 128 + 2 * lane) = c.aB1;
+}
+__device__ __forceinline__ void hll_chunk_store(const hll_chunk<float> &c,
+                                                float *s_as, int lane) {
+    *(v4f *)(s_as + 4 * lane) = c.aA;
+    *(v4f *)(s_as + CH_SLOTS + 4 * lane) = c.aB;
+}
+
+template <int ORDER, typename V>
 __global__ void k_hll_col_lds(int b0, int b1, int wide, xcd_ranges xr,
                               const int64_t *__restrict__ off,
                               const int *__restrict__ ja,
-                              const double *__restrict__ as,
+                              const V *__restrict__ as,
                               const double *__restrict__ x,
                               double *__restrict__ y) {
-    /* per wavefront: two blocks x (256 ints + 256 doubles) = 6 KiB */
+    /* per wavefront: two blocks x (256 ints + 256 values) = 6 KiB (fp64
+     * values) or 4 KiB (fp32): values of all wavefronts first, then indices */
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     const int lane = threadIdx.x & (WAVE - 1);
     const int wave = threadIdx.x / WAVE;
     const int waves = blockDim.x / WAVE;
-    double *s_as = (double *)lds_raw + (size_t)wave * 2 * CH_SLOTS;
-    int *s_ja = (int *)((double *)lds_raw + (size_t)waves * 2 * CH_SLOTS) +
+    V *s_as = (V *)lds_raw + (size_t)wave * 2 * CH_SLOTS;
+    int *s_ja = (int *)((V *)lds_raw + (size_t)waves * 2 * CH_SLOTS) +
                 (size_t)wave * 2 * CH_SLOTS;
 
     int bA; /* wave-uniform */
@@ -278,22 +318,19 @@ __global__ void k_hll_col_lds(int b0, int b1, int wide, xcd_ranges xr,
     const int nmax = nA > nB ? nA : nB;
 
     const int *gjA = ja + oA, *gjB = ja + oB;
-    const double *gaA = as + oA, *gaB = as + oB;
+    const V *gaA = as + oA, *gaB = as + oB;
     const int *lj = s_ja + half * CH_SLOTS + i;
-    const double *la = s_as + half * CH_SLOTS + i;
+    const V *la = s_as + half * CH_SLOTS + i;
     double acc = 0.0;
 
     /* register-staged pipeline: chunk c+1 is in flight from HBM while chunk
      * c is consumed out of LDS */
-    hll_chunk cur;
+    hll_chunk<V> cur;
     hll_chunk_load(cur, 0, lane, gjA, gjB, gaA, gaB, nA, nB);
     for (int s0 = 0; s0 < nmax; s0 += CH_SLOTS) {
         *(v4i *)(s_ja + 4 * lane) = cur.jA;
         *(v4i *)(s_ja + CH_SLOTS + 4 * lane) = cur.jB;
-        *(v2d *)(s_as + 2 * lane) = cur.aA0;
-        *(v2d *)(s_as + 128 + 2 * lane) = cur.aA1;
-        *(v2d *)(s_as + CH_SLOTS + 2 * lane) = cur.aB0;
-        *(v2d *)(s_as + CH_SLOTS + 128 + 2 * lane) = cur.aB1;
+        hll_chunk_store(cur, s_as, lane);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -301,7 +338,8 @@ __global__ void k_hll_col_lds(int b0, int b1, int wide, xcd_ranges xr,
         /* this lane's 8 columns out of LDS, their x gathers issued first */
         const int c0 = s0 >> 5;
         int cc[CH];
-        double av[CH], xv[CH];
+        V av[CH];
+        double xv[CH];
 #pragma unroll
         for (int jj = 0; jj < CH; ++jj) {
             cc[jj] = lj[jj * HACK];
@@ -316,7 +354,7 @@ __global__ void k_hll_col_lds(int b0, int b1, int wide, xcd_ranges xr,
 #pragma unroll
         for (int jj = 0; jj < CH; ++jj)
             if (c0 + jj < w)
-                acc += av[jj] * xv[jj];
+                acc += (double)av[jj] * xv[jj];
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
@@ -327,10 +365,11 @@ __global__ void k_hll_col_lds(int b0, int b1, int wide, xcd_ranges xr,
 /* ------------------------------------------------------------------ */
 /* 3: 16 lanes per row, row-major                                       */
 /* ------------------------------------------------------------------ */
+template <typename V>
 __global__ void k_hll_subwave_row(int M, int b0, int b1, int wide,
                                   const int64_t *__restrict__ off,
                                   const int *__restrict__ ja,
-                                  const double *__restrict__ as,
+                                  const V *__restrict__ as,
                                   const double *__restrict__ x,
                                   double *__restrict__ y) {
     const int sub = threadIdx.x & 15;
@@ -355,7 +394,7 @@ __global__ void k_hll_subwave_row(int M, int b0, int b1, int wide,
                 int w = hack_block_width(off, b, rows);
                 live = !(wide > 0 && w > wide);
                 const int *rj = ja + o + (int64_t)i * w;
-                const double *ra = as + o + (int64_t)i * w;
+                const V *ra = as + o + (int64_t)i * w;
                 if (live)
                     acc = strided_dot<16, 4>(rj, ra, x, 0, w, sub);
             }
@@ -374,10 +413,11 @@ __global__ void k_hll_subwave_row(int M, int b0, int b1, int wide,
 /* block's last segment to arrive adds the partial row sums in a fixed      */
 /* order (deterministic), writes y and re-arms the counter.                */
 /* ------------------------------------------------------------------ */
+template <typename V>
 __global__ void __launch_bounds__(256)
     k_hll_wide(int M, int b0, int b1, int col_major,
                const int4 *__restrict__ seg, const int64_t *__restrict__ off,
-               const int *__restrict__ ja, const double *__restrict__ as,
+               const int *__restrict__ ja, const V *__restrict__ as,
                const double *__restrict__ x, double *__restrict__ y,
                double *part, unsigned long long *cnt, unsigned epoch) {
     __shared__ double red[8][HACK];
@@ -407,7 +447,8 @@ __global__ void __launch_bounds__(256)
         constexpr int U = 8;
         for (; j + 8 * (U - 1) < j1; j += 8 * U) {
             int c[U];
-            double v[U], xv[U];
+            V v[U];
+            double xv[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int64_t t = base + (int64_t)(j + 8 * u) * step;
@@ -419,11 +460,11 @@ __global__ void __launch_bounds__(256)
                 xv[u] = x[c[u]];
 #pragma unroll
             for (int u = 0; u < U; ++u)
-                acc += v[u] * xv[u];
+                acc += widen(v[u]) * xv[u];
         }
         for (; j < j1; j += 8) {
             const int64_t t = base + (int64_t)j * step;
-            acc += ld_stream(as + t) * x[ld_stream(ja + t)];
+            acc += widen(ld_stream(as + t)) * x[ld_stream(ja + t)];
         }
     }
     red[cl][i] = acc;
@@ -465,9 +506,10 @@ __global__ void __launch_bounds__(256)
 }
 
 /* ------------------------------------------------------------------ */
-int hll_launch_kernel(const spmv_hll_dev *H, int kernel, int waves,
-                      int variant, const double *x, double *y, int b0, int b1,
-                      hipStream_t s) {
+template <typename V>
+static int hll_launch_t(const spmv_hll_dev *H, const V *as, int kernel,
+                        int waves, int variant, const double *x, double *y,
+                        int b0, int b1, hipStream_t s) {
     (void)hipGetLastError(); /* an earlier caller's unread error is not ours */
     if (!H || !x || !y || b0 < 0 || b1 > H->nb || b0 > b1)
         return -EINVAL;
@@ -504,10 +546,10 @@ int hll_launch_kernel(const spmv_hll_dev *H, int kernel, int waves,
                    ? xr.first[k + 1] - xr.first[k] : xmax;
     switch (kernel) {
     case 0:
-        hipLaunchKernelGGL(k_hll_row_major,
+        hipLaunchKernelGGL(k_hll_row_major<V>,
                            dim3((unsigned)((lanes + threads - 1) / threads)),
                            dim3(threads), 0, s, H->M, b0, b1, wide, H->off,
-                           H->ja, H->as, x, y);
+                           H->ja, as, x, y);
         break;
     case 1: {
         /* full blocks through LDS; a ragged last block goes direct */
@@ -516,28 +558,28 @@ int hll_launch_kernel(const spmv_hll_dev *H, int kernel, int waves,
             full_end = b1 - 1;
         if (full_end > b0) {
             int pairs = (full_end - b0 + 1) / 2;
-            size_t lds = (size_t)waves * 2 * CH_SLOTS * (sizeof(double) + sizeof(int));
+            size_t lds = (size_t)waves * 2 * CH_SLOTS * (sizeof(V) + sizeof(int));
             const int nwg = (pairs + waves - 1) / waves;
             if (order == 1)
-                hipLaunchKernelGGL(k_hll_col_lds<1>,
+                hipLaunchKernelGGL((k_hll_col_lds<1, V>),
                                    dim3(NUM_XCD * (((xmax + 1) / 2 + waves - 1) /
                                                    waves)),
                                    dim3(threads), lds, s, b0, full_end, wide, xr,
-                                   H->off, H->ja, H->as, x, y);
+                                   H->off, H->ja, as, x, y);
             else if (order == 2)
-                hipLaunchKernelGGL(k_hll_col_lds<2>,
+                hipLaunchKernelGGL((k_hll_col_lds<2, V>),
                                    dim3((nwg + NUM_XCD * HLL_GROUP - 1) /
                                         (NUM_XCD * HLL_GROUP) * NUM_XCD * HLL_GROUP),
                                    dim3(threads), lds, s, b0, full_end, wide, xr,
-                                   H->off, H->ja, H->as, x, y);
+                                   H->off, H->ja, as, x, y);
             else
-                hipLaunchKernelGGL(k_hll_col_lds<0>, dim3(nwg), dim3(threads),
+                hipLaunchKernelGGL((k_hll_col_lds<0, V>), dim3(nwg), dim3(threads),
                                    lds, s, b0, full_end, wide, xr, H->off, H->ja,
-                                   H->as, x, y);
+                                   as, x, y);
         }
         if (full_end < b1)
-            hipLaunchKernelGGL((k_hll_col_direct<8, 0>), dim3(1), dim3(WAVE), 0, s,
-                               H->M, full_end, b1, wide, xr, H->off, H->ja, H->as, x, y);
+            hipLaunchKernelGGL((k_hll_col_direct<V, 8, 0>), dim3(1), dim3(WAVE), 0, s,
+                               H->M, full_end, b1, wide, xr, H->off, H->ja, as, x, y);
         break;
     }
     case 2: {
@@ -546,56 +588,67 @@ int hll_launch_kernel(const spmv_hll_dev *H, int kernel, int waves,
             NUM_XCD * (unsigned)(((long long)xmax * HACK + threads - 1) / threads);
 #ifdef SPMV_ABLATIONS /* experiment arms: `make abl` builds them */
         if (variant & 32) { /* tuning: 4 columns per pipeline stage */
-            hipLaunchKernelGGL((k_hll_col_direct<4, 1>), dim3(xgrid),
+            hipLaunchKernelGGL((k_hll_col_direct<V, 4, 1>), dim3(xgrid),
                                dim3(threads), 0, s, H->M, b0, b1, wide, xr, H->off,
-                               H->ja, H->as, x, y);
+                               H->ja, as, x, y);
             break;
         }
         if (variant & 64) { /* tuning: 16 columns per pipeline stage */
-            hipLaunchKernelGGL((k_hll_col_direct<16, 1>), dim3(xgrid),
+            hipLaunchKernelGGL((k_hll_col_direct<V, 16, 1>), dim3(xgrid),
                                dim3(threads), 0, s, H->M, b0, b1, wide, xr, H->off,
-                               H->ja, H->as, x, y);
+                               H->ja, as, x, y);
             break;
         }
         if (variant & 16) { /* ABL 1: every gather reads x[0..1]: WRONG y */
-            hipLaunchKernelGGL((k_hll_col_direct<8, 1, 1>), dim3(xgrid),
+            hipLaunchKernelGGL((k_hll_col_direct<V, 8, 1, 1>), dim3(xgrid),
                                dim3(threads), 0, s, H->M, b0, b1, wide, xr, H->off,
-                               H->ja, H->as, x, y);
+                               H->ja, as, x, y);
             break;
         }
 #endif
         const unsigned hwgrid = (unsigned)((lanes + threads - 1) / threads);
         if (order == 1)
-            hipLaunchKernelGGL((k_hll_col_direct<8, 1>), dim3(xgrid),
+            hipLaunchKernelGGL((k_hll_col_direct<V, 8, 1>), dim3(xgrid),
                                dim3(threads), 0, s, H->M, b0, b1, wide, xr, H->off,
-                               H->ja, H->as, x, y);
+                               H->ja, as, x, y);
         else if (order == 2)
-            hipLaunchKernelGGL((k_hll_col_direct<8, 2>),
+            hipLaunchKernelGGL((k_hll_col_direct<V, 8, 2>),
                                dim3((hwgrid + NUM_XCD * HLL_GROUP - 1) /
                                     (NUM_XCD * HLL_GROUP) * NUM_XCD * HLL_GROUP),
                                dim3(threads), 0, s, H->M, b0, b1, wide, xr, H->off,
-                               H->ja, H->as, x, y);
+                               H->ja, as, x, y);
         else
-            hipLaunchKernelGGL((k_hll_col_direct<8, 0>), dim3(hwgrid),
+            hipLaunchKernelGGL((k_hll_col_direct<V, 8, 0>), dim3(hwgrid),
                                dim3(threads), 0, s, H->M, b0, b1, wide, xr, H->off,
-                               H->ja, H->as, x, y);
+                               H->ja, as, x, y);
         break;
     }
     case 3:
         hipLaunchKernelGGL(
-            k_hll_subwave_row,
+            k_hll_subwave_row<V>,
             dim3((unsigned)std::min<long long>((lanes * 16 + threads - 1) / threads,
                                                0xFFFFFFFFll / threads)),
-            dim3(threads), 0, s, H->M, b0, b1, wide, H->off, H->ja, H->as, x,
+            dim3(threads), 0, s, H->M, b0, b1, wide, H->off, H->ja, as, x,
             y);
         break;
     default:
         return -EINVAL;
     }
     if (wide > 0)
-        hipLaunchKernelGGL(k_hll_wide, dim3(H->n_wide_seg), dim3(256), 0, s,
+        hipLaunchKernelGGL(k_hll_wide<V>, dim3(H->n_wide_seg), dim3(256), 0, s,
                            H->M, b0, b1, H->col_major, H->wide_seg, H->off,
-                           H->ja, H->as, x, y, H->wide_part, H->wide_cnt,
+                           H->ja, as, x, y, H->wide_part, H->wide_cnt,
                            next_launch_epoch(&H->launch_epoch));
     return hip_errno(hipGetLastError());
+}
+
+/* dispatch on the handle's value type (hip_common.h: value_bytes) */
+int hll_launch_kernel(const spmv_hll_dev *H, int kernel, int waves,
+                      int variant, const double *x, double *y, int b0, int b1,
+                      hipStream_t s) {
+    if (H && H->value_bytes == 4)
+        return hll_launch_t(H, (const float *)H->as32, kernel, waves, variant,
+                            x, y, b0, b1, s);
+    return hll_launch_t(H, H ? (const double *)H->as : NULL, kernel, waves,
+                        variant, x, y, b0, b1, s);
 }
