@@ -370,6 +370,46 @@ int spmv_hll_time(const spmv_hll_dev *H, int kernel,
                   void *stream);
 
 /*
+ * Several right-hand sides in one launch (added after 0.7; spmv_version() is
+ * unchanged, callers detect the feature by the symbol).
+ *
+ * Y[r*ldy + j] = sum_c A[r][c] * X[c*ldx + j],  j = 0..k-1,  1 <= k <= 8.
+ * X: N rows of ldx doubles, Y: M rows of ldy doubles (row-major,
+ * "interleaved"); ldx, ldy >= k (0 = k).  Only columns 0..k-1 of a row of Y
+ * are written.  X and Y must not overlap.  Whole matrix only.  Asynchronous
+ * on `stream`, stream-ordered and capturable like every other launch.  The
+ * matrix is read once for all k products and the k values of a column are one
+ * request to one cache line (16-byte loads of pairs, whatever ldx and the
+ * alignment of d_X are).  Both value types of a handle.
+ *
+ * Order: column j of Y has the bits of spmv_csr_launch(A, 2, opts with the
+ * same group) / spmv_hll_launch(H, 1) on the contiguous vector X[:, j], for
+ * every row of at most 2048 entries / hack block of at most 512 columns;
+ * longer rows and wider blocks are summed by one workgroup each in a fixed
+ * order (reproducible, within 1e-12 of the row scale sum |a x|).
+ *
+ * opts may be NULL; waves_per_block and (CSR) group as in the single-vector
+ * launch; variant and reserved must be 0 (the workgroup order is the
+ * handle's and never changes a result).  -EINVAL: NULL handle, k outside
+ * 1..8, ldx / ldy below k, NULL d_X / d_Y, waves_per_block outside 0..16, a
+ * group that is not 0, 2, 4, 8, 16 or 32, a nonzero variant / reserved word,
+ * a row-major HLL handle.  -EBADF: not a live handle (-ENODEV when there is
+ * no GPU at all).  -ENODATA after spmv_*_release_source().  M == 0: returns 0
+ * and launches nothing.
+ */
+int spmv_csr_launch_multi(const spmv_csr_dev *A, const spmv_launch_opts *opts,
+                          int k, const double *d_X, int64_t ldx,
+                          double *d_Y, int64_t ldy, void *stream);
+int spmv_hll_launch_multi(const spmv_hll_dev *H, const spmv_launch_opts *opts,
+                          int k, const double *d_X, int64_t ldx,
+                          double *d_Y, int64_t ldy, void *stream);
+/* bytes one launch_multi must move: (4 + value_bytes) * NZ (slots for HLL) +
+ * the index / offset arrays as in spmv_*_algorithmic_bytes + 8*k*M + 8*k*N;
+ * -EINVAL for k outside 1..8 */
+int64_t spmv_csr_multi_bytes(const spmv_csr_dev *A, int k);
+int64_t spmv_hll_multi_bytes(const spmv_hll_dev *H, int k);
+
+/*
  * Pick the fastest kernel for this matrix by measurement (5 launches each):
  * the coalesced kernels of the handle's layout and, when allow_panels != 0
  * and those run well below the stream rate, the 2-D blocked path (built on

@@ -564,6 +564,10 @@ _TWINS = (
     ("algorithmic_bytes", C.c_int64, C.c_void_p),
     ("value_bytes", C.c_int, C.c_void_p),
     ("release", None, C.c_void_p),
+    ("launch_multi", C.c_int,
+     C.c_void_p, C.POINTER(LaunchOpts), C.c_int, C.c_void_p, C.c_int64,
+     C.c_void_p, C.c_int64, C.c_void_p),
+    ("multi_bytes", C.c_int64, C.c_void_p, C.c_int),
     ("time", C.c_int,
      C.c_void_p, C.c_int, C.POINTER(LaunchOpts), C.c_void_p, C.c_void_p,
      C.c_int, C.c_int, C.c_size_t, _dp, C.c_void_p),
@@ -1263,6 +1267,29 @@ class _Device:
         """8 (fp64 values) or 4 (stored as fp32; products and sums stay
         fp64)"""
         return self._call("value_bytes")
+
+    def launch_multi(self, d_X, d_Y, k, ldx=0, ldy=0, waves_per_block=0,
+                     group=0, stream=None):
+        """Y[r*ldy + j] = sum_c A[r][c] * X[c*ldx + j] for j < k, 1 <= k <= 8
+        vectors stored interleaved (ldx, ldy >= k; 0 = k): the matrix is read
+        once for all k products.  Column j has the bits of launch(2, group)
+        (CSR) / launch(1) (HLL, column-major only) on X[:, j].  X and Y must
+        not overlap; only k columns of a row of Y are written.  `group` is
+        ignored by HLL."""
+        k, ldx, ldy = int(k), int(ldx), int(ldy)
+        if not 1 <= k <= 8:
+            raise ValueError("k=%r: 1..8 vectors per launch" % (k,))
+        if (ldx and ldx < k) or (ldy and ldy < k):
+            raise ValueError("ldx=%d, ldy=%d: at least k=%d (or 0)"
+                             % (ldx, ldy, k))
+        o = _opts(waves_per_block, group if self._FMT == "csr" else 0)
+        self._call("launch_multi", C.byref(o), k, d_X, ldx, d_Y, ldy, stream)
+
+    def multi_bytes(self, k):
+        """bytes one launch_multi(k) must move: the matrix once, k vectors
+        read and k written"""
+        return _check(self._fn("multi_bytes")(self.h, int(k)),
+                      "spmv_%s_multi_bytes" % self._FMT)
 
     def build_panels(self, panel_cols=0, sched=None, tile_rows=0,
                      sweep_wgs_per_cu=0, reserve_cus=0, lds_min=0,

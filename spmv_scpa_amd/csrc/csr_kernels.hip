@@ -608,16 +608,6 @@ template <> const float *values_of<float>(const spmv_csr_dev *A) {
     return A->as32;
 }
 
-static int pick_group(const spmv_csr_dev *A, int group) {
-    if (group >= 2 && group <= 32 && (group & (group - 1)) == 0)
-        return group;
-    double mean = A->M > 0 ? (double)A->NZ / A->M : 1.0;
-    int g = 2;
-    while (g < 32 && g < mean)
-        g <<= 1;
-    return g;
-}
-
 template <typename V, int G, int P, bool UNI>
 static void launch_subwave_u(int r0, int r1, int threads, int order,
                              const spmv_csr_dev *A, const double *x, double *y,

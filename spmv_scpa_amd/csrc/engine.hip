@@ -1548,6 +1548,75 @@ static int launch(const D *d, int kernel, const spmv_launch_opts *opts,
     return launch_range(d, kernel, opts, d_x, d_y, 0, units(d), stream);
 }
 
+/* ---- Y = A X, 1..8 interleaved vectors (multi_kernels.hip) ---- */
+static bool multi_group_ok(const spmv_csr_dev *, int g) {
+    return g == 0 || (g >= 2 && g <= 32 && (g & (g - 1)) == 0);
+}
+static bool multi_group_ok(const spmv_hll_dev *, int) { return true; }
+/* the multi-vector HLL kernel is the column-major one */
+static bool multi_layout_ok(const spmv_csr_dev *) { return true; }
+static bool multi_layout_ok(const spmv_hll_dev *H) { return H->col_major != 0; }
+static int multi_direct(const spmv_csr_dev *A, const spmv_launch_opts *opts,
+                        int k, const double *X, int64_t ldx, double *Y,
+                        int64_t ldy, hipStream_t s) {
+    return csr_launch_multi(A, pick_waves(opts, default_waves(g_csr_waves, A->M)),
+                            opts ? opts->group : 0, k, X, ldx, Y, ldy, s);
+}
+static int multi_direct(const spmv_hll_dev *H, const spmv_launch_opts *opts,
+                        int k, const double *X, int64_t ldx, double *Y,
+                        int64_t ldy, hipStream_t s) {
+    return hll_launch_multi(H, pick_waves(opts, default_waves(g_hll_waves, H->M)),
+                            k, X, ldx, Y, ldy, s);
+}
+static int64_t matrix_bytes(const spmv_csr_dev *A) {
+    return (4 + A->value_bytes) * A->NZ + 4 * ((int64_t)A->M + 1);
+}
+static int64_t matrix_bytes(const spmv_hll_dev *H) {
+    return (4 + H->value_bytes) * H->slots + 12 * (int64_t)H->nb;
+}
+
+template <typename D>
+static int launch_multi(const D *d, const spmv_launch_opts *opts, int k,
+                        const double *d_X, int64_t ldx, double *d_Y,
+                        int64_t ldy, void *stream) {
+    if (!d)
+        return -EINVAL;
+    if (!live_has(d)) /* without a device no handle can be live: -ENODEV is
+                         the more useful answer (as spmv_csr_to_f32) */
+        return spmv_device_count() == 0 ? -ENODEV : -EBADF;
+    if (k < 1 || k > 8)
+        return -EINVAL;
+    if (ldx == 0)
+        ldx = k;
+    if (ldy == 0)
+        ldy = k;
+    if (ldx < k || ldy < k || !d_X || !d_Y)
+        return -EINVAL;
+    if (opts) {
+        if (opts->waves_per_block < 0 || opts->waves_per_block > 16 ||
+            !multi_group_ok(d, opts->group) || opts->variant)
+            return -EINVAL;
+        for (int r : opts->reserved)
+            if (r)
+                return -EINVAL;
+    }
+    if (!multi_layout_ok(d))
+        return -EINVAL;
+    if (!has_source(d))
+        return -ENODATA; /* spmv_*_release_source() */
+    if (d->M == 0)
+        return 0;
+    return multi_direct(d, opts, k, d_X, ldx, d_Y, ldy, (hipStream_t)stream);
+}
+
+/* what one launch_multi has to move at least: the matrix once, k vectors */
+template <typename D> static int64_t multi_bytes(const D *d, int k) {
+    HANDLE_OK(d);
+    if (k < 1 || k > 8)
+        return -EINVAL;
+    return matrix_bytes(d) + 8 * (int64_t)k * d->M + 8 * (int64_t)k * d->N;
+}
+
 /* a new blocked copy in place of the old one: `build(&d->panels)` */
 template <typename D, typename Build> static int rebuild(D *d, Build build) {
     if (d->value_bytes == 4)
@@ -2083,6 +2152,14 @@ static int copy_tune_log(const D *d, char *buf, size_t len) {
                              const spmv_launch_opts *opts, const double *d_x,  \
                              double *d_y, int begin, int end, void *stream) {  \
         return launch_range(d, kernel, opts, d_x, d_y, begin, end, stream);    \
+    }                                                                          \
+    int spmv_##fmt##_launch_multi(const D *d, const spmv_launch_opts *opts,    \
+                                  int k, const double *d_X, int64_t ldx,       \
+                                  double *d_Y, int64_t ldy, void *stream) {    \
+        return launch_multi(d, opts, k, d_X, ldx, d_Y, ldy, stream);           \
+    }                                                                          \
+    int64_t spmv_##fmt##_multi_bytes(const D *d, int k) {                      \
+        return multi_bytes(d, k);                                              \
     }                                                                          \
     int spmv_##fmt##_time(const D *d, int kernel,                              \
                           const spmv_launch_opts *opts, const double *d_x,     \

@@ -379,6 +379,26 @@ static inline int pick_waves(const spmv_launch_opts *o, int dflt) {
     return w;
 }
 
+/* lanes per row of the CSR sub-wave kernels (single- and multi-vector): the
+ * caller's power of two in 2..32, else by the mean row length */
+static inline int pick_group(const spmv_csr_dev *A, int group) {
+    if (group >= 2 && group <= 32 && (group & (group - 1)) == 0)
+        return group;
+    double mean = A->M > 0 ? (double)A->NZ / A->M : 1.0;
+    int g = 2;
+    while (g < 32 && g < mean)
+        g <<= 1;
+    return g;
+}
+
+/* Y = A X for k = 1..8 interleaved vectors (multi_kernels.hip); the caller
+ * has checked the arguments, `waves` is 1..16 */
+int csr_launch_multi(const spmv_csr_dev *A, int waves, int group, int k,
+                     const double *X, int64_t ldx, double *Y, int64_t ldy,
+                     hipStream_t s);
+int hll_launch_multi(const spmv_hll_dev *H, int waves, int k, const double *X,
+                     int64_t ldx, double *Y, int64_t ldy, hipStream_t s);
+
 /* kernel launchers (csr_kernels.hip / hll_kernels.hip) */
 int csr_launch_kernel(const spmv_csr_dev *A, int kernel, int waves, int group,
                       int variant, const double *x, double *y, int r0, int r1,
