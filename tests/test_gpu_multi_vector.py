@@ -255,6 +255,13 @@ def test_two_launches_give_the_same_bits_in_every_row(values):
 
 # ---------------------------------------------------------- 4. special values
 def test_a_nan_stays_in_its_column_and_empty_rows_give_exactly_zero():
+    """One NaN at X[1, 1]: it stays in column 1 of Y, in exactly the rows that
+    hold matrix column 1.  For the HLL handle that is a property of THIS
+    input: the NaN is not on column 0, and no row holding column 1 is followed
+    by a pad (each is as wide as its hack block), so no pad carries it to
+    another row.  A non-finite x[0], or one on the last valid column of a
+    padded row, reaches more rows of a direct HLL launch --
+    test_gpu_multi_vector_edges.py pins that down against the padded oracle."""
     rows = [[(0, 1.0), (1, 2.0)], [], [(2, 1.0)], [(1, 0.5), (3, -1.0)],
             [(4, 0.0), (5, 0.0)]]
     rows += [[] for _ in range(40)] + [[(0, 0.0)], [(1, 3.0)]]
