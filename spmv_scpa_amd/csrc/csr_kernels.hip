@@ -33,42 +33,6 @@
 #include <type_traits>
 #include "hip_common.h"
 
-template <typename T> __device__ __forceinline__ T ld_stream(const T *p) {
-    return __builtin_nontemporal_load(p);
-}
-
-/*
- * Segmented reduction inside a wavefront: sum over groups of G consecutive
- * lanes, result in the first lane of each group (what a __shfl_down(width G)
- * tree gives).  Offsets 8,4,2,1 stay inside a 16-lane DPP row and run on the
- * VALU as row_shl moves (no LDS-crossbar ds_bpermute); only the 16- and
- * 32-lane steps use __shfl_down.
- */
-template <int CTRL> __device__ __forceinline__ double dpp_f64(double v) {
-    const long long b = __builtin_bit_cast(long long, v);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, 0xf, 0xf, true);
-    const int hi =
-        __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xf, 0xf, true);
-    return __builtin_bit_cast(
-        double, ((long long)hi << 32) | (unsigned long long)(unsigned)lo);
-}
-
-template <int G> __device__ __forceinline__ double group_sum(double v) {
-    if (G >= 64)
-        v += __shfl_down(v, 32, 64);
-    if (G >= 32)
-        v += __shfl_down(v, 16, G >= 64 ? 64 : 32);
-    if (G >= 16)
-        v += dpp_f64<0x108>(v); /* row_shl:8 */
-    if (G >= 8)
-        v += dpp_f64<0x104>(v); /* row_shl:4 */
-    if (G >= 4)
-        v += dpp_f64<0x102>(v); /* row_shl:2 */
-    if (G >= 2)
-        v += dpp_f64<0x101>(v); /* row_shl:1 */
-    return v;
-}
-
 /* ------------------------------------------------------------------ */
 /* `lrow` > 0 (kernels 0-3): the matrix has rows of more than `lrow` (2048:
  * the stream kernel's entry budget, i.e. rows that own a range) entries;
@@ -119,15 +83,6 @@ __global__ void k_csr_wave_row(int r0, int r1, int lrow,
 }
 
 /* ------------------------------------------------------------------ */
-__device__ __forceinline__ int xcd_remap(int bid, int nblk) {
-    /* contiguous range of the grid per XCD (bijective for any nblk): row
-     * tiles that share an x window then meet in the same L2 */
-    const int nx = 8;
-    int q = nblk / nx, r = nblk % nx;
-    int x = bid % nx, k = bid / nx;
-    return x * q + (x < r ? x : r) + k;
-}
-
 /*
  * G lanes per row, P rows per lane group: a wavefront owns P*(64/G)
  * consecutive rows.  The P passes are independent, so their IRP, JA/AS and x
@@ -135,12 +90,6 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
  * instead of 768 B): the kernel is latency-bound otherwise (1 pass 1.30 ms,
  * 4 passes 0.83 ms, 8 passes 0.79 ms on banded 10M x 32).
  */
-#define CSR_GROUP 32 /* grouped order: runs of 32 workgroups per XCD */
-__device__ __forceinline__ int xcd_grouped(int bid) {
-    const int xx = bid % 8, kk = bid / 8;
-    return ((kk / CSR_GROUP) * 8 + xx) * CSR_GROUP + kk % CSR_GROUP;
-}
-
 /* UNI: every row of the matrix holds exactly `ulen` entries (the handle
  * found that out at upload), so IRP[r] = r * ulen needs no load: the wavefront
  * fetches JA / AS at once instead of one memory latency later.  A launch of
@@ -159,10 +108,11 @@ __global__ void k_csr_subwave_row(int r0, int r1, int ulen, int lrow,
     const int lane = threadIdx.x & (WAVE - 1);
     const int sub = lane & (G - 1);
     /* ORDER 0: hardware order, 1: XCD-contiguous equal ranges, 2: grouped
-     * (the grid is then padded to a multiple of 8 x CSR_GROUP; rows beyond
-     * r1 are masked below) */
-    const int bid = ORDER == 1 ? xcd_remap(blockIdx.x, gridDim.x)
-                    : ORDER == 2 ? xcd_grouped(blockIdx.x) : (int)blockIdx.x;
+     * (the grid is then padded to a multiple of NUM_XCD x XCD_GROUP; rows
+     * beyond r1 are masked below) */
+    const int bid = ORDER == 1   ? xcd_remap(blockIdx.x, gridDim.x)
+                    : ORDER == 2 ? xcd_grouped<int>(blockIdx.x)
+                                 : (int)blockIdx.x;
     const long long wave_global =
         ((long long)bid * blockDim.x + threadIdx.x) / WAVE;
     const long long rbase = (long long)r0 + wave_global * (P * RPP) + lane / G;
@@ -362,7 +312,7 @@ __global__ void __launch_bounds__(STREAM_THREADS)
      * contiguous runs of equal work -- eight distant regions of JA/AS
      * streamed at once -- were measured SLOWER than hardware order (banded
      * 0.738 vs 0.704, stencil 0.621 vs 0.605, 1M x 16 0.049 vs 0.046). */
-    const int rb = grouped ? xcd_grouped(blockIdx.x) : (int)blockIdx.x;
+    const int rb = grouped ? xcd_grouped<int>(blockIdx.x) : (int)blockIdx.x;
     if (rb >= n_rowblk)
         return;
     const int2 t_a = rowblk[rb], t_z = rowblk[rb + 1]; /* (row, entry) */
@@ -599,15 +549,6 @@ __global__ void __launch_bounds__(STREAM_THREADS)
 }
 
 /* ------------------------------------------------------------------ */
-/* the handle's value array as the type the kernels are instantiated for */
-template <typename V> static const V *values_of(const spmv_csr_dev *A);
-template <> const double *values_of<double>(const spmv_csr_dev *A) {
-    return A->as;
-}
-template <> const float *values_of<float>(const spmv_csr_dev *A) {
-    return A->as32;
-}
-
 template <typename V, int G, int P, bool UNI>
 static void launch_subwave_u(int r0, int r1, int threads, int order,
                              const spmv_csr_dev *A, const double *x, double *y,
@@ -624,10 +565,9 @@ static void launch_subwave_u(int r0, int r1, int threads, int order,
                            A->ja, values_of<V>(A), x, y);
     else if (order == 2)
         hipLaunchKernelGGL((k_csr_subwave_row<G, P, 2, UNI, V>),
-                           dim3((grid + 8 * CSR_GROUP - 1) / (8 * CSR_GROUP) *
-                                8 * CSR_GROUP),
-                           dim3(threads), 0, s, r0, r1, ulen, lrow, A->irp,
-                           A->ja, values_of<V>(A), x, y);
+                           dim3(grouped_grid(grid)), dim3(threads), 0, s, r0,
+                           r1, ulen, lrow, A->irp, A->ja, values_of<V>(A), x,
+                           y);
     else
         hipLaunchKernelGGL((k_csr_subwave_row<G, P, 0, UNI, V>), dim3(grid),
                            dim3(threads), 0, s, r0, r1, ulen, lrow, A->irp,
@@ -791,9 +731,7 @@ static int csr_launch_t(const spmv_csr_dev *A, int kernel, int waves, int group,
             const int grp = (variant & 32) ? 1 : (variant & 64) ? 0
                                                                : A->stream_grouped;
             const unsigned grid =
-                grp ? (unsigned)((A->n_rowblk + 8 * CSR_GROUP - 1) /
-                                 (8 * CSR_GROUP) * 8 * CSR_GROUP)
-                    : (unsigned)A->n_rowblk;
+                grp ? grouped_grid(A->n_rowblk) : (unsigned)A->n_rowblk;
             if (variant & 16) /* tuning: 4- / 8-byte loads only */
                 hipLaunchKernelGGL((k_csr_stream<false, V>), dim3(grid),
                                    dim3(STREAM_THREADS), 0, s, A->n_rowblk, grp,

@@ -1,6 +1,8 @@
 /*
  * hip_common.h -- internals shared by the HIP translation units
- * (engine.hip, csr_kernels.hip, hll_kernels.hip).  Not installed.
+ * (engine.hip, csr_kernels.hip, hll_kernels.hip, multi_kernels.hip,
+ * panels.hip, mgpu.hip, and mat_ref.h on behalf of the first and the last).
+ * Not installed.
  */
 #ifndef SPMV_HIP_COMMON_H
 #define SPMV_HIP_COMMON_H
@@ -8,6 +10,7 @@
 #include <errno.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "spmv_engine.h"
 
@@ -18,6 +21,18 @@
  * build-time constant rather than a queried property -- HIP exposes no XCD
  * count. */
 #define NUM_XCD 8
+/* grouped workgroup order: runs of this many consecutive workgroups per XCD,
+ * the runs dealt to the XCDs round-robin (xcd_grouped below; panels.hip
+ * carries its own, run-time group size) */
+#define XCD_GROUP 32
+#define HACK HACK_SIZE /* rows of a hack block (hll.h) */
+
+/* grid of a launch in grouped order: n workgroups padded to whole rounds of
+ * NUM_XCD runs (the kernels mask the surplus workgroups) */
+static inline unsigned grouped_grid(unsigned n) {
+    return (n + NUM_XCD * XCD_GROUP - 1) / (NUM_XCD * XCD_GROUP) * NUM_XCD *
+           XCD_GROUP;
+}
 
 /* HIP status -> negative errno (the host API's error convention) */
 static inline int hip_errno(hipError_t e) {
@@ -195,7 +210,78 @@ static inline unsigned next_launch_epoch(const unsigned *field) {
     return e;
 }
 
+/* the handle's value array (CSR or HLL) as the type V the kernels are
+ * instantiated for: `as` of an f64 handle, `as32` of an f32 handle */
+template <typename V, typename H> static inline const V *values_of(const H *h) {
+    if constexpr (std::is_same<V, float>::value)
+        return h->as32;
+    else
+        return h->as;
+}
+
 #if defined(__HIPCC__)
+/* JA / AS are read once: non-temporal, so they do not evict x from the L2 /
+ * Infinity Cache */
+template <typename T> __device__ __forceinline__ T ld_stream(const T *p) {
+    return __builtin_nontemporal_load(p);
+}
+
+/*
+ * Segmented reduction inside a wavefront: sum over groups of G consecutive
+ * lanes, result in the first lane of each group (what a __shfl_down(width G)
+ * tree gives).  Offsets 8,4,2,1 stay inside a 16-lane DPP row and run on the
+ * VALU as row_shl moves (no LDS-crossbar ds_bpermute); only the 16- and
+ * 32-lane steps use __shfl_down.  The single- and the multi-vector sub-wave
+ * kernels share this tree: the order contract of multi_kernels.hip.
+ */
+template <int CTRL> __device__ __forceinline__ double dpp_f64(double v) {
+    const long long b = __builtin_bit_cast(long long, v);
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, 0xf, 0xf, true);
+    const int hi =
+        __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xf, 0xf, true);
+    return __builtin_bit_cast(
+        double, ((long long)hi << 32) | (unsigned long long)(unsigned)lo);
+}
+
+template <int G> __device__ __forceinline__ double group_sum(double v) {
+    if (G >= 64)
+        v += __shfl_down(v, 32, 64);
+    if (G >= 32)
+        v += __shfl_down(v, 16, G >= 64 ? 64 : 32);
+    if (G >= 16)
+        v += dpp_f64<0x108>(v); /* row_shl:8 */
+    if (G >= 8)
+        v += dpp_f64<0x104>(v); /* row_shl:4 */
+    if (G >= 4)
+        v += dpp_f64<0x102>(v); /* row_shl:2 */
+    if (G >= 2)
+        v += dpp_f64<0x101>(v); /* row_shl:1 */
+    return v;
+}
+
+/* Workgroup orders (workgroups are dealt to the XCDs round-robin).
+ * XCD-contiguous: a contiguous range of the grid per XCD (bijective for any
+ * nblk): row tiles that share an x window then meet in the same L2 */
+__device__ __forceinline__ int xcd_remap(int bid, int nblk) {
+    const int nx = NUM_XCD;
+    int q = nblk / nx, r = nblk % nx;
+    int x = bid % nx, k = bid / nx;
+    return x * q + (x < r ? x : r) + k;
+}
+
+/* Grouped: workgroup bid, the kk-th of XCD xx, runs item
+ * ((kk / XCD_GROUP) * NUM_XCD + xx) * XCD_GROUP + kk % XCD_GROUP of a grid of
+ * grouped_grid() workgroups.  The kernels differ in the arithmetic they need,
+ * and their code is to stay what it is: B is the type bid is split in (name it
+ * where blockIdx.x is passed: deduction chooses unsigned), K the type kk and
+ * xx are held in, I the type the item is formed in (the run number is widened
+ * BEFORE the products) */
+template <typename B, typename K = B, typename I = K>
+__device__ __forceinline__ I xcd_grouped(B bid) {
+    const K xx = bid % NUM_XCD, kk = bid / NUM_XCD;
+    return ((I)(kk / XCD_GROUP) * NUM_XCD + xx) * XCD_GROUP + kk % XCD_GROUP;
+}
+
 /*
  * Arrival at a last-arriver counter.  The counter holds (launch epoch << 32 |
  * arrivals of that launch).  Fast path: ONE fetch-and-add that finds the

@@ -28,15 +28,6 @@
 #include <algorithm>
 #include "hip_common.h"
 
-#define HACK 32
-/* grouped order: runs of this many consecutive workgroups per XCD, the runs
- * dealt to the XCDs round-robin (see panels.hip, the blocked schedules) */
-#define HLL_GROUP 32
-
-template <typename T> __device__ __forceinline__ T ld_stream(const T *p) {
-    return __builtin_nontemporal_load(p);
-}
-
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef double v2d __attribute__((ext_vector_type(2)));
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -143,10 +134,8 @@ __global__ void k_hll_col_direct(int M, int b0, int b1, int wide, xcd_ranges xr,
         i = (int)(t % HACK);
         if (b >= xr.first[xx + 1])
             return;
-    } else if (ORDER == 2) { /* groups of HLL_GROUP workgroups per XCD */
-        const int xx = blockIdx.x % NUM_XCD, kk = blockIdx.x / NUM_XCD;
-        const long long w =
-            ((long long)(kk / HLL_GROUP) * NUM_XCD + xx) * HLL_GROUP + kk % HLL_GROUP;
+    } else if (ORDER == 2) { /* groups of XCD_GROUP workgroups per XCD */
+        const long long w = xcd_grouped<unsigned, int, long long>(blockIdx.x);
         const long long t = w * blockDim.x + threadIdx.x;
         b = b0 + (int)(t / HACK);
         i = (int)(t % HACK);
@@ -294,9 +283,8 @@ __global__ void k_hll_col_lds(int b0, int b1, int wide, xcd_ranges xr,
         bA = xr.first[xx] + 2 * (kk * waves + wave);
         if (xr.first[xx + 1] < b1)
             b1 = xr.first[xx + 1]; /* the pair stays inside the XCD's range */
-    } else if (ORDER == 2) { /* groups of HLL_GROUP workgroups per XCD */
-        const int xx = blockIdx.x % NUM_XCD, kk = blockIdx.x / NUM_XCD;
-        const int w = ((kk / HLL_GROUP) * NUM_XCD + xx) * HLL_GROUP + kk % HLL_GROUP;
+    } else if (ORDER == 2) { /* groups of XCD_GROUP workgroups per XCD */
+        const int w = xcd_grouped<unsigned, int>(blockIdx.x);
         bA = b0 + 2 * (w * waves + wave);
     } else {
         bA = b0 + 2 * ((int)blockIdx.x * waves + wave);
@@ -507,9 +495,9 @@ __global__ void __launch_bounds__(256)
 
 /* ------------------------------------------------------------------ */
 template <typename V>
-static int hll_launch_t(const spmv_hll_dev *H, const V *as, int kernel,
-                        int waves, int variant, const double *x, double *y,
-                        int b0, int b1, hipStream_t s) {
+static int hll_launch_t(const spmv_hll_dev *H, int kernel, int waves,
+                        int variant, const double *x, double *y, int b0,
+                        int b1, hipStream_t s) {
     (void)hipGetLastError(); /* an earlier caller's unread error is not ours */
     if (!H || !x || !y || b0 < 0 || b1 > H->nb || b0 > b1)
         return -EINVAL;
@@ -532,6 +520,7 @@ static int hll_launch_t(const spmv_hll_dev *H, const V *as, int kernel,
     const int threads = waves * WAVE;
     const long long lanes = (long long)(b1 - b0) * HACK;
     const int wide = H->n_wide_seg > 0 ? HLL_WIDE : 0;
+    const V *as = values_of<V>(H);
     /* XCD ranges of this launch: the handle's slot-balanced table for the
      * whole matrix, an even split for a block sub-range (multi-GPU chunks) */
     xcd_ranges xr = H->xcd_blk;
@@ -568,10 +557,9 @@ static int hll_launch_t(const spmv_hll_dev *H, const V *as, int kernel,
                                    H->off, H->ja, as, x, y);
             else if (order == 2)
                 hipLaunchKernelGGL((k_hll_col_lds<2, V>),
-                                   dim3((nwg + NUM_XCD * HLL_GROUP - 1) /
-                                        (NUM_XCD * HLL_GROUP) * NUM_XCD * HLL_GROUP),
-                                   dim3(threads), lds, s, b0, full_end, wide, xr,
-                                   H->off, H->ja, as, x, y);
+                                   dim3(grouped_grid(nwg)), dim3(threads), lds,
+                                   s, b0, full_end, wide, xr, H->off, H->ja, as,
+                                   x, y);
             else
                 hipLaunchKernelGGL((k_hll_col_lds<0, V>), dim3(nwg), dim3(threads),
                                    lds, s, b0, full_end, wide, xr, H->off, H->ja,
@@ -613,10 +601,8 @@ static int hll_launch_t(const spmv_hll_dev *H, const V *as, int kernel,
                                H->ja, as, x, y);
         else if (order == 2)
             hipLaunchKernelGGL((k_hll_col_direct<V, 8, 2>),
-                               dim3((hwgrid + NUM_XCD * HLL_GROUP - 1) /
-                                    (NUM_XCD * HLL_GROUP) * NUM_XCD * HLL_GROUP),
-                               dim3(threads), 0, s, H->M, b0, b1, wide, xr, H->off,
-                               H->ja, as, x, y);
+                               dim3(grouped_grid(hwgrid)), dim3(threads), 0, s,
+                               H->M, b0, b1, wide, xr, H->off, H->ja, as, x, y);
         else
             hipLaunchKernelGGL((k_hll_col_direct<V, 8, 0>), dim3(hwgrid),
                                dim3(threads), 0, s, H->M, b0, b1, wide, xr, H->off,
@@ -647,8 +633,6 @@ int hll_launch_kernel(const spmv_hll_dev *H, int kernel, int waves,
                       int variant, const double *x, double *y, int b0, int b1,
                       hipStream_t s) {
     if (H && H->value_bytes == 4)
-        return hll_launch_t(H, (const float *)H->as32, kernel, waves, variant,
-                            x, y, b0, b1, s);
-    return hll_launch_t(H, H ? (const double *)H->as : NULL, kernel, waves,
-                        variant, x, y, b0, b1, s);
+        return hll_launch_t<float>(H, kernel, waves, variant, x, y, b0, b1, s);
+    return hll_launch_t<double>(H, kernel, waves, variant, x, y, b0, b1, s);
 }

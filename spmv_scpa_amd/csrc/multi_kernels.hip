@@ -12,9 +12,11 @@
  * the library already has, on the same handle with x = X[:, j]:
  *   CSR  k_csr_subwave_row (kernel 2) with the same G: lane `sub` of a row's G
  *        lanes starts from the plain product of entry `sub`, adds the entries
- *        sub + G, sub + 2G, ... in order with fused multiply-adds, then the
- *        group_sum<G> tree.  The passes P are independent rows, so P is free:
- *        it falls as K grows (multi_shape) to keep P * K accumulators in registers.
+ *        sub + G, sub + 2G, ... in order with fused multiply-adds, then
+ *        group_sum<G> -- the SAME function in both kernels (hip_common.h), so
+ *        the two trees cannot drift apart.  The passes P are independent rows,
+ *        so P is free: it falls as K grows (multi_shape) to keep P * K
+ *        accumulators in registers.
  *   HLL  k_hll_col_lds / k_hll_col_direct (kernels 1 / 2, column-major): one
  *        lane per row, acc = 0.0, then acc = fma(a, x, acc) over the block's
  *        columns in order, pads included.
@@ -23,61 +25,12 @@
  * one workgroup each here: a fixed-order reduction through LDS, no state
  * between workgroups -- reproducible, within the parity bound, but not the
  * bits of the segment kernels.
- *
- * The small helpers (ld_stream, dpp_f64, group_sum, the XCD orders) repeat
- * those of csr_kernels.hip word for word: the existing translation units stay
- * untouched.
  */
 #include <algorithm>
 #include "hip_common.h"
 
-#define HACK 32
-#define MULTI_GROUP 32 /* grouped order: runs of 32 workgroups per XCD */
 #define MULTI_MAXK 8
 #define MULTI_LONG_THREADS 256
-
-template <typename T> __device__ __forceinline__ T ld_stream(const T *p) {
-    return __builtin_nontemporal_load(p);
-}
-
-template <int CTRL> __device__ __forceinline__ double dpp_f64(double v) {
-    const long long b = __builtin_bit_cast(long long, v);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, 0xf, 0xf, true);
-    const int hi =
-        __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xf, 0xf, true);
-    return __builtin_bit_cast(
-        double, ((long long)hi << 32) | (unsigned long long)(unsigned)lo);
-}
-
-/* sum over groups of G consecutive lanes, result in each group's first lane:
- * the tree of csr_kernels.hip */
-template <int G> __device__ __forceinline__ double group_sum(double v) {
-    if (G >= 64)
-        v += __shfl_down(v, 32, 64);
-    if (G >= 32)
-        v += __shfl_down(v, 16, G >= 64 ? 64 : 32);
-    if (G >= 16)
-        v += dpp_f64<0x108>(v); /* row_shl:8 */
-    if (G >= 8)
-        v += dpp_f64<0x104>(v); /* row_shl:4 */
-    if (G >= 4)
-        v += dpp_f64<0x102>(v); /* row_shl:2 */
-    if (G >= 2)
-        v += dpp_f64<0x101>(v); /* row_shl:1 */
-    return v;
-}
-
-__device__ __forceinline__ int xcd_remap(int bid, int nblk) {
-    const int nx = NUM_XCD;
-    int q = nblk / nx, r = nblk % nx;
-    int x = bid % nx, k = bid / nx;
-    return x * q + (x < r ? x : r) + k;
-}
-
-__device__ __forceinline__ long long xcd_grouped(long long bid) {
-    const long long xx = bid % NUM_XCD, kk = bid / NUM_XCD;
-    return ((kk / MULTI_GROUP) * NUM_XCD + xx) * MULTI_GROUP + kk % MULTI_GROUP;
-}
 
 /* X[c * ldx + 0 .. K): plain cached loads, the row offset formed in 64 bits.
  * Written as K 8-byte loads of consecutive doubles; the compiler merges pairs
@@ -106,9 +59,9 @@ __global__ void k_csr_multi(int M, int order, const int *__restrict__ irp,
     const int lane = threadIdx.x & (WAVE - 1);
     const int sub = lane & (G - 1);
     /* order 0: hardware, 1: XCD-contiguous equal ranges, 2: grouped (grid
-     * padded to a multiple of 8 x MULTI_GROUP; rows beyond M are masked) */
+     * padded to a multiple of NUM_XCD x XCD_GROUP; rows beyond M are masked) */
     const long long bid = order == 1 ? xcd_remap(blockIdx.x, gridDim.x)
-                          : order == 2 ? xcd_grouped(blockIdx.x)
+                          : order == 2 ? xcd_grouped<long long>(blockIdx.x)
                                        : (long long)blockIdx.x;
     const long long wave_global = (bid * blockDim.x + threadIdx.x) / WAVE;
     const long long rbase = wave_global * (P * RPP) + lane / G;
@@ -258,9 +211,9 @@ __global__ void k_hll_multi(int M, int nb, int order,
                             const V *__restrict__ as,
                             const double *__restrict__ X, int64_t ldx,
                             double *__restrict__ Y, int64_t ldy) {
-    /* order 2: groups of MULTI_GROUP workgroups per XCD; else hardware */
-    const long long wg =
-        order == 2 ? xcd_grouped(blockIdx.x) : (long long)blockIdx.x;
+    /* order 2: groups of XCD_GROUP workgroups per XCD; else hardware */
+    const long long wg = order == 2 ? xcd_grouped<long long>(blockIdx.x)
+                                    : (long long)blockIdx.x;
     const long long t = wg * blockDim.x + threadIdx.x;
     if (t / HACK >= nb)
         return;
@@ -410,17 +363,16 @@ template <int K> struct multi_shape {
 };
 
 template <typename V, int G, int K>
-static void csr_multi_gk(const spmv_csr_dev *A, const V *as, int threads,
-                         const double *X, int64_t ldx, double *Y, int64_t ldy,
-                         hipStream_t s) {
+static void csr_multi_gk(const spmv_csr_dev *A, int threads, const double *X,
+                         int64_t ldx, double *Y, int64_t ldy, hipStream_t s) {
     constexpr int P = multi_shape<K>::P;
+    const V *as = values_of<V>(A);
     const int rows_per_wave = P * (WAVE / G);
     const long long waves = ((long long)A->M + rows_per_wave - 1) / rows_per_wave;
     const long long wpb = threads / WAVE;
     unsigned grid = (unsigned)((waves + wpb - 1) / wpb);
     if (A->order == 2)
-        grid = (grid + NUM_XCD * MULTI_GROUP - 1) / (NUM_XCD * MULTI_GROUP) *
-               NUM_XCD * MULTI_GROUP;
+        grid = grouped_grid(grid);
     hipLaunchKernelGGL((k_csr_multi<G, P, K, V>), dim3(grid), dim3(threads), 0,
                        s, A->M, A->order, A->irp, A->ja, as, X, ldx, Y, ldy);
     if (A->n_long_rb > 0)
@@ -443,35 +395,35 @@ static void csr_multi_gk(const spmv_csr_dev *A, const V *as, int threads,
     }
 
 template <typename V, int G>
-static void csr_multi_g(const spmv_csr_dev *A, const V *as, int threads, int k,
+static void csr_multi_g(const spmv_csr_dev *A, int threads, int k,
                         const double *X, int64_t ldx, double *Y, int64_t ldy,
                         hipStream_t s) {
-#define CALL(KK) csr_multi_gk<V, G, KK>(A, as, threads, X, ldx, Y, ldy, s)
+#define CALL(KK) csr_multi_gk<V, G, KK>(A, threads, X, ldx, Y, ldy, s)
     MULTI_K_SWITCH(k, CALL)
 #undef CALL
 }
 
 template <typename V>
-static int csr_multi_t(const spmv_csr_dev *A, const V *as, int waves, int group,
-                       int k, const double *X, int64_t ldx, double *Y,
-                       int64_t ldy, hipStream_t s) {
+static int csr_multi_t(const spmv_csr_dev *A, int waves, int group, int k,
+                       const double *X, int64_t ldx, double *Y, int64_t ldy,
+                       hipStream_t s) {
     (void)hipGetLastError(); /* an earlier caller's unread error is not ours */
     const int threads = waves * WAVE;
     switch (pick_group(A, group)) {
     case 2:
-        csr_multi_g<V, 2>(A, as, threads, k, X, ldx, Y, ldy, s);
+        csr_multi_g<V, 2>(A, threads, k, X, ldx, Y, ldy, s);
         break;
     case 4:
-        csr_multi_g<V, 4>(A, as, threads, k, X, ldx, Y, ldy, s);
+        csr_multi_g<V, 4>(A, threads, k, X, ldx, Y, ldy, s);
         break;
     case 8:
-        csr_multi_g<V, 8>(A, as, threads, k, X, ldx, Y, ldy, s);
+        csr_multi_g<V, 8>(A, threads, k, X, ldx, Y, ldy, s);
         break;
     case 16:
-        csr_multi_g<V, 16>(A, as, threads, k, X, ldx, Y, ldy, s);
+        csr_multi_g<V, 16>(A, threads, k, X, ldx, Y, ldy, s);
         break;
     default:
-        csr_multi_g<V, 32>(A, as, threads, k, X, ldx, Y, ldy, s);
+        csr_multi_g<V, 32>(A, threads, k, X, ldx, Y, ldy, s);
         break;
     }
     return hip_errno(hipGetLastError());
@@ -486,24 +438,21 @@ int csr_launch_multi(const spmv_csr_dev *A, int waves, int group, int k,
     if (A->M == 0)
         return 0;
     if (A->value_bytes == 4)
-        return csr_multi_t(A, (const float *)A->as32, waves, group, k, X, ldx, Y,
-                           ldy, s);
-    return csr_multi_t(A, (const double *)A->as, waves, group, k, X, ldx, Y, ldy,
-                       s);
+        return csr_multi_t<float>(A, waves, group, k, X, ldx, Y, ldy, s);
+    return csr_multi_t<double>(A, waves, group, k, X, ldx, Y, ldy, s);
 }
 
 template <typename V, int K>
-static void hll_multi_k(const spmv_hll_dev *H, const V *as, int threads,
-                        const double *X, int64_t ldx, double *Y, int64_t ldy,
-                        hipStream_t s) {
+static void hll_multi_k(const spmv_hll_dev *H, int threads, const double *X,
+                        int64_t ldx, double *Y, int64_t ldy, hipStream_t s) {
     constexpr int U = multi_shape<K>::U;
+    const V *as = values_of<V>(H);
     const long long lanes = (long long)H->nb * HACK;
     unsigned grid = (unsigned)((lanes + threads - 1) / threads);
     /* the handle's order; XCD ranges (1) run in hardware order here */
     const int order = H->order == 2 ? 2 : 0;
     if (order == 2)
-        grid = (grid + NUM_XCD * MULTI_GROUP - 1) / (NUM_XCD * MULTI_GROUP) *
-               NUM_XCD * MULTI_GROUP;
+        grid = grouped_grid(grid);
     hipLaunchKernelGGL((k_hll_multi<K, U, V>), dim3(grid), dim3(threads), 0, s,
                        H->M, H->nb, order, H->off, H->ja, as, X, ldx, Y,
                        ldy);
@@ -514,12 +463,11 @@ static void hll_multi_k(const spmv_hll_dev *H, const V *as, int threads,
 }
 
 template <typename V>
-static int hll_multi_t(const spmv_hll_dev *H, const V *as, int waves, int k,
-                       const double *X, int64_t ldx, double *Y, int64_t ldy,
-                       hipStream_t s) {
+static int hll_multi_t(const spmv_hll_dev *H, int waves, int k, const double *X,
+                       int64_t ldx, double *Y, int64_t ldy, hipStream_t s) {
     (void)hipGetLastError();
     const int threads = waves * WAVE;
-#define CALL(KK) hll_multi_k<V, KK>(H, as, threads, X, ldx, Y, ldy, s)
+#define CALL(KK) hll_multi_k<V, KK>(H, threads, X, ldx, Y, ldy, s)
     MULTI_K_SWITCH(k, CALL)
 #undef CALL
     return hip_errno(hipGetLastError());
@@ -533,6 +481,6 @@ int hll_launch_multi(const spmv_hll_dev *H, int waves, int k, const double *X,
     if (H->M == 0)
         return 0;
     if (H->value_bytes == 4)
-        return hll_multi_t(H, (const float *)H->as32, waves, k, X, ldx, Y, ldy, s);
-    return hll_multi_t(H, (const double *)H->as, waves, k, X, ldx, Y, ldy, s);
+        return hll_multi_t<float>(H, waves, k, X, ldx, Y, ldy, s);
+    return hll_multi_t<double>(H, waves, k, X, ldx, Y, ldy, s);
 }
