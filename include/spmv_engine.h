@@ -30,6 +30,8 @@
  *   CSR   12*NZ + 4*(M+1) + 8*M + 8*N
  *   HLL   12*S + 12*nb + 8*M + 8*N
  *   f32 handles: 8*NZ + 4*(M+1) + 8*M + 8*N  /  8*S + 12*nb + 8*M + 8*N
+ *   compact HLL handles (spmv_hll_to_index16): (2 + value bytes)*S + 16*nb
+ *   + 8*M + 8*N
  */
 #ifndef SPMV_ENGINE_H
 #define SPMV_ENGINE_H
@@ -303,6 +305,52 @@ int spmv_hll_upload(const sparse_hll *H, int is_col_major, spmv_hll_dev **out);
 int spmv_hll_upload_f32(const sparse_hll *H, int is_col_major,
                         spmv_hll_dev **out);
 int spmv_hll_value_bytes(const spmv_hll_dev *H); /* 8 or 4 */
+/*
+ * Index type of a column-major handle (added after 0.7; spmv_version() is
+ * unchanged, callers detect the feature by the symbol).  4: JA int32[S] as
+ * above.  2: a "compact" handle -- one base column per hack block and a 16-bit
+ * offset per slot,
+ *     column of slot t of block b = base[b] + off16[t],
+ * 10 bytes per slot instead of 12 (f64 values), 6 instead of 8 (f32).  For
+ * matrices whose hack blocks (32 consecutive rows) each keep their columns in
+ * a window of 65 536: bands, 2-D stencils, 3-D stencils while
+ * 2 nx ny < 65 536.
+ *
+ * spmv_hll_to_index16 makes a new compact handle on the device with the
+ * pattern, the slot order, off[] and the value type (f64 or f32) of H; H stays
+ * valid.  base[b] is the smallest column among the non-pad slots of block b (0
+ * for a block of width 0).  A pad slot whose rewritten column lies outside
+ * [base, base + 65535] -- the column-0 pad of an empty row -- is stored as
+ * offset 0.  Errors (after the dead-handle contract below; without a GPU
+ * -ENODEV): -EINVAL row-major or already compact source; -ENODATA source
+ * after spmv_hll_release_source(); -ENOTSUP a hack block wider than 512
+ * columns (hub rows: their side launch is not built for compact handles);
+ * -ERANGE the valid columns of some block span more than 65 536.  Nothing is
+ * created on any error.
+ *
+ * Order: for finite x, y of a compact handle has the bits of
+ * spmv_hll_launch(H, 1) (and so of kernel 2) on its source, for either kernel
+ * id, every workgroup order, every waves_per_block and both value types:
+ * acc = 0.0, one fused multiply-add per column in column order, pads
+ * included.  NON-FINITE x: a pad's product is 0.0 * x[its column]; on a
+ * compact handle a non-finite x[base[b]] therefore reaches the EMPTY rows of
+ * block b (NaN instead of 0.0), where a 4-byte handle lets a non-finite x[0]
+ * reach them.
+ *
+ * On a compact handle: spmv_hll_launch / _launch_blocks / _time with kernel
+ * ids 1 and 2 (ids 0, 3 and PANELS: -EINVAL), streams and graph capture,
+ * spmv_hll_autotune (kernels 1 / 2 in the three orders; allow_panels ignored,
+ * one line in the tune log says so), _shape, _value_bytes, _algorithmic_bytes
+ * / _kernel_bytes ((2 + value_bytes) S + 4 nb for the bases + 12 nb + 8 M +
+ * 8 N), release / release_checked.  spmv_hll_build_panels*,
+ * spmv_hll_launch_multi and spmv_hll_multi_bytes: -ENOTSUP.  The handle owns
+ * no 4-byte JA and no pad bitmap.  The one-shot seam, the reference ABI names
+ * and spmv_mgpu.h create 4-byte handles only.
+ */
+int spmv_hll_to_index16(const spmv_hll_dev *H, spmv_hll_dev **out);
+int spmv_hll_index_bytes(const spmv_hll_dev *H); /* 4 or 2 */
+/* tests: base[nb], off16[slots] as stored (-EINVAL on a 4-byte handle) */
+int spmv_hll_download_index16(const spmv_hll_dev *H, int *base, uint16_t *off16);
 /* CSR -> HLL conversion on the device (reference hll.c:19-95 semantics,
  * pads already rewritten); the CSR handle stays valid.  The HLL handle has
  * the CSR handle's value type. */

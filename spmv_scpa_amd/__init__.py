@@ -572,8 +572,14 @@ _TWINS = (
      C.c_void_p, C.c_int, C.POINTER(LaunchOpts), C.c_void_p, C.c_void_p,
      C.c_int, C.c_int, C.c_size_t, _dp, C.c_void_p),
 )
-for _f in ("csr", "hll"):
-    for _n, _res, *_args in _TWINS:
+#: spmv_hll_<name> only: compact handles (16-bit column offsets)
+_HLL_ONLY = (
+    ("to_index16", C.c_int, C.c_void_p, C.POINTER(C.c_void_p)),
+    ("index_bytes", C.c_int, C.c_void_p),
+    ("download_index16", C.c_int, C.c_void_p, _ip, C.POINTER(C.c_uint16)),
+)
+for _f, _list in (("csr", _TWINS), ("hll", _TWINS + _HLL_ONLY)):
+    for _n, _res, *_args in _list:
         _sig("spmv_%s_%s" % (_f, _n), _res, *_args)
 
 def declared_symbols():
@@ -1469,10 +1475,35 @@ class HllDevice(_Device):
         _check(getattr(_lib, name)(H, int(col_major), C.byref(h)), name)
         return cls(h)
 
+    def to_index16(self):
+        """a new "compact" handle with this one's pattern and values, the
+        columns stored as one base per hack block + 16-bit offsets (10 / 6
+        instead of 12 / 8 bytes per slot); this handle stays valid.  Column-
+        major handles without wide hack blocks only; OSError(ERANGE) when the
+        columns of some block span more than 65 536.  Kernels 1 and 2 give
+        the bits of launch(1) on this handle"""
+        h = C.c_void_p()
+        self._call("to_index16", C.byref(h))
+        return HllDevice(h)
+
+    @property
+    def index_bytes(self):
+        """4 (int32 columns) or 2 (compact: base + 16-bit offsets)"""
+        return self._call("index_bytes")
+
+    def download_index16(self):
+        """-> (base int32[num_blocks], off16 uint16[slots]) of a compact
+        handle, as stored"""
+        base = np.zeros(max(self.num_blocks, 1), np.int32)
+        off16 = np.zeros(max(self.slots, 1), np.uint16)
+        self._call("download_index16", base.ctypes.data_as(_ip),
+                   off16.ctypes.data_as(C.POINTER(C.c_uint16)))
+        return base[:self.num_blocks], off16[:self.slots]
+
     def kernel_bytes(self, kernel):
         """bytes one launch of `kernel` must move: 12 per STORED slot (8 with
-        fp32 values) for the direct kernels, 12 per true entry for the blocked
-        copy (no padding)"""
+        fp32 values; 10 / 6 on a compact handle) for the direct kernels, 12
+        per true entry for the blocked copy (no padding)"""
         return _lib.spmv_hll_kernel_bytes(self.h, kernel)
 
     def launch(self, kernel, d_x, d_y, waves_per_block=0, stream=None,

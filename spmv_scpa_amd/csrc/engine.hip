@@ -1121,6 +1121,8 @@ static void teardown(spmv_hll_dev *d) {
     (void)hipFree(d->as32);
     (void)hipFree(d->off);
     (void)hipFree(d->padmask);
+    (void)hipFree(d->base16);
+    (void)hipFree(d->off16);
     (void)hipFree(d->wide_seg);
     (void)hipFree(d->wide_part);
     (void)hipFree(d->wide_cnt);
@@ -1129,9 +1131,11 @@ static void teardown(spmv_hll_dev *d) {
     free(d);
 }
 
+/* index_bytes 4: ja + padmask; 2: base16 + off16 instead (a compact handle,
+ * spmv_hll_to_index16) */
 static int hll_alloc_dev(int M, int N, int64_t NZ, int nb, int col_major,
                          int value_bytes, const int64_t *host_off,
-                         spmv_hll_dev **out) {
+                         spmv_hll_dev **out, int index_bytes = 4) {
     int rc = 0;
     spmv_hll_dev *d = (spmv_hll_dev *)calloc(1, sizeof *d);
     if (!d)
@@ -1142,6 +1146,7 @@ static int hll_alloc_dev(int M, int N, int64_t NZ, int nb, int col_major,
     d->NZ = NZ;
     d->nb = nb;
     d->value_bytes = value_bytes;
+    d->index_bytes = index_bytes;
     d->col_major = col_major ? 1 : 0;
     d->slots = host_off[nb];
     /* before tuning: grouped order for matrices of >= 2M rows (banded
@@ -1169,13 +1174,19 @@ static int hll_alloc_dev(int M, int N, int64_t NZ, int nb, int col_major,
     d->xcd_blk.first[NUM_XCD] = nb;
     HIP_TRY(hipGetDevice(&d->device));
     /* +64 slots of slack: vector loads of the last chunk stay in bounds */
-    HIP_TRY(hipMalloc((void **)&d->ja, ((size_t)d->slots + 64) * sizeof(int)));
+    if (index_bytes == 2) {
+        HIP_TRY(hipMalloc((void **)&d->off16,
+                          ((size_t)d->slots + 64) * sizeof(unsigned short)));
+        HIP_TRY(hipMalloc((void **)&d->base16, ((size_t)nb + 1) * sizeof(int)));
+    } else {
+        HIP_TRY(hipMalloc((void **)&d->ja, ((size_t)d->slots + 64) * sizeof(int)));
+    }
     if (value_bytes == 4)
         HIP_TRY(hipMalloc((void **)&d->as32, ((size_t)d->slots + 64) * sizeof(float)));
     else
         HIP_TRY(hipMalloc((void **)&d->as, ((size_t)d->slots + 64) * sizeof(double)));
     HIP_TRY(hipMalloc((void **)&d->off, ((size_t)nb + 1) * sizeof(int64_t)));
-    {
+    if (index_bytes != 2) {
         const size_t words = ((size_t)d->slots + 31) / 32 + 1;
         HIP_TRY(hipMalloc((void **)&d->padmask, words * sizeof(unsigned)));
         HIP_TRY(hipMemset(d->padmask, 0, words * sizeof(unsigned)));
@@ -1400,6 +1411,93 @@ int spmv_hll_from_csr(const spmv_csr_dev *A, int is_col_major,
     return hll_from_csr(A, (const double *)A->as, is_col_major, out);
 }
 
+/* NULL -> -EINVAL; not a live handle -> -EBADF, or -ENODEV when there is no
+ * GPU at all (no handle can be live then: the more useful answer) */
+#define HLL16_HANDLE_OK(h)                                                    \
+    do {                                                                      \
+        if (!(h))                                                             \
+            return -EINVAL;                                                   \
+        if (!live_has(h))                                                     \
+            return spmv_device_count() == 0 ? -ENODEV : -EBADF;               \
+    } while (0)
+
+int spmv_hll_index_bytes(const spmv_hll_dev *H) {
+    HLL16_HANDLE_OK(H);
+    return H->index_bytes == 2 ? 2 : 4;
+}
+
+/* a new handle with the pattern and the values of H, the columns stored as
+ * one base per hack block + 16-bit offsets (hll16_kernels.hip) */
+int spmv_hll_to_index16(const spmv_hll_dev *H, spmv_hll_dev **out) {
+    if (!H || !out)
+        return -EINVAL;
+    *out = NULL;
+    HLL16_HANDLE_OK(H);
+    if (!H->col_major || H->index_bytes == 2)
+        return -EINVAL;
+    if (!H->ja && H->slots > 0)
+        return -ENODATA; /* spmv_hll_release_source() */
+    if (H->n_wide_seg > 0)
+        return -ENOTSUP; /* hub rows: not the class this format is for */
+    int rc = 0;
+    spmv_hll_dev *d = NULL;
+    unsigned *d_over = NULL, over = 0;
+    std::vector<int64_t> off((size_t)H->nb + 1, 0);
+    if (H->nb > 0)
+        HIP_RET(hipMemcpy(off.data(), H->off,
+                          ((size_t)H->nb + 1) * sizeof(int64_t),
+                          hipMemcpyDeviceToHost));
+    rc = hll_alloc_dev(H->M, H->N, H->NZ, H->nb, 1, H->value_bytes, off.data(),
+                       &d, 2);
+    if (rc)
+        return rc;
+    d->max_width = H->max_width;
+    d->order = H->order;
+    if (H->slots > 0) {
+        if (H->value_bytes == 4)
+            HIP_TRY(hipMemcpy(d->as32, H->as32, (size_t)H->slots * sizeof(float),
+                              hipMemcpyDeviceToDevice));
+        else
+            HIP_TRY(hipMemcpy(d->as, H->as, (size_t)H->slots * sizeof(double),
+                              hipMemcpyDeviceToDevice));
+    }
+    HIP_TRY(hipMalloc((void **)&d_over, sizeof(unsigned)));
+    HIP_TRY(hipMemset(d_over, 0, sizeof(unsigned)));
+    rc = hll16_convert_dev(H, d, d_over, 0);
+    if (rc)
+        goto fail;
+    HIP_TRY(hipMemcpy(&over, d_over, sizeof(unsigned), hipMemcpyDeviceToHost));
+    if (over) {
+        rc = -ERANGE; /* some block's valid columns span more than 65 536 */
+        goto fail;
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    (void)hipFree(d_over);
+    *out = d;
+    return 0;
+fail:
+    (void)hipFree(d_over);
+    spmv_hll_release(d);
+    return rc;
+}
+
+/* tests: base[nb] and off16[slots] as stored */
+int spmv_hll_download_index16(const spmv_hll_dev *H, int *base,
+                              uint16_t *off16) {
+    HLL16_HANDLE_OK(H);
+    if (H->index_bytes != 2)
+        return -EINVAL;
+    if ((H->nb > 0 && !base) || (H->slots > 0 && !off16))
+        return -EINVAL;
+    if (H->nb > 0)
+        HIP_RET(hipMemcpy(base, H->base16, (size_t)H->nb * sizeof(int),
+                          hipMemcpyDeviceToHost));
+    if (H->slots > 0)
+        HIP_RET(hipMemcpy(off16, H->off16, (size_t)H->slots * sizeof(uint16_t),
+                          hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int spmv_hll_shape(const spmv_hll_dev *H, int *M, int *N, int64_t *NZ,
                    int *num_blocks, int64_t *slots, int *is_col_major) {
     HANDLE_OK(H);
@@ -1420,6 +1518,9 @@ int spmv_hll_shape(const spmv_hll_dev *H, int *M, int *N, int64_t *NZ,
 
 int64_t spmv_hll_algorithmic_bytes(const spmv_hll_dev *H) {
     HANDLE_OK(H);
+    if (H->index_bytes == 2) /* 2-byte offsets, and a 4-byte base per block */
+        return (2 + H->value_bytes) * H->slots + 4 * (int64_t)H->nb +
+               12 * (int64_t)H->nb + 8 * (int64_t)H->M + 8 * (int64_t)H->N;
     return (4 + H->value_bytes) * H->slots + 12 * (int64_t)H->nb +
            8 * (int64_t)H->M + 8 * (int64_t)H->N;
 }
@@ -1430,7 +1531,7 @@ int64_t spmv_hll_algorithmic_bytes(const spmv_hll_dev *H) {
  * (S = 10 NZ on a power-law one) would show the blocked kernel above 100 % */
 int64_t spmv_hll_kernel_bytes(const spmv_hll_dev *H, int kernel) {
     HANDLE_OK(H);
-    if (kernel != SPMV_HLL_KERNEL_PANELS)
+    if (kernel != SPMV_HLL_KERNEL_PANELS || H->index_bytes == 2)
         return spmv_hll_algorithmic_bytes(H);
     return (4 + H->value_bytes) * H->NZ + 12 * (int64_t)H->nb +
            8 * (int64_t)H->M + 8 * (int64_t)H->N;
@@ -1444,7 +1545,12 @@ int64_t spmv_hll_kernel_bytes(const spmv_hll_dev *H, int kernel) {
 
 /* where the two formats differ */
 static bool has_source(const spmv_csr_dev *A) { return A->ja || A->NZ == 0; }
-static bool has_source(const spmv_hll_dev *H) { return H->ja || H->slots == 0; }
+static bool has_source(const spmv_hll_dev *H) {
+    return H->ja || H->off16 || H->slots == 0;
+}
+/* compact handles (16-bit column offsets, spmv_hll_to_index16): HLL only */
+static bool is_compact(const spmv_csr_dev *) { return false; }
+static bool is_compact(const spmv_hll_dev *H) { return H->index_bytes == 2; }
 static int units(const spmv_csr_dev *A) { return A->M; }  /* launch ranges: */
 static int units(const spmv_hll_dev *H) { return H->nb; } /* rows / blocks */
 static int blocked_kernel(const spmv_csr_dev *) {
@@ -1506,7 +1612,11 @@ static int launch_direct(const spmv_hll_dev *H, int kernel,
                          double *d_y, int b0, int b1, hipStream_t s) {
     int waves = pick_waves(opts, default_waves(g_hll_waves, H->M));
     if (kernel == 1 && waves > 8)
-        waves = 8; /* 6 KiB of LDS per wavefront, stay under 64 KiB */
+        waves = 8; /* 6 KiB of LDS per wavefront, stay under 64 KiB.  Compact
+                      handles (5 / 3 KiB per wavefront) keep the clamp: 16
+                      wavefronts of fp64 values are 80 KiB all the same, and a
+                      compact launch then has the workgroup shape of its
+                      4-byte twin, whatever waves_per_block asks for */
     return hll_launch_kernel(H, kernel, waves, opts ? opts->variant : 0, d_x,
                              d_y, b0, b1, s);
 }
@@ -1584,6 +1694,8 @@ static int launch_multi(const D *d, const spmv_launch_opts *opts, int k,
     if (!live_has(d)) /* without a device no handle can be live: -ENODEV is
                          the more useful answer (as spmv_csr_to_f32) */
         return spmv_device_count() == 0 ? -ENODEV : -EBADF;
+    if (is_compact(d))
+        return -ENOTSUP; /* the multi-vector kernels read 4-byte columns */
     if (k < 1 || k > 8)
         return -EINVAL;
     if (ldx == 0)
@@ -1612,6 +1724,8 @@ static int launch_multi(const D *d, const spmv_launch_opts *opts, int k,
 /* what one launch_multi has to move at least: the matrix once, k vectors */
 template <typename D> static int64_t multi_bytes(const D *d, int k) {
     HANDLE_OK(d);
+    if (is_compact(d))
+        return -ENOTSUP;
     if (k < 1 || k > 8)
         return -EINVAL;
     return matrix_bytes(d) + 8 * (int64_t)k * d->M + 8 * (int64_t)k * d->N;
@@ -1621,6 +1735,8 @@ template <typename D> static int64_t multi_bytes(const D *d, int k) {
 template <typename D, typename Build> static int rebuild(D *d, Build build) {
     if (d->value_bytes == 4)
         return -ENOTSUP; /* the blocked copy's 12-byte entries hold fp64 values */
+    if (is_compact(d))
+        return -ENOTSUP; /* ... and is built from 4-byte columns and padmask */
     if (!has_source(d))
         return -ENODATA;
     panels_free(d->panels);
@@ -1902,6 +2018,11 @@ static int autotune(D *d, const double *d_x, double *d_y, int allow_panels,
     if (d->value_bytes == 4) {
         t.log("blocked path: not available for f32 values (direct kernels "
               "only)");
+        allow_panels = 0;
+    }
+    if (is_compact(d)) {
+        t.log("blocked path: skipped, not available for 16-bit column offsets "
+              "(direct kernels only)");
         allow_panels = 0;
     }
     if (allow_panels) {

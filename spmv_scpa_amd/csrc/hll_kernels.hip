@@ -632,6 +632,8 @@ static int hll_launch_t(const spmv_hll_dev *H, int kernel, int waves,
 int hll_launch_kernel(const spmv_hll_dev *H, int kernel, int waves,
                       int variant, const double *x, double *y, int b0, int b1,
                       hipStream_t s) {
+    if (H && H->index_bytes == 2) /* compact handle: hll16_kernels.hip */
+        return hll16_launch_kernel(H, kernel, waves, variant, x, y, b0, b1, s);
     if (H && H->value_bytes == 4)
         return hll_launch_t<float>(H, kernel, waves, variant, x, y, b0, b1, s);
     return hll_launch_t<double>(H, kernel, waves, variant, x, y, b0, b1, s);

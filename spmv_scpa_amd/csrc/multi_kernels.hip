@@ -478,6 +478,8 @@ int hll_launch_multi(const spmv_hll_dev *H, int waves, int k, const double *X,
     if (!H || !H->col_major || k < 1 || k > MULTI_MAXK || !X || !Y || ldx < k ||
         ldy < k)
         return -EINVAL;
+    if (H->index_bytes == 2)
+        return -ENOTSUP; /* compact handle: no 4-byte columns to read */
     if (H->M == 0)
         return 0;
     if (H->value_bytes == 4)

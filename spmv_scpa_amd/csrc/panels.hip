@@ -2210,6 +2210,8 @@ int panels_from_csr_opts(const spmv_csr_dev *A, const spmv_panel_opts *o,
 
 int panels_from_hll_opts(const spmv_hll_dev *H, const spmv_panel_opts *o,
                          spmv_panels **out) {
+    if (H->index_bytes == 2)
+        return -ENOTSUP; /* compact handle: neither 4-byte columns nor padmask */
     if (H->slots > 0 && !H->padmask)
         return -ENODATA;
     return panels_build(H->M, H->N, H->slots, o, H->nb, NULL, H->off,
