@@ -1427,7 +1427,7 @@ int spmv_hll_index_bytes(const spmv_hll_dev *H) {
 }
 
 /* a new handle with the pattern and the values of H, the columns stored as
- * one base per hack block + 16-bit offsets (hll16_kernels.hip) */
+ * one base per hack block + 16-bit offsets (hll_kernels.hip) */
 int spmv_hll_to_index16(const spmv_hll_dev *H, spmv_hll_dev **out) {
     if (!H || !out)
         return -EINVAL;

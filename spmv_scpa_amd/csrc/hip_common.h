@@ -1,8 +1,7 @@
 /*
  * hip_common.h -- internals shared by the HIP translation units
- * (engine.hip, csr_kernels.hip, hll_kernels.hip, hll16_kernels.hip,
- * multi_kernels.hip, panels.hip, mgpu.hip, and mat_ref.h on behalf of the
- * first and the last).
+ * (engine.hip, csr_kernels.hip, hll_kernels.hip, multi_kernels.hip,
+ * panels.hip, mgpu.hip, and mat_ref.h on behalf of the first and the last).
  * Not installed.
  */
 #ifndef SPMV_HIP_COMMON_H
@@ -200,7 +199,7 @@ struct spmv_hll_dev {
     /* index type (spmv_hll_to_index16): 4 = `ja` above; 2 = a "compact"
      * col-major handle that owns NO ja and NO padmask but one base column per
      * hack block and a 16-bit offset per slot, column of slot t of block b =
-     * base16[b] + off16[t] (hll16_kernels.hip) */
+     * base16[b] + off16[t] (hll_kernels.hip: cols16) */
     int index_bytes;
     int *base16;            /* [nb] smallest valid column of the block */
     unsigned short *off16;  /* [S] in the slot order of the source's ja */
@@ -501,12 +500,9 @@ int hll_launch_kernel(const spmv_hll_dev *H, int kernel, int waves,
                       int variant, const double *x, double *y, int b0, int b1,
                       hipStream_t s);
 int hll_fix_pads_dev(spmv_hll_dev *H, hipStream_t s);
-/* compact handles (hll16_kernels.hip): kernel ids 1 / 2 on 16-bit offsets,
- * and the conversion: dst->base16 / dst->off16 from src->ja / src->padmask,
+/* compact handles (hll_launch_kernel takes them: kernel ids 1 / 2 only), the
+ * conversion: dst->base16 / dst->off16 from src->ja / src->padmask,
  * *d_overflow |= 1 when the valid columns of a block span more than 65 536 */
-int hll16_launch_kernel(const spmv_hll_dev *H, int kernel, int waves,
-                        int variant, const double *x, double *y, int b0,
-                        int b1, hipStream_t s);
 int hll16_convert_dev(const spmv_hll_dev *src, spmv_hll_dev *dst,
                       unsigned *d_overflow, hipStream_t s);
 

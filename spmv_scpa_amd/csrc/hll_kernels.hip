@@ -22,6 +22,18 @@
  *   3 subwave_row        16 lanes per row over row-major blocks,
  *                        __shfl_down(width 16) reduction.
  *
+ * Kernels 1 and 2 are templates over the handle's INDEX type as well (cols32 /
+ * cols16 below): 4-byte columns, or on a "compact" handle one base column per
+ * hack block and a 16-bit offset per slot (spmv_hll_to_index16, DESIGN.md
+ * section 14),
+ *
+ *     column of slot t of block b = base16[b] + off16[t]
+ *
+ * 10 bytes per slot instead of 12 (fp64 values), 6 instead of 8 (fp32).  Slot
+ * order, off[], values and the order of the sums are the same for both, and
+ * so are the bits of y: acc = 0.0, one fused multiply-add per column in column
+ * order, pads included.
+ *
  * No MFMA (no dense contraction).  JA/AS stream once -> non-temporal loads;
  * x gathers are ordinary cached loads.
  */
@@ -31,6 +43,32 @@
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef double v2d __attribute__((ext_vector_type(2)));
 typedef float v4f __attribute__((ext_vector_type(4)));
+typedef unsigned short u16;
+
+/* ------------------------------------------------------------------ */
+/* index types of the col-major kernels: where the column of a slot is  */
+/* ------------------------------------------------------------------ */
+struct cols32 { /* 4-byte columns: the handle's ja */
+    typedef int slot_t;
+    typedef const int *__restrict__ arg; /* a plain pointer kernel argument */
+    static constexpr bool compact = false;
+    static constexpr bool wide_blocks = true; /* k_hll_wide may own blocks */
+    static arg of(const spmv_hll_dev *H) { return H->ja; }
+    static __device__ __forceinline__ const int *slots(const int *a) { return a; }
+    static __device__ __forceinline__ int base(const int *, int) { return 0; }
+};
+struct cols16 { /* compact handle: base16[b] + off16[t] */
+    typedef u16 slot_t;
+    struct arg {
+        const int *base16;
+        const u16 *off16;
+    };
+    static constexpr bool compact = true; /* ids 1 / 2 only, no experiment arms */
+    static constexpr bool wide_blocks = false; /* the conversion refused them */
+    static arg of(const spmv_hll_dev *H) { return arg{H->base16, H->off16}; }
+    static __device__ __forceinline__ const u16 *slots(arg a) { return a.off16; }
+    static __device__ __forceinline__ int base(arg a, int b) { return a.base16[b]; }
+};
 
 /* ------------------------------------------------------------------ */
 /* pad rewrite on the device (reference cuda_hll.cu:173-195 does it on  */
@@ -74,6 +112,68 @@ int hll_fix_pads_dev(spmv_hll_dev *H, hipStream_t s) {
 }
 
 /* ------------------------------------------------------------------ */
+/* conversion: 4-byte columns -> base + 16-bit offsets                   */
+/* ------------------------------------------------------------------ */
+/* One wavefront per hack block (at most 32 x HLL_WIDE slots: the caller has
+ * refused wide blocks).  Pass 1: min / max over the slots that were entries
+ * before the pad rewrite (bit t of padmask clear).  Pass 2: the offsets.  A
+ * pad that points outside [base, base + 65535] -- the column-0 pad of an
+ * empty row in a block whose columns start further right -- gets offset 0:
+ * its value is 0.0 and its product a zero wherever it points. */
+__global__ void __launch_bounds__(WAVE)
+    k_hll16_convert(int nb, const int64_t *__restrict__ off,
+                    const int *__restrict__ ja,
+                    const unsigned *__restrict__ padmask,
+                    int *__restrict__ base, u16 *__restrict__ off16,
+                    unsigned *overflow) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= nb)
+        return;
+    const int64_t o = off[b];
+    const int n = (int)(off[b + 1] - o);
+    int lo = 0x7fffffff, hi = -1;
+    for (int t = lane; t < n; t += WAVE) {
+        const int64_t g = o + t;
+        const int c = ja[g];
+        if (!((padmask[g >> 5] >> (g & 31)) & 1u)) {
+            lo = min(lo, c);
+            hi = max(hi, c);
+        }
+    }
+#pragma unroll
+    for (int d = WAVE / 2; d > 0; d >>= 1) {
+        lo = min(lo, __shfl_xor(lo, d, WAVE));
+        hi = max(hi, __shfl_xor(hi, d, WAVE));
+    }
+    const int bs = hi < 0 ? 0 : lo; /* no entry at all (width 0): base 0 */
+    if (lane == 0)
+        base[b] = bs;
+    if (hi >= 0 && hi - lo > 65535) {
+        if (lane == 0)
+            atomicOr(overflow, 1u);
+        return;
+    }
+    for (int t = lane; t < n; t += WAVE) {
+        const int d = ja[o + t] - bs;
+        off16[o + t] = (u16)(d < 0 || d > 65535 ? 0 : d);
+    }
+}
+
+int hll16_convert_dev(const spmv_hll_dev *src, spmv_hll_dev *dst,
+                      unsigned *d_overflow, hipStream_t s) {
+    if (!src || !dst || !d_overflow || dst->nb != src->nb ||
+        dst->slots != src->slots)
+        return -EINVAL;
+    if (src->nb == 0)
+        return 0;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_hll16_convert, dim3(src->nb), dim3(WAVE), 0, s, src->nb,
+                       src->off, src->ja, src->padmask, dst->base16, dst->off16,
+                       d_overflow);
+    return hip_errno(hipGetLastError());
+}
+
+/* ------------------------------------------------------------------ */
 /* 0: lane per row, row-major                                           */
 /* ------------------------------------------------------------------ */
 /* `wide` > 0 (kernels 0-3): the matrix has hack blocks of more than `wide`
@@ -108,6 +208,8 @@ __global__ void k_hll_row_major(int M, int b0, int b1, int wide,
 /*    Software pipelined: while the x gathers of columns [j, j+U) are    */
 /*    in flight the JA/AS loads of [j+U, j+2U) are already issued, so    */
 /*    the stream never waits behind a gather round trip.                 */
+/*    On 16-bit offsets the index is one 2-byte load per lane and column */
+/*    (64 contiguous bytes per block and column).                        */
 /* ------------------------------------------------------------------ */
 /*
  * Workgroup -> hack blocks.  REMAP: workgroups are dealt round-robin over the
@@ -119,13 +221,15 @@ __global__ void k_hll_row_major(int M, int b0, int b1, int wide,
  * DESIGN.md section 4).  The launch has 8 x (longest range) workgroups; the
  * surplus ones of shorter ranges exit.
  */
-template <typename V, int U, int ORDER, int ABL = 0> /* ABL 1: all gathers read x[0] */
+template <typename V, int U, int ORDER, int ABL = 0, /* ABL 1: all gathers read x[0] */
+          typename IX = cols32>
 __global__ void k_hll_col_direct(int M, int b0, int b1, int wide, xcd_ranges xr,
                                  const int64_t *__restrict__ off,
-                                 const int *__restrict__ ja,
+                                 typename IX::arg ix,
                                  const V *__restrict__ as,
                                  const double *__restrict__ x,
                                  double *__restrict__ y) {
+    static_assert(ABL == 0 || !IX::compact, "the ABL arm is 4-byte only");
     int b, i;
     if (ORDER == 1) {
         const int xx = blockIdx.x % NUM_XCD, kk = blockIdx.x / NUM_XCD;
@@ -151,9 +255,10 @@ __global__ void k_hll_col_direct(int M, int b0, int b1, int wide, xcd_ranges xr,
         return;
     const int64_t o = off[b];
     const int w = hack_block_width(off, b, rows);
-    if (wide > 0 && w > wide)
+    if (IX::wide_blocks && wide > 0 && w > wide)
         return;
-    const int *cj = ja + o + i;
+    const int bs = IX::base(ix, b);
+    const typename IX::slot_t *cj = IX::slots(ix) + o + i;
     const V *ca = as + o + i;
     double acc = 0.0;
     int cJ[U];
@@ -171,11 +276,11 @@ __global__ void k_hll_col_direct(int M, int b0, int b1, int wide, xcd_ranges xr,
         V av[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            xv[u] = (ABL & 1) ? x[cJ[u] & 1] : x[cJ[u]];
+            xv[u] = (ABL & 1) ? x[cJ[u] & 1] : x[bs + cJ[u]];
             av[u] = cA[u];
         }
         if (c + 1 < nfull) {
-            const int *nj = cj + (size_t)(c + 1) * U * rows;
+            const typename IX::slot_t *nj = cj + (size_t)(c + 1) * U * rows;
             const V *na = ca + (size_t)(c + 1) * U * rows;
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -189,7 +294,7 @@ __global__ void k_hll_col_direct(int M, int b0, int b1, int wide, xcd_ranges xr,
     }
     for (int j = nfull * U; j < w; ++j)
         acc += widen(ld_stream(ca + (size_t)j * rows)) *
-               x[ld_stream(cj + (size_t)j * rows)];
+               x[bs + (int)ld_stream(cj + (size_t)j * rows)];
     __builtin_nontemporal_store(acc, y + (int64_t)b * HACK + i);
 }
 
@@ -201,81 +306,110 @@ __global__ void k_hll_col_direct(int M, int b0, int b1, int wide, xcd_ranges xr,
 #define CH 8                     /* columns per staged chunk */
 #define CH_SLOTS (CH * HACK)     /* 256 slots: 1 KiB of JA, 2 KiB of AS */
 
-template <typename V> struct hll_chunk;
-template <> struct hll_chunk<double> {
-    v4i jA, jB;
+/* a chunk in registers, values and indices apart.  Values: every lane loads
+ * 16 B pieces of both blocks. */
+template <typename V> struct val_chunk;
+template <> struct val_chunk<double> {
     v2d aA0, aA1, aB0, aB1;
 };
-/* fp32 values: a chunk's 256 values are 1 KiB like its 256 indices -- one
- * 16 B/lane load per block, a lane's four values the slots of its indices */
-template <> struct hll_chunk<float> {
-    v4i jA, jB;
+/* fp32 values: a chunk's 256 values are 1 KiB -- one 16 B/lane load per block */
+template <> struct val_chunk<float> {
     v4f aA, aB;
+};
+/* 4-byte columns: 1 KiB per block, a lane's four indices of either block.
+ * 16-bit offsets: 512 B per block, so ONE 16 B/lane load fetches both blocks'
+ * -- j is the 8 offsets at slots s0 + 8 (lane & 31) of the lane's OWN block
+ * (lanes 0-31 block A, 32-63 block B) */
+template <typename IX> struct idx_chunk;
+template <> struct idx_chunk<cols32> {
+    v4i jA, jB;
+};
+template <> struct idx_chunk<cols16> {
+    v4i j;
 };
 
 /* coalesced 16 B/lane loads of slots [s0, s0+256) of the wavefront's two
- * blocks (predicated past the end of each block) */
-__device__ __forceinline__ void hll_chunk_load(hll_chunk<double> &c, int s0, int lane,
-                                               const int *gjA, const int *gjB,
-                                               const double *gaA,
-                                               const double *gaB, int nA,
-                                               int nB) {
-    const int sj = s0 + 4 * lane; /* 4 ints */
+ * blocks, predicated past the end of each block (a block's slot count is a
+ * multiple of 32, so every 16-byte piece is wholly inside or wholly outside) */
+__device__ __forceinline__ void chunk_load(val_chunk<double> &c, int s0, int lane,
+                                           const double *gaA, const double *gaB,
+                                           int nA, int nB) {
     const int sa = s0 + 2 * lane; /* 2 doubles, twice */
-    const v4i zi = {0, 0, 0, 0};
     const v2d zd = {0, 0};
-    c.jA = sj < nA ? ld_stream((const v4i *)(gjA + sj)) : zi;
-    c.jB = sj < nB ? ld_stream((const v4i *)(gjB + sj)) : zi;
     c.aA0 = sa < nA ? ld_stream((const v2d *)(gaA + sa)) : zd;
     c.aA1 = sa + 128 < nA ? ld_stream((const v2d *)(gaA + sa + 128)) : zd;
     c.aB0 = sa < nB ? ld_stream((const v2d *)(gaB + sa)) : zd;
     c.aB1 = sa + 128 < nB ? ld_stream((const v2d *)(gaB + sa + 128)) : zd;
 }
-
-__device__ __forceinline__ void hll_chunk_load(hll_chunk<float> &c, int s0, int lane,
-                                               const int *gjA, const int *gjB,
-                                               const float *gaA,
-                                               const float *gaB, int nA,
-                                               int nB) {
-    const int sj = s0 + 4 * lane; /* 4 ints, 4 floats */
-    const v4i zi = {0, 0, 0, 0};
+__device__ __forceinline__ void chunk_load(val_chunk<float> &c, int s0, int lane,
+                                           const float *gaA, const float *gaB,
+                                           int nA, int nB) {
+    const int sa = s0 + 4 * lane; /* 4 floats */
     const v4f zf = {0, 0, 0, 0};
+    c.aA = sa < nA ? ld_stream((const v4f *)(gaA + sa)) : zf;
+    c.aB = sa < nB ? ld_stream((const v4f *)(gaB + sa)) : zf;
+}
+__device__ __forceinline__ void chunk_load(idx_chunk<cols32> &c, int s0, int lane,
+                                           const int *gjA, const int *gjB, int nA,
+                                           int nB) {
+    const int sj = s0 + 4 * lane; /* 4 ints */
+    const v4i zi = {0, 0, 0, 0};
     c.jA = sj < nA ? ld_stream((const v4i *)(gjA + sj)) : zi;
     c.jB = sj < nB ? ld_stream((const v4i *)(gjB + sj)) : zi;
-    c.aA = sj < nA ? ld_stream((const v4f *)(gaA + sj)) : zf;
-    c.aB = sj < nB ? ld_stream((const v4f *)(gaB + sj)) : zf;
+}
+__device__ __forceinline__ void chunk_load(idx_chunk<cols16> &c, int s0, int lane,
+                                           const u16 *gjA, const u16 *gjB, int nA,
+                                           int nB) {
+    const int sj = s0 + 8 * (lane & 31); /* 8 offsets */
+    const v4i zi = {0, 0, 0, 0};
+    const u16 *gj = lane < HACK ? gjA : gjB;
+    c.j = sj < (lane < HACK ? nA : nB) ? ld_stream((const v4i *)(gj + sj)) : zi;
 }
 
-/* a chunk's values into the wavefront's LDS slice (two blocks x CH_SLOTS) */
-__device__ __forceinline__ void hll_chunk_store(const hll_chunk<double> &c,
-                                                double *s_as, int lane) {
+/* a chunk into the wavefront's LDS slices (two blocks x CH_SLOTS each) */
+__device__ __forceinline__ void chunk_store(const val_chunk<double> &c,
+                                            double *s_as, int lane) {
     *(v2d *)(s_as + 2 * lane) = c.aA0;
     *(v2d *)(s_as + 128 + 2 * lane) = c.aA1;
     *(v2d *)(s_as + CH_SLOTS + 2 * lane) = c.aB0;
     *(v2d *)(s_as + CH_SLOTS + 128 + 2 * lane) = c.aB1;
 }
-__device__ __forceinline__ void hll_chunk_store(const hll_chunk<float> &c,
-                                                float *s_as, int lane) {
+__device__ __forceinline__ void chunk_store(const val_chunk<float> &c,
+                                            float *s_as, int lane) {
     *(v4f *)(s_as + 4 * lane) = c.aA;
     *(v4f *)(s_as + CH_SLOTS + 4 * lane) = c.aB;
 }
+__device__ __forceinline__ void chunk_store(const idx_chunk<cols32> &c, int *s_ja,
+                                            int lane) {
+    *(v4i *)(s_ja + 4 * lane) = c.jA;
+    *(v4i *)(s_ja + CH_SLOTS + 4 * lane) = c.jB;
+}
+/* lane l's 16 bytes land at byte 16 l of the wavefront's 1 KiB: block A's 256
+ * offsets, then block B's */
+__device__ __forceinline__ void chunk_store(const idx_chunk<cols16> &c, u16 *s_ja,
+                                            int lane) {
+    *(v4i *)(s_ja + 8 * lane) = c.j;
+}
 
-template <int ORDER, typename V>
+template <int ORDER, typename V, typename IX>
 __global__ void k_hll_col_lds(int b0, int b1, int wide, xcd_ranges xr,
                               const int64_t *__restrict__ off,
-                              const int *__restrict__ ja,
+                              typename IX::arg ix,
                               const V *__restrict__ as,
                               const double *__restrict__ x,
                               double *__restrict__ y) {
-    /* per wavefront: two blocks x (256 ints + 256 values) = 6 KiB (fp64
-     * values) or 4 KiB (fp32): values of all wavefronts first, then indices */
+    /* per wavefront: two blocks x (256 values + 256 indices) = 6 KiB (fp64
+     * values) or 4 KiB (fp32) with 4-byte columns, 5 / 3 KiB with 16-bit
+     * offsets: values of all wavefronts first, then indices (every carve is a
+     * multiple of 16 bytes) */
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     const int lane = threadIdx.x & (WAVE - 1);
     const int wave = threadIdx.x / WAVE;
     const int waves = blockDim.x / WAVE;
     V *s_as = (V *)lds_raw + (size_t)wave * 2 * CH_SLOTS;
-    int *s_ja = (int *)((V *)lds_raw + (size_t)waves * 2 * CH_SLOTS) +
-                (size_t)wave * 2 * CH_SLOTS;
+    typedef typename IX::slot_t slot_t;
+    slot_t *s_ja = (slot_t *)((V *)lds_raw + (size_t)waves * 2 * CH_SLOTS) +
+                   (size_t)wave * 2 * CH_SLOTS;
 
     int bA; /* wave-uniform */
     if (ORDER == 1) {
@@ -297,28 +431,30 @@ __global__ void k_hll_col_lds(int b0, int b1, int wide, xcd_ranges xr,
      * hub block of 2^26 columns and more does not fit an int) */
     const int64_t nA64 = oB - oA, nB64 = hasB ? off[bA + 2] - oB : 0;
     /* a wide block of the pair is k_hll_wide's: nothing read, nothing stored */
-    const bool skipA = wide > 0 && (nA64 >> 5) > wide;
-    const bool skipB = wide > 0 && (nB64 >> 5) > wide;
+    const bool skipA = IX::wide_blocks && wide > 0 && (nA64 >> 5) > wide;
+    const bool skipB = IX::wide_blocks && wide > 0 && (nB64 >> 5) > wide;
     const int nA = skipA ? 0 : (int)nA64;
     const int nB = skipB ? 0 : (int)nB64;
     const int half = lane >> 5, i = lane & 31;
     const int w = (half ? nB : nA) >> 5;
     const int nmax = nA > nB ? nA : nB;
+    const int bs = half ? (hasB ? IX::base(ix, bA + 1) : 0) : IX::base(ix, bA);
 
-    const int *gjA = ja + oA, *gjB = ja + oB;
+    const slot_t *gjA = IX::slots(ix) + oA, *gjB = IX::slots(ix) + oB;
     const V *gaA = as + oA, *gaB = as + oB;
-    const int *lj = s_ja + half * CH_SLOTS + i;
+    const slot_t *lj = s_ja + half * CH_SLOTS + i;
     const V *la = s_as + half * CH_SLOTS + i;
     double acc = 0.0;
 
     /* register-staged pipeline: chunk c+1 is in flight from HBM while chunk
      * c is consumed out of LDS */
-    hll_chunk<V> cur;
-    hll_chunk_load(cur, 0, lane, gjA, gjB, gaA, gaB, nA, nB);
+    idx_chunk<IX> curj;
+    val_chunk<V> cura;
+    chunk_load(curj, 0, lane, gjA, gjB, nA, nB);
+    chunk_load(cura, 0, lane, gaA, gaB, nA, nB);
     for (int s0 = 0; s0 < nmax; s0 += CH_SLOTS) {
-        *(v4i *)(s_ja + 4 * lane) = cur.jA;
-        *(v4i *)(s_ja + CH_SLOTS + 4 * lane) = cur.jB;
-        hll_chunk_store(cur, s_as, lane);
+        chunk_store(curj, s_ja, lane);
+        chunk_store(cura, s_as, lane);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -330,15 +466,16 @@ __global__ void k_hll_col_lds(int b0, int b1, int wide, xcd_ranges xr,
         double xv[CH];
 #pragma unroll
         for (int jj = 0; jj < CH; ++jj) {
-            cc[jj] = lj[jj * HACK];
+            cc[jj] = bs + (int)lj[jj * HACK];
             av[jj] = la[jj * HACK];
         }
 #pragma unroll
         for (int jj = 0; jj < CH; ++jj)
             xv[jj] = (c0 + jj < w) ? x[cc[jj]] : 0.0;
-        if (s0 + CH_SLOTS < nmax)
-            hll_chunk_load(cur, s0 + CH_SLOTS, lane, gjA, gjB, gaA, gaB, nA,
-                           nB);
+        if (s0 + CH_SLOTS < nmax) {
+            chunk_load(curj, s0 + CH_SLOTS, lane, gjA, gjB, nA, nB);
+            chunk_load(cura, s0 + CH_SLOTS, lane, gaA, gaB, nA, nB);
+        }
 #pragma unroll
         for (int jj = 0; jj < CH; ++jj)
             if (c0 + jj < w)
@@ -494,7 +631,7 @@ __global__ void __launch_bounds__(256)
 }
 
 /* ------------------------------------------------------------------ */
-template <typename V>
+template <typename V, typename IX>
 static int hll_launch_t(const spmv_hll_dev *H, int kernel, int waves,
                         int variant, const double *x, double *y, int b0,
                         int b1, hipStream_t s) {
@@ -503,14 +640,20 @@ static int hll_launch_t(const spmv_hll_dev *H, int kernel, int waves,
         return -EINVAL;
     if ((kernel == 0 || kernel == 3) == (H->col_major != 0))
         return -EINVAL; /* layout of the handle does not fit the kernel */
-#ifndef SPMV_ABLATIONS
+    if (IX::compact && kernel != 1 && kernel != 2)
+        return -EINVAL; /* a compact handle is col-major: ids 1 and 2 only */
     /* product build: only the documented bits (spmv_engine.h: 0, 1, 2 the
      * workgroup orders; 29 belongs to the timed loops).  The ablation arms
      * (bits 4-6: pipeline depths, an arm whose result is wrong by design) are
-     * compiled only with -DSPMV_ABLATIONS (make abl) */
-    if (variant & ~(1 | 2 | 4 | SPMV_VARIANT_TIMING_BITS))
-        return -EINVAL;
+     * compiled only with -DSPMV_ABLATIONS (make abl), and for 4-byte columns
+     * only: a compact handle refuses them in either build flavour */
+#ifdef SPMV_ABLATIONS
+    constexpr bool arms = !IX::compact;
+#else
+    constexpr bool arms = false;
 #endif
+    if (!arms && (variant & ~(1 | 2 | 4 | SPMV_VARIANT_TIMING_BITS)))
+        return -EINVAL;
     if (b0 == b1)
         return 0;
     /* workgroup order: variant bit 0 hardware, bit 1 XCD ranges, bit 2
@@ -519,8 +662,9 @@ static int hll_launch_t(const spmv_hll_dev *H, int kernel, int waves,
                                                         : H->order;
     const int threads = waves * WAVE;
     const long long lanes = (long long)(b1 - b0) * HACK;
-    const int wide = H->n_wide_seg > 0 ? HLL_WIDE : 0;
+    const int wide = IX::wide_blocks && H->n_wide_seg > 0 ? HLL_WIDE : 0;
     const V *as = values_of<V>(H);
+    const typename IX::arg ix = IX::of(H);
     /* XCD ranges of this launch: the handle's slot-balanced table for the
      * whole matrix, an even split for a block sub-range (multi-GPU chunks) */
     xcd_ranges xr = H->xcd_blk;
@@ -547,66 +691,68 @@ static int hll_launch_t(const spmv_hll_dev *H, int kernel, int waves,
             full_end = b1 - 1;
         if (full_end > b0) {
             int pairs = (full_end - b0 + 1) / 2;
-            size_t lds = (size_t)waves * 2 * CH_SLOTS * (sizeof(V) + sizeof(int));
+            size_t lds = (size_t)waves * 2 * CH_SLOTS *
+                         (sizeof(V) + sizeof(typename IX::slot_t));
             const int nwg = (pairs + waves - 1) / waves;
             if (order == 1)
-                hipLaunchKernelGGL((k_hll_col_lds<1, V>),
+                hipLaunchKernelGGL((k_hll_col_lds<1, V, IX>),
                                    dim3(NUM_XCD * (((xmax + 1) / 2 + waves - 1) /
                                                    waves)),
                                    dim3(threads), lds, s, b0, full_end, wide, xr,
-                                   H->off, H->ja, as, x, y);
+                                   H->off, ix, as, x, y);
             else if (order == 2)
-                hipLaunchKernelGGL((k_hll_col_lds<2, V>),
+                hipLaunchKernelGGL((k_hll_col_lds<2, V, IX>),
                                    dim3(grouped_grid(nwg)), dim3(threads), lds,
-                                   s, b0, full_end, wide, xr, H->off, H->ja, as,
+                                   s, b0, full_end, wide, xr, H->off, ix, as,
                                    x, y);
             else
-                hipLaunchKernelGGL((k_hll_col_lds<0, V>), dim3(nwg), dim3(threads),
-                                   lds, s, b0, full_end, wide, xr, H->off, H->ja,
+                hipLaunchKernelGGL((k_hll_col_lds<0, V, IX>), dim3(nwg), dim3(threads),
+                                   lds, s, b0, full_end, wide, xr, H->off, ix,
                                    as, x, y);
         }
         if (full_end < b1)
-            hipLaunchKernelGGL((k_hll_col_direct<V, 8, 0>), dim3(1), dim3(WAVE), 0, s,
-                               H->M, full_end, b1, wide, xr, H->off, H->ja, as, x, y);
+            hipLaunchKernelGGL((k_hll_col_direct<V, 8, 0, 0, IX>), dim3(1),
+                               dim3(WAVE), 0, s, H->M, full_end, b1, wide, xr,
+                               H->off, ix, as, x, y);
         break;
     }
     case 2: {
         /* REMAP grid: 8 x (workgroups of the longest XCD range) */
         const unsigned xgrid =
             NUM_XCD * (unsigned)(((long long)xmax * HACK + threads - 1) / threads);
-#ifdef SPMV_ABLATIONS /* experiment arms: `make abl` builds them */
-        if (variant & 32) { /* tuning: 4 columns per pipeline stage */
-            hipLaunchKernelGGL((k_hll_col_direct<V, 4, 1>), dim3(xgrid),
-                               dim3(threads), 0, s, H->M, b0, b1, wide, xr, H->off,
-                               H->ja, as, x, y);
-            break;
+        if constexpr (arms) { /* experiment arms: `make abl` builds them */
+            if (variant & 32) { /* tuning: 4 columns per pipeline stage */
+                hipLaunchKernelGGL((k_hll_col_direct<V, 4, 1>), dim3(xgrid),
+                                   dim3(threads), 0, s, H->M, b0, b1, wide, xr,
+                                   H->off, ix, as, x, y);
+                break;
+            }
+            if (variant & 64) { /* tuning: 16 columns per pipeline stage */
+                hipLaunchKernelGGL((k_hll_col_direct<V, 16, 1>), dim3(xgrid),
+                                   dim3(threads), 0, s, H->M, b0, b1, wide, xr,
+                                   H->off, ix, as, x, y);
+                break;
+            }
+            if (variant & 16) { /* ABL 1: every gather reads x[0..1]: WRONG y */
+                hipLaunchKernelGGL((k_hll_col_direct<V, 8, 1, 1>), dim3(xgrid),
+                                   dim3(threads), 0, s, H->M, b0, b1, wide, xr,
+                                   H->off, ix, as, x, y);
+                break;
+            }
         }
-        if (variant & 64) { /* tuning: 16 columns per pipeline stage */
-            hipLaunchKernelGGL((k_hll_col_direct<V, 16, 1>), dim3(xgrid),
-                               dim3(threads), 0, s, H->M, b0, b1, wide, xr, H->off,
-                               H->ja, as, x, y);
-            break;
-        }
-        if (variant & 16) { /* ABL 1: every gather reads x[0..1]: WRONG y */
-            hipLaunchKernelGGL((k_hll_col_direct<V, 8, 1, 1>), dim3(xgrid),
-                               dim3(threads), 0, s, H->M, b0, b1, wide, xr, H->off,
-                               H->ja, as, x, y);
-            break;
-        }
-#endif
         const unsigned hwgrid = (unsigned)((lanes + threads - 1) / threads);
         if (order == 1)
-            hipLaunchKernelGGL((k_hll_col_direct<V, 8, 1>), dim3(xgrid),
+            hipLaunchKernelGGL((k_hll_col_direct<V, 8, 1, 0, IX>), dim3(xgrid),
                                dim3(threads), 0, s, H->M, b0, b1, wide, xr, H->off,
-                               H->ja, as, x, y);
+                               ix, as, x, y);
         else if (order == 2)
-            hipLaunchKernelGGL((k_hll_col_direct<V, 8, 2>),
+            hipLaunchKernelGGL((k_hll_col_direct<V, 8, 2, 0, IX>),
                                dim3(grouped_grid(hwgrid)), dim3(threads), 0, s,
-                               H->M, b0, b1, wide, xr, H->off, H->ja, as, x, y);
+                               H->M, b0, b1, wide, xr, H->off, ix, as, x, y);
         else
-            hipLaunchKernelGGL((k_hll_col_direct<V, 8, 0>), dim3(hwgrid),
+            hipLaunchKernelGGL((k_hll_col_direct<V, 8, 0, 0, IX>), dim3(hwgrid),
                                dim3(threads), 0, s, H->M, b0, b1, wide, xr, H->off,
-                               H->ja, as, x, y);
+                               ix, as, x, y);
         break;
     }
     case 3:
@@ -628,13 +774,23 @@ static int hll_launch_t(const spmv_hll_dev *H, int kernel, int waves,
     return hip_errno(hipGetLastError());
 }
 
-/* dispatch on the handle's value type (hip_common.h: value_bytes) */
+/* dispatch on the handle's index and value types (hip_common.h: index_bytes,
+ * value_bytes); `waves` is 1..16 (kernel 1: at most 8, engine.hip
+ * launch_direct) */
 int hll_launch_kernel(const spmv_hll_dev *H, int kernel, int waves,
                       int variant, const double *x, double *y, int b0, int b1,
                       hipStream_t s) {
-    if (H && H->index_bytes == 2) /* compact handle: hll16_kernels.hip */
-        return hll16_launch_kernel(H, kernel, waves, variant, x, y, b0, b1, s);
-    if (H && H->value_bytes == 4)
-        return hll_launch_t<float>(H, kernel, waves, variant, x, y, b0, b1, s);
-    return hll_launch_t<double>(H, kernel, waves, variant, x, y, b0, b1, s);
+    const bool f32 = H && H->value_bytes == 4;
+    if (H && H->index_bytes == 2) {
+        if (!H->off16 || !H->base16)
+            return -EINVAL;
+        return f32 ? hll_launch_t<float, cols16>(H, kernel, waves, variant, x, y,
+                                                 b0, b1, s)
+                   : hll_launch_t<double, cols16>(H, kernel, waves, variant, x,
+                                                  y, b0, b1, s);
+    }
+    return f32 ? hll_launch_t<float, cols32>(H, kernel, waves, variant, x, y, b0,
+                                             b1, s)
+               : hll_launch_t<double, cols32>(H, kernel, waves, variant, x, y,
+                                              b0, b1, s);
 }

@@ -1,5 +1,5 @@
 """Compact column-major HLL handles on the GPU: one base column per hack block
-and a 16-bit offset per slot (spmv_hll_to_index16, hll16_kernels.hip).
+and a 16-bit offset per slot (spmv_hll_to_index16, hll_kernels.hip).
 
 The expected result needs no oracle and no tolerance: for finite x a compact
 handle gives THE BITS of launch(1) on its 4-byte source handle -- either
@@ -24,7 +24,7 @@ import spmv_scpa_amd as S
 pytestmark = pytest.mark.gpu
 
 TIGHT = 1e-12  # the project's parity bound (of the row scale)
-CHUNK = 8      # columns per staged chunk of kernel 1 (CH16, hll16_kernels.hip)
+CHUNK = 8      # columns per staged chunk of kernel 1 (CH, hll_kernels.hip)
 ORDERS = (1, 2, 4)  # variant bit: hardware / XCD ranges / grouped
 
 
