@@ -62,6 +62,7 @@
 #include <time.h>
 
 #include "hip_common.h"
+#include "panel_launch.h"
 
 #define TILE_ROWS_STEPS 4096 /* "steps" schedule default: 32 KiB of LDS */
 #define SWEEP_WG_PER_CU 2
@@ -69,24 +70,13 @@
                                 perf only, see phase_wait */
 #define CNT_STRIDE 32        /* one phase counter per 128-B line */
 #define SWEEP_TAIL 16384     /* zero slots behind the entries: >= 3 chunks */
-#define BIG_LDS_BYTES (160 * 1024 - 256) /* most dynamic LDS a launch asks for */
 
-struct spmv_panels {
+/* (what the launch decision reads is the base: panel_launch.h) */
+struct spmv_panels : panel_shape {
     int N;           /* columns */
     int shift;       /* log2(columns per panel) */
-    int panels;      /* column panels */
-    int tile_rows;   /* rows per tile (multiple of 32) */
-    int tiles;       /* row tiles */
-    int sweep;       /* built for the persistent schedule */
-    int chain;       /* steps layout, launched as one chain launch */
-    int waves_hint;  /* wavefronts per workgroup when the caller passes 0
-                        (set by the autotuner; 0 = the built-in heuristic) */
-    int grid;        /* sweep: workgroups of the launch */
-    int wgs_per_cu;  /* sweep: workgroups sharing a CU's LDS */
     int reserve_cus; /* sweep: CUs left out of the grid (spmv_panel_opts) */
     int pmajor;      /* sweep: buckets stored panel-major inside a round */
-    int lds_min;     /* launch with at least this much dynamic LDS; 0: tile */
-    int64_t nnz;     /* entries kept */
     int64_t total;   /* slots of ENT/VAL in use (bucket padding included) */
     unsigned *ent;   /* [nnz] row-in-tile << shift | column-in-panel */
     double *val;     /* [nnz] */
@@ -98,11 +88,9 @@ struct spmv_panels {
                         bucket of each tile, tile-major */
     int *cpanel;     /* DEVICE [tiles*panels] panel of that bucket */
     int *nbk;        /* DEVICE [tiles] non-empty buckets per tile */
-    int max_nbk;     /* launches needed = max over tiles */
     int span;        /* steps / chain: widest run of panels a tile touches */
     int residue;     /* steps / chain: buckets listed in residue order */
     int bucket_order; /* spmv_panel_opts.bucket_order the copy was built with */
-    int det;          /* spmv_panel_opts.deterministic: ordered LDS additions */
     /* steps / chain: XCD k runs the CONTIGUOUS tile range
      * [xcd_first[k], xcd_first[k+1]) -- neighbouring tiles share their x
      * window, so they should meet in one L2 -- and the ranges hold about
@@ -112,10 +100,6 @@ struct spmv_panels {
      * of the XCDs idle while the others finish (0.62 ms; balanced: see
      * DESIGN.md) */
     int xcd_first[NUM_XCD + 1];
-    int xcd_max;     /* longest range: the launch has NUM_XCD * xcd_max groups */
-    int order;       /* steps / chain, which tile a workgroup runs
-                        (spmv_panel_opts.tile_order; the selector measures):
-                        0 grouped, 1 hardware order, 2 XCD-contiguous ranges */
     int *phase_cnt;  /* DEVICE sweep: [NUM_XCD][rounds*panels] arrival counters */
     size_t phase_cnt_bytes;
     /* LONG ROWS BESIDE THE COPY (round 4).  A row of more than PANELS_LONG_ROW
@@ -1636,6 +1620,109 @@ __global__ void __launch_bounds__(NT)
 }
 
 /* ------------------------------------------------------------------ */
+/* what the chain and the steps kernel share                             */
+/* ------------------------------------------------------------------ */
+/* Same entry layout and load discipline as the sweep kernel: blocks of 256
+ * slots per wavefront, 16-byte loads over whole lines, every vector load
+ * unconditional, the loads of chunk c+1 behind the gathers of chunk c. */
+
+/* The tile of this workgroup; false: none (beyond the tiles / this XCD's
+ * range).  tiles_hw > 0: hardware order (tile = workgroup index); < 0: groups
+ * of G = -tiles_hw >> 24 consecutive tiles per XCD, the groups dealt to the
+ * XCDs round-robin (tiles = -tiles_hw & 0xffffff): neighbouring tiles share
+ * an L2 AND the chip as a whole advances through one region; 0:
+ * XCD-contiguous tile ranges of equal work (xcd_ranges): the tiles an XCD
+ * runs at one time are neighbours, so their panels coincide or are adjacent */
+__device__ __forceinline__ bool tile_of_workgroup(int tiles_hw,
+                                                  const xcd_ranges &xr, int &t) {
+    int t_end;
+    if (tiles_hw > 0) {
+        t = (int)blockIdx.x;
+        t_end = tiles_hw;
+    } else if (tiles_hw < 0) {
+        const int G = (-tiles_hw) >> 24, k = blockIdx.x / NUM_XCD;
+        t = ((k / G) * NUM_XCD + (int)(blockIdx.x % NUM_XCD)) * G + k % G;
+        t_end = (-tiles_hw) & 0xffffff;
+    } else {
+        t = xr.first[blockIdx.x % NUM_XCD] + (int)(blockIdx.x / NUM_XCD);
+        t_end = xr.first[blockIdx.x % NUM_XCD + 1];
+    }
+    return t < t_end;
+}
+
+/* the workgroup's chunk at slot k0 of a bucket that ends at slot e (past the
+ * bucket: slack slots, masked by `live`) */
+template <int NT, int Q>
+__device__ __forceinline__ void load_chunk(sweep_chunk<Q> &c, unsigned k0,
+                                           unsigned e, const unsigned *tent,
+                                           const double *tval, int tid) {
+    const unsigned lane = tid & (WAVE - 1);
+    const unsigned wbase = (tid & ~(WAVE - 1)) * 4u;
+#pragma unroll
+    for (int g = 0; g < Q; ++g) {
+        const unsigned blk = k0 + (unsigned)g * NT * 4u + wbase;
+        c.live[g] = (int)(e - blk) - (int)lane; /* > 64u: entry u */
+        c.en[g] = __builtin_nontemporal_load(
+            (const u32x4 *)(tent + blk + lane * 4u));
+        c.va[g] = __builtin_nontemporal_load(
+            (const f64x2 *)(tval + blk + lane * 2u));
+        c.vb[g] = __builtin_nontemporal_load(
+            (const f64x2 *)(tval + blk + 128u + lane * 2u));
+    }
+}
+
+/* gather x for chunk `c` (panel window xp), start the next loads (`next`),
+ * add the products into the LDS slice -- in deterministic mode under the
+ * wavefront's turn, taken with the products in hand (det_have) */
+template <int NT, int Q, bool DET, typename Next>
+__device__ __forceinline__ void add_chunk(const sweep_chunk<Q> &c,
+                                          const double *xp, unsigned lowmask,
+                                          int shift, double *ytile,
+                                          int *det_turn, int &det_seq,
+                                          Next next) {
+    double pr[Q][4], w[Q][4];
+    unsigned rr[Q][4];
+    int on[Q];
+#pragma unroll
+    for (int g = 0; g < Q; ++g) {
+        on[g] = c.live[g];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const unsigned col = 64 * u < on[g] ? (c.en[g][u] & lowmask) : 0u;
+            pr[g][u] = xp[col];
+            rr[g][u] = c.en[g][u] >> shift;
+        }
+        w[g][0] = c.va[g][0];
+        w[g][1] = c.va[g][1];
+        w[g][2] = c.vb[g][0];
+        w[g][3] = c.vb[g][1];
+    }
+    next();
+    if (DET) {
+#pragma unroll
+        for (int g = 0; g < Q; ++g)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                pr[g][u] *= w[g][u];
+                w[g][u] = 1.0;
+                det_have(pr[g][u]);
+            }
+        det_wait(det_turn, det_seq);
+    }
+#pragma unroll
+    for (int g = 0; g < Q; ++g)
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            if (64 * u < on[g])
+                unsafeAtomicAdd(&ytile[rr[g][u]],
+                                DET ? pr[g][u] : pr[g][u] * w[g][u]);
+    if (DET) {
+        det_pass(det_turn, det_seq + 1);
+        det_seq += NT / WAVE;
+    }
+}
+
+/* ------------------------------------------------------------------ */
 /* schedule "steps": one launch per step                                 */
 /* ------------------------------------------------------------------ */
 /*
@@ -1643,10 +1730,7 @@ __global__ void __launch_bounds__(NT)
  * tile's slice of y (through LDS; a tile has one owner per launch and the
  * launches are stream-ordered).  Step 0 starts every slice from zero -- also
  * for tiles without entries -- so y needs no memset and is only re-read by
- * tiles that reach a second panel.  Same entry layout and load discipline as
- * the sweep kernel: blocks of 256 slots per wavefront, 16-byte loads over
- * whole lines, every vector load unconditional, the loads of chunk c+1 behind
- * the gathers of chunk c.
+ * tiles that reach a second panel.
  */
 template <int NT, int Q, bool DET = false>
 __global__ void __launch_bounds__(NT)
@@ -1659,32 +1743,13 @@ __global__ void __launch_bounds__(NT)
     extern __shared__ double ytile[];
     __shared__ int det_turn;
     constexpr unsigned CH = NT * Q * 4;
-    constexpr int WAVES = NT / WAVE;
     const int tid = threadIdx.x;
     int det_seq = tid / WAVE;
     if (tid == 0)
         det_turn = 0; /* published by the barrier behind the slice's load */
-    /* XCD-contiguous tile ranges of equal work (xcd_ranges): the tiles an
-     * XCD runs at one time are neighbours, so their step-th panels coincide
-     * or are adjacent */
-    /* tiles_hw > 0: hardware order (tile = workgroup index); < 0: groups of
-     * G = -tiles_hw >> 24 consecutive tiles per XCD, the groups dealt to the
-     * XCDs round-robin (tiles = -tiles_hw & 0xffffff): neighbouring tiles
-     * share an L2 AND the chip as a whole advances through one region */
-    int t, t_end;
-    if (tiles_hw > 0) {
-        t = (int)blockIdx.x;
-        t_end = tiles_hw;
-    } else if (tiles_hw < 0) {
-        const int G = (-tiles_hw) >> 24, k = blockIdx.x / NUM_XCD;
-        t = ((k / G) * NUM_XCD + (int)(blockIdx.x % NUM_XCD)) * G + k % G;
-        t_end = (-tiles_hw) & 0xffffff;
-    } else {
-        t = xr.first[blockIdx.x % NUM_XCD] + (int)(blockIdx.x / NUM_XCD);
-        t_end = xr.first[blockIdx.x % NUM_XCD + 1];
-    }
-    if (t >= t_end)
-        return; /* beyond the tiles / this XCD's range */
+    int t;
+    if (!tile_of_workgroup(tiles_hw, xr, t))
+        return;
     const int64_t row0 = (int64_t)t * tile_rows;
     if (step >= nbk[t]) {
         if (step == 0) /* a tile without entries: its rows are zero */
@@ -1696,67 +1761,14 @@ __global__ void __launch_bounds__(NT)
     const unsigned e = (unsigned)cb[((int64_t)t * panels + step) * 2 + 1];
     const double *xp = x + ((int64_t)cpanel[(int64_t)t * panels + step] << shift);
     const unsigned lowmask = (1u << shift) - 1u;
-    const unsigned lane = tid & (WAVE - 1);
-    const unsigned wbase = (tid & ~(WAVE - 1)) * 4u;
 
-    auto fill = [&](sweep_chunk<Q> &c, unsigned k0) {
-#pragma unroll
-        for (int g = 0; g < Q; ++g) {
-            const unsigned blk = k0 + (unsigned)g * NT * 4u + wbase;
-            c.live[g] = (int)(e - blk) - (int)lane; /* > 64u: entry u */
-            c.en[g] = __builtin_nontemporal_load(
-                (const u32x4 *)(tent + blk + lane * 4u));
-            c.va[g] = __builtin_nontemporal_load(
-                (const f64x2 *)(tval + blk + lane * 2u));
-            c.vb[g] = __builtin_nontemporal_load(
-                (const f64x2 *)(tval + blk + 128u + lane * 2u));
-        }
-    };
     auto consume = [&](sweep_chunk<Q> &c, sweep_chunk<Q> &f, unsigned knext) {
-        double pr[Q][4], w[Q][4];
-        unsigned rr[Q][4];
-        int on[Q];
-#pragma unroll
-        for (int g = 0; g < Q; ++g) {
-            on[g] = c.live[g];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const unsigned col = 64 * u < on[g] ? (c.en[g][u] & lowmask) : 0u;
-                pr[g][u] = xp[col];
-                rr[g][u] = c.en[g][u] >> shift;
-            }
-            w[g][0] = c.va[g][0];
-            w[g][1] = c.va[g][1];
-            w[g][2] = c.vb[g][0];
-            w[g][3] = c.vb[g][1];
-        }
-        fill(f, knext); /* past the bucket: slack slots, masked by `live` */
-        if (DET) {
-#pragma unroll
-            for (int g = 0; g < Q; ++g)
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    pr[g][u] *= w[g][u];
-                    w[g][u] = 1.0;
-                    det_have(pr[g][u]);
-                }
-            det_wait(&det_turn, det_seq);
-        }
-#pragma unroll
-        for (int g = 0; g < Q; ++g)
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (64 * u < on[g])
-                    unsafeAtomicAdd(&ytile[rr[g][u]],
-                                    DET ? pr[g][u] : pr[g][u] * w[g][u]);
-        if (DET) {
-            det_pass(&det_turn, det_seq + 1);
-            det_seq += WAVES;
-        }
+        add_chunk<NT, Q, DET>(c, xp, lowmask, shift, ytile, &det_turn, det_seq,
+                              [&] { load_chunk<NT>(f, knext, e, tent, tval, tid); });
     };
 
     sweep_chunk<Q> A, B;
-    fill(A, b);
+    load_chunk<NT>(A, b, e, tent, tval, tid);
     /* the first entries and the y slice are fetched together; the x gathers
      * follow the barrier (issued before it they delay the slice, whose loads
      * return in order behind them) */
@@ -1807,36 +1819,18 @@ __global__ void __launch_bounds__(NT)
     extern __shared__ double ytile[];
     __shared__ int det_turn;
     constexpr unsigned CH = NT * Q * 4;
-    constexpr int WAVES = NT / WAVE;
     const int tid = threadIdx.x;
     int det_seq = tid / WAVE;
     if (tid == 0)
         det_turn = 0; /* published by the barrier behind the slice's zeroing */
-    /* tiles_hw > 0: hardware order (tile = workgroup index); < 0: groups of
-     * G = -tiles_hw >> 24 consecutive tiles per XCD, the groups dealt to the
-     * XCDs round-robin (tiles = -tiles_hw & 0xffffff): neighbouring tiles
-     * share an L2 AND the chip as a whole advances through one region */
-    int t, t_end;
-    if (tiles_hw > 0) {
-        t = (int)blockIdx.x;
-        t_end = tiles_hw;
-    } else if (tiles_hw < 0) {
-        const int G = (-tiles_hw) >> 24, k = blockIdx.x / NUM_XCD;
-        t = ((k / G) * NUM_XCD + (int)(blockIdx.x % NUM_XCD)) * G + k % G;
-        t_end = (-tiles_hw) & 0xffffff;
-    } else {
-        t = xr.first[blockIdx.x % NUM_XCD] + (int)(blockIdx.x / NUM_XCD);
-        t_end = xr.first[blockIdx.x % NUM_XCD + 1];
-    }
-    if (t >= t_end)
-        return; /* beyond the tiles / this XCD's range */
+    int t;
+    if (!tile_of_workgroup(tiles_hw, xr, t))
+        return;
     const int64_t row0 = (int64_t)t * tile_rows;
     const int nb = nbk[t];
     const int64_t *tcb = cb + (int64_t)t * panels * 2;
     const int *tpan = cpanel + (int64_t)t * panels;
     const unsigned lowmask = (1u << shift) - 1u;
-    const unsigned lane = tid & (WAVE - 1);
-    const unsigned wbase = (tid & ~(WAVE - 1)) * 4u;
 
     /* position of the next chunk to load (wave-uniform) */
     int fs = 0, fpan = nb > 0 ? tpan[0] : 0;
@@ -1845,17 +1839,7 @@ __global__ void __launch_bounds__(NT)
 
     auto fill = [&](sweep_chunk<Q> &c) {
         c.p = fs < nb ? fpan : -1;
-#pragma unroll
-        for (int g = 0; g < Q; ++g) {
-            const unsigned blk = fk + (unsigned)g * NT * 4u + wbase;
-            c.live[g] = (int)(fe - blk) - (int)lane;
-            c.en[g] = __builtin_nontemporal_load(
-                (const u32x4 *)(tent + blk + lane * 4u));
-            c.va[g] = __builtin_nontemporal_load(
-                (const f64x2 *)(tval + blk + lane * 2u));
-            c.vb[g] = __builtin_nontemporal_load(
-                (const f64x2 *)(tval + blk + 128u + lane * 2u));
-        }
+        load_chunk<NT>(c, fk, fe, tent, tval, tid);
         if (fs < nb) {
             fk += CH;
             if (fk >= fe) {
@@ -1871,47 +1855,8 @@ __global__ void __launch_bounds__(NT)
         }
     };
     auto consume = [&](sweep_chunk<Q> &c, sweep_chunk<Q> &f) {
-        const double *xp = x + ((int64_t)c.p << shift);
-        double pr[Q][4], w[Q][4];
-        unsigned rr[Q][4];
-        int on[Q];
-#pragma unroll
-        for (int g = 0; g < Q; ++g) {
-            on[g] = c.live[g];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const unsigned col = 64 * u < on[g] ? (c.en[g][u] & lowmask) : 0u;
-                pr[g][u] = xp[col];
-                rr[g][u] = c.en[g][u] >> shift;
-            }
-            w[g][0] = c.va[g][0];
-            w[g][1] = c.va[g][1];
-            w[g][2] = c.vb[g][0];
-            w[g][3] = c.vb[g][1];
-        }
-        fill(f);
-        if (DET) {
-#pragma unroll
-            for (int g = 0; g < Q; ++g)
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    pr[g][u] *= w[g][u];
-                    w[g][u] = 1.0;
-                    det_have(pr[g][u]);
-                }
-            det_wait(&det_turn, det_seq);
-        }
-#pragma unroll
-        for (int g = 0; g < Q; ++g)
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (64 * u < on[g])
-                    unsafeAtomicAdd(&ytile[rr[g][u]],
-                                    DET ? pr[g][u] : pr[g][u] * w[g][u]);
-        if (DET) {
-            det_pass(&det_turn, det_seq + 1);
-            det_seq += WAVES;
-        }
+        add_chunk<NT, Q, DET>(c, x + ((int64_t)c.p << shift), lowmask, shift,
+                              ytile, &det_turn, det_seq, [&] { fill(f); });
     };
 
     sweep_chunk<Q> A, B;
@@ -1953,6 +1898,54 @@ template <auto Kernel> static int allow_big_lds(void) {
     return 0;
 }
 
+/*
+ * The tile kernels of this build, one table per family: row i is the
+ * instantiation that PANEL_*_KERNELS[i] (panel_launch.h) names, with its
+ * big-LDS opt-in.  These tables are the only place a tile kernel is
+ * instantiated; panel_launch_plan() picks the row.
+ */
+#ifdef SPMV_ABLATIONS
+constexpr bool ABLATIONS = true;
+#else
+constexpr bool ABLATIONS = false;
+#endif
+
+template <typename K> struct tile_kernel {
+    K launch;
+    int (*allow)(void);
+};
+template <auto Kernel>
+constexpr tile_kernel<decltype(Kernel)> tile_kernel_of = {
+    Kernel, &allow_big_lds<Kernel>};
+using sweep_fn = decltype(&k_tiles_sweep<256, 1>);
+using chain_fn = decltype(&k_tiles_chain<256, 1>);
+using step_fn = decltype(&k_tiles_step<256, 1>);
+
+template <int... I>
+static const tile_kernel<sweep_fn> &sweep_kernel(int row,
+                                                 std::integer_sequence<int, I...>) {
+    static const tile_kernel<sweep_fn> rows[] = {tile_kernel_of<&k_tiles_sweep<
+        PANEL_SWEEP_KERNELS[I].threads, PANEL_SWEEP_KERNELS[I].q,
+        PANEL_SWEEP_KERNELS[I].abl, PANEL_SWEEP_KERNELS[I].det != 0>>...};
+    return rows[row];
+}
+template <int... I>
+static const tile_kernel<chain_fn> &chain_kernel(int row,
+                                                 std::integer_sequence<int, I...>) {
+    static const tile_kernel<chain_fn> rows[] = {tile_kernel_of<&k_tiles_chain<
+        PANEL_CHAIN_KERNELS[I].threads, PANEL_CHAIN_KERNELS[I].q,
+        PANEL_CHAIN_KERNELS[I].det != 0>>...};
+    return rows[row];
+}
+template <int... I>
+static const tile_kernel<step_fn> &step_kernel(int row,
+                                               std::integer_sequence<int, I...>) {
+    static const tile_kernel<step_fn> rows[] = {tile_kernel_of<&k_tiles_step<
+        PANEL_STEP_KERNELS[I].threads, PANEL_STEP_KERNELS[I].q,
+        PANEL_STEP_KERNELS[I].det != 0>>...};
+    return rows[row];
+}
+
 static int panels_launch_tiles(const spmv_panels *P, int M, int waves,
                                int variant, const double *x, double *y,
                                hipStream_t s);
@@ -1971,6 +1964,8 @@ int panels_launch(const spmv_panels *P, int M, int waves, int variant,
     return hip_errno(hipGetLastError());
 }
 
+/* ask for the plan (panel_launch.h), zero the sweep's phase counters, look
+ * the kernel up, launch */
 static int panels_launch_tiles(const spmv_panels *P, int M, int waves,
                                int variant, const double *x, double *y,
                                hipStream_t s) {
@@ -1978,223 +1973,50 @@ static int panels_launch_tiles(const spmv_panels *P, int M, int waves,
         return -EINVAL;
     if (M == 0)
         return 0;
-#ifndef SPMV_ABLATIONS
-    /* product build: bit 0 flips chain <-> steps, bits 1 / 2 force a tile
-     * order (spmv_engine.h).  Everything else this function understands --
-     * lag override (4-6), no phase wait (7), the ABL arms whose result is
-     * WRONG by design (8-10), group counts (11), staggered panels (12),
-     * group sizes (14-15) -- exists only in a -DSPMV_ABLATIONS build
-     * (`make abl`; tools/sweep.py, tools/pmc.sh load that flavour) */
-    if (variant & ~(1 | 2 | 4 | SPMV_VARIANT_TIMING_BITS))
-        return -EINVAL;
-#endif
+    panel_plan pl;
+    if (int rc = panel_launch_plan(*P, waves, variant, ABLATIONS, &pl))
+        return rc;
     (void)hipGetLastError(); /* an earlier caller's unread error is not ours */
-    size_t lds = (size_t)P->tile_rows * sizeof(double);
-#ifdef SPMV_ABLATIONS
-    if (P->sweep && lds > (size_t)BIG_LDS_BYTES) /* tall-tile probe: aliased */
-        lds = 16384 * sizeof(double);
-#endif
-    if (waves <= 0)
-        waves = P->waves_hint;
-    if ((size_t)P->lds_min > lds) /* tuning: caps workgroups per CU */
-        lds = (size_t)P->lds_min;
-    if (P->sweep) {
-        /* variant (tuning): bits 4-6 lag override (1..7), bit 7 no phase
-         * wait, bits 8-10 ablations, bit 11 the other group count, bit 12
-         * staggered panel order */
-        int lag = (variant >> 4) & 7;
-        if (lag == 0) /* measured best: 6 for 1 MiB panels, 3 for 2 MiB ones,
-                         7 when there are hundreds of them (80 M columns:
-                         3.30 -> 2.98 ms) */
-            lag = P->wgs_per_cu == 1 ? 6 : P->panels >= 256 ? 7 : 3;
-        if (variant & 128)
-            lag = 0;
+    if (pl.launches == 0)
+        return 0;
+    const int row = panel_plan_row(pl, ABLATIONS);
+    const dim3 grid(pl.grid), block(pl.k.threads);
+    if (pl.family == PANEL_SWEEP) {
         HIP_RET(hipMemsetAsync(P->phase_cnt, 0, P->phase_cnt_bytes, s));
-#define SW_(NTHR, QQ, A, D)                                                    \
-    do {                                                                       \
-        if (int rc_ = allow_big_lds<&k_tiles_sweep<NTHR, QQ, A, D>>())         \
-            return rc_;                                                        \
-        hipLaunchKernelGGL((k_tiles_sweep<NTHR, QQ, A, D>), dim3(P->grid),    \
-                           dim3(NTHR), lds, s, M, P->tile_rows, P->tiles,      \
-                           P->panels, P->shift, lag, SWEEP_SPIN_MAX,           \
-                           !!(variant & 4096), P->pmajor, (unsigned)P->total,  \
-                           P->bptr, P->blen, P->ent, P->val, x, y,             \
-                           P->phase_cnt);                                      \
-    } while (0)
-#define SW(NTHR, QQ, A)                                                        \
-    do {                                                                       \
-        if (P->det && (A) == 0)                                                \
-            SW_(NTHR, QQ, 0, true);                                            \
-        else                                                                   \
-            SW_(NTHR, QQ, A, false);                                           \
-    } while (0)
-        const int two = !((variant >> 11) & 1); /* 2 groups of 4 per lane */
-#ifdef SPMV_ABLATIONS /* timing ablations (results WRONG by design for 2, 3,
-                         7): compiled only by `make abl` */
-        const int abl = (variant >> 8) & 7;
-        if (abl == 1) { SW(256, 1, 1); }
-        else if (abl == 2) { SW(256, 1, 2); }
-        else if (abl == 3) { SW(256, 1, 3); }
-        else if (abl == 4) { SW(256, 1, 4); }
-        else if (abl == 7) { SW(256, 1, 7); }
-        else if (abl == 5) { /* tall-tile probe, the production launch shapes */
-            if (waves > 8) SW(1024, 2, 8);
-            else if (waves > 0 && waves < 8) SW(256, 2, 8);
-            else SW(512, 2, 8);
-        }
-        else if (abl == 6) {
-            if (waves > 8) SW(1024, 1, 8);
-            else if (waves > 0 && waves < 8) SW(256, 1, 8);
-            else SW(512, 1, 8);
-        }
-        else
-#endif
-        if (P->wgs_per_cu == 1) {
-            /* 512 lanes x 2 groups measured best with the 160 KiB tile
-             * (1.53 ms on config 3; 1024 x 1: 1.60); bit 11 flips the groups */
-            if (waves > 8) { if (variant & 2048) SW(1024, 2, 0); else SW(1024, 1, 0); }
-            else if (waves > 0 && waves < 8) { if (variant & 2048) SW(256, 1, 0); else SW(256, 2, 0); }
-            else { if (variant & 2048) SW(512, 1, 0); else SW(512, 2, 0); }
-        }
-        else if (waves > 0 && waves < 8) { if (two) SW(256, 2, 0); else SW(256, 1, 0); }
-        else if (waves >= 8) { if (two) SW(512, 2, 0); else SW(512, 1, 0); }
-        else {
-            /* default: the chunk (threads x groups x 4 slots) that wastes
-             * few lanes on the average bucket; 512 x 2 measured best on
-             * config 3 (8000 entries per bucket) */
-            const double per_bucket =
-                (double)P->nnz / ((double)P->tiles * (double)P->panels);
-            if (per_bucket >= 6000.0) SW(512, 2, 0);
-            else if (per_bucket >= 3000.0) SW(512, 1, 0);
-            else SW(256, 1, 0);
-        }
-#undef SW
-#undef SW_
+        const auto &k = sweep_kernel(
+            row, std::make_integer_sequence<int, panel_sweep_kernels(ABLATIONS)>{});
+        if (int rc = k.allow())
+            return rc;
+        hipLaunchKernelGGL(k.launch, grid, block, pl.lds, s, M, P->tile_rows,
+                           P->tiles, P->panels, P->shift, pl.lag,
+                           SWEEP_SPIN_MAX, pl.stagger, P->pmajor,
+                           (unsigned)P->total, P->bptr, P->blen, P->ent, P->val,
+                           x, y, P->phase_cnt);
         return hip_errno(hipGetLastError());
     }
-    if (P->tiles <= 0 || P->xcd_max <= 0)
-        return 0;
     if (!P->cb || !P->cpanel || !P->nbk)
         return -EINVAL; /* not a chain / steps copy */
     xcd_ranges xr;
     memcpy(xr.first, P->xcd_first, sizeof xr.first);
-    /* Which tile a workgroup runs (workgroups are dealt to the XCDs
-     * round-robin).  0 GROUPED (default): groups of 32 consecutive tiles --
-     * one per CU of an XCD -- per XCD, the groups dealt round-robin, so
-     * neighbouring tiles share an L2 AND the eight XCDs together advance
-     * through one region of the matrix (and through rows of any density
-     * together: no XCD idles on a matrix that is denser in one half).
-     * 1 HARDWARE order: tile = workgroup index.  2 XCD-CONTIGUOUS ranges of
-     * equal work.  Measured (round 2, tile 8192 unless noted; ms):
-     *                      grouped  hardware  contiguous
-     *   banded 10M x 32     0.615     0.619     0.642
-     *   random W = 2^11     0.646     0.642     0.665
-     *   random W = 2^17     0.672     0.755     0.654
-     *   random W = 2^20     0.925     1.686     0.922   (20448 rows: 0.79 / 1.12 / 0.78)
-     *   27-point stencil    0.473     0.485     0.499
-     *   skewed rows 8.3M    0.171     0.176     0.174
-     * variant bit 1 forces hardware order, bit 2 the contiguous ranges,
-     * bits 14-15 a group size of 32 / 64 / 16 (experiments). */
-    const int gsel = (variant >> 14) & 3;
-    int ord = gsel ? 0 : (variant & 2) ? 1 : (variant & 4) ? 2 : P->order;
-    if (ord == 0 && P->tiles >= (1 << 24))
-        ord = 2; /* the packed (group, tiles) argument holds 24 bits of tiles */
-    const int G = gsel == 2 ? 64 : gsel == 3 ? 16 : 32; /* < 128: 7 bits */
-    const int order_arg = ord == 0 ? -((G << 24) | P->tiles)
-                          : ord == 1 ? P->tiles : 0;
-    const unsigned order_grid =
-        ord == 0 ? (unsigned)((P->tiles + NUM_XCD * G - 1) / (NUM_XCD * G)) *
-                       NUM_XCD * G
-        : ord == 1 ? (unsigned)P->tiles : (unsigned)(NUM_XCD * P->xcd_max);
-    if (P->chain != !!(variant & 1)) { /* variant bit 0 flips the stored mode */
-        const double per_bucket_c =
-            (double)P->nnz / ((double)P->tiles *
-                              (double)(P->max_nbk > 0 ? P->max_nbk : 1));
-#define CHN_(NTHR, QQ, D)                                                      \
-    do {                                                                       \
-        if (int rc_ = allow_big_lds<&k_tiles_chain<NTHR, QQ, D>>())            \
-            return rc_;                                                        \
-        hipLaunchKernelGGL((k_tiles_chain<NTHR, QQ, D>),                      \
-                           dim3(order_grid),                                   \
-                           dim3(NTHR), lds, s, M, P->tile_rows, P->panels,     \
-                           P->shift, (unsigned)P->total, order_arg,            \
-                           xr, P->cb, P->cpanel, P->nbk, P->ent, P->val, x,    \
-                           y);                                                 \
-    } while (0)
-/* deterministic: several groups of 4 entries per lane and turn -- the
- * hand-offs of the turn counter are what the mode costs, and they go with
- * the number of turns -- at most 512 lanes.  Four groups when the tile fills
- * a CU's LDS by itself (one workgroup per CU: W = 2^20, 19552-row tiles,
- * 0.797 ms vs 0.900 with two groups and 0.728 in the default mode), two when
- * two or more workgroups share the CU and hide each other's hand-offs (four
- * groups cost them occupancy: 8192-row tiles at W = 2^17 0.690 vs 0.836 ms;
- * default mode 0.604).  profiles/r05_det_cost.md */
-#define CHN(NTHR, QQ)                                                          \
-    do {                                                                       \
-        if (P->det && (size_t)P->tile_rows * sizeof(double) > 80 * 1024) {     \
-            if ((NTHR) <= 256)                                                 \
-                CHN_(256, 4, true);                                            \
-            else                                                               \
-                CHN_(512, 4, true);                                            \
-        } else if (P->det) {                                                   \
-            if ((NTHR) <= 256)                                                 \
-                CHN_(256, 2, true);                                            \
-            else                                                               \
-                CHN_(512, 2, true);                                            \
-        } else                                                                 \
-            CHN_(NTHR, QQ, false);                                             \
-    } while (0)
-        if (variant & 2048) { /* tuning: two groups of 4 per lane */
-            if (waves > 0 && waves < 8) CHN(256, 2);
-            else CHN(512, 2);
-        }
-        else if (waves > 0 && waves < 8) CHN(256, 1);
-        else if (waves > 8) CHN(1024, 1);
-        else if (waves == 8 || per_bucket_c >= 3000.0) CHN(512, 1);
-        else CHN(256, 1);
-#undef CHN
-#undef CHN_
+    if (pl.family == PANEL_CHAIN) {
+        const auto &k = chain_kernel(
+            row, std::make_integer_sequence<int, PANEL_CHAIN_PRODUCT>{});
+        if (int rc = k.allow())
+            return rc;
+        hipLaunchKernelGGL(k.launch, grid, block, pl.lds, s, M, P->tile_rows,
+                           P->panels, P->shift, (unsigned)P->total,
+                           pl.order_arg, xr, P->cb, P->cpanel, P->nbk, P->ent,
+                           P->val, x, y);
         return hip_errno(hipGetLastError());
     }
-    /* launch `step` handles the step-th NON-EMPTY bucket of every tile: a
-     * matrix whose rows reach over k panels needs k launches, all tiles busy
-     * in each of them; step 0 also zeroes the rows of empty tiles */
-    const int steps = P->max_nbk > 0 ? P->max_nbk : 1;
-    const double per_bucket =
-        (double)P->nnz / ((double)P->tiles * (double)steps);
-    for (int p = 0; p < steps; ++p) {
-#define ST_(NTHR, QQ, D)                                                       \
-    do {                                                                       \
-        if (int rc_ = allow_big_lds<&k_tiles_step<NTHR, QQ, D>>())             \
-            return rc_;                                                        \
-        hipLaunchKernelGGL((k_tiles_step<NTHR, QQ, D>),                       \
-                           dim3(order_grid),                                   \
-                           dim3(NTHR), lds, s, M, P->tile_rows, P->panels,     \
-                           P->shift, p, order_arg, xr, P->cb,                  \
-                           P->cpanel, P->nbk, P->ent, P->val, x, y);           \
-    } while (0)
-#define ST(NTHR, QQ)                                                           \
-    do {                                                                       \
-        if (P->det) {                                                          \
-            if ((NTHR) <= 256)                                                 \
-                ST_(256, 2, true);                                             \
-            else                                                               \
-                ST_(512, 2, true);                                             \
-        } else                                                                 \
-            ST_(NTHR, QQ, false);                                              \
-    } while (0)
-        if (variant & 2048) { /* tuning: two groups of 4 per lane */
-            if (waves > 0 && waves < 8) ST(256, 2);
-            else ST(512, 2);
-        }
-        else if (waves > 0 && waves < 8) ST(256, 1);
-        else if (waves > 8) ST(1024, 1);
-        else if (waves == 8) ST(512, 1);
-        else if (per_bucket >= 3000.0) ST(512, 1);
-        else ST(256, 1);
-#undef ST
-#undef ST_
-    }
+    const auto &k =
+        step_kernel(row, std::make_integer_sequence<int, PANEL_STEP_PRODUCT>{});
+    if (int rc = k.allow())
+        return rc;
+    for (int p = 0; p < pl.launches; ++p)
+        hipLaunchKernelGGL(k.launch, grid, block, pl.lds, s, M, P->tile_rows,
+                           P->panels, P->shift, p, pl.order_arg, xr, P->cb,
+                           P->cpanel, P->nbk, P->ent, P->val, x, y);
     return hip_errno(hipGetLastError());
 }
 

@@ -543,6 +543,40 @@ def test_steps_schedule_tile_heights(tile_rows, default_panel_schedule,
     S.csr_free(A)
 
 
+@pytest.mark.parametrize("sched,tile_rows", [("chain", 8192), ("chain", 16384),
+                                             ("steps", 4096)])
+def test_deterministic_chain_and_steps_at_every_launch_shape(sched, tile_rows):
+    """The ordered mode of the chain / steps kernels at explicit
+    waves_per_block, not only the default: 256 and 512 threads, two groups per
+    lane and -- chain tiles above 80 KiB of LDS -- four.  Each launch shape
+    agrees with the oracle and gives the same bits on 20 further launches."""
+    M, N, K, W = 50_000, 60_000, 16, 20_000
+    IRP, JA, AS = O.synth_csr(S.SYNTH_KKT, M, N, K, W, 42)
+    x = O.synth_x(7, 0, N)
+    y_ref = O.csr_spmv(IRP, JA, AS, x)
+    scale = O.csr_abs_spmv(IRP, JA, AS, x)
+    A = S.csr_from_arrays("det tiles", M, N, IRP, JA, AS)
+    d_x, d_y = S.DevBuffer.from_numpy(x), S.DevBuffer(M * 8)
+    dA = S.CsrDevice.upload(A)
+    dA.build_panels(8192, sched, tile_rows, deterministic=True)
+    assert dA.panels_schedule() == sched and dA.panels_tile_rows() == tile_rows
+    assert "deterministic" in dA.panels_describe()
+    for waves in (4, 8, 16):
+        S._lib.spmv_dev_memset(d_y.ptr, 0xFF, M * 8, None)
+        dA.launch(S.CSR_KERNEL_PANELS, d_x.ptr, d_y.ptr, waves_per_block=waves)
+        S.stream_sync()
+        y0 = d_y.to_numpy(np.float64, M)
+        assert_parity(y0, y_ref, scale, ("det", sched, tile_rows, waves))
+        for it in range(20):
+            dA.launch(S.CSR_KERNEL_PANELS, d_x.ptr, d_y.ptr,
+                      waves_per_block=waves)
+            S.stream_sync()
+            assert np.array_equal(d_y.to_numpy(np.float64, M).view(np.uint64),
+                                  y0.view(np.uint64)), (sched, waves, it)
+    dA.release()
+    S.csr_free(A)
+
+
 @pytest.mark.parametrize("sched", ["chain", "steps"])
 def test_residue_bucket_order_on_a_band(sched, default_panel_schedule,
                                         monkeypatch):

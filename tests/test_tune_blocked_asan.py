@@ -53,3 +53,31 @@ def test_stream_table_invariants_under_asan(tmp_path):
     sys.stdout.write(r.stdout)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "every entry covered once" in r.stdout and "ERROR" not in r.stderr
+
+
+def test_panel_launch_plans_under_asan(tmp_path):
+    """the launch shape of the blocked path's tile kernels (panel_launch.h:
+    family, instantiation, lag, LDS, grid, tile order per (copy, waves,
+    variant) in both build flavours): a table of plans written out from the
+    macro ladders the function replaced, the product flavour's refusals, and
+    invariants over 4000 seeded random inputs"""
+    exe = str(tmp_path / "panel_launch_asan")
+    # the constants the library is compiled with (hip_common.h)
+    import re
+    hdr = open(os.path.join(ROOT, "spmv_scpa_amd", "csrc", "hip_common.h")).read()
+    defs = []
+    for name in ("NUM_XCD", "SPMV_VARIANT_TIMING_BITS"):
+        m = re.search(r"#define\s+%s\s+(\d+|\([^)]*\))" % name, hdr)
+        assert m, name
+        defs.append("-D%s=%s" % (name, m.group(1)))
+    subprocess.run(
+        ["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined",
+         "-fno-omit-frame-pointer", "-fno-sanitize-recover=all"] + defs +
+        ["-I", os.path.join(ROOT, "spmv_scpa_amd", "csrc"),
+         os.path.join(ROOT, "tests", "asan", "panel_launch_asan.cc"),
+         "-o", exe], check=True)
+    r = subprocess.run([exe, "4000"], capture_output=True, text=True)
+    sys.stdout.write(r.stdout)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "every plan names an instantiated kernel" in r.stdout
+    assert "FAILED" not in r.stdout and "ERROR" not in r.stderr
