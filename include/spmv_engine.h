@@ -343,7 +343,8 @@ int spmv_hll_value_bytes(const spmv_hll_dev *H); /* 8 or 4 */
  * one line in the tune log says so), _shape, _value_bytes, _algorithmic_bytes
  * / _kernel_bytes ((2 + value_bytes) S + 4 nb for the bases + 12 nb + 8 M +
  * 8 N), release / release_checked.  spmv_hll_build_panels*,
- * spmv_hll_launch_multi and spmv_hll_multi_bytes: -ENOTSUP.  The handle owns
+ * spmv_hll_launch_multi, spmv_hll_multi_bytes, spmv_hll_launch_axpby and
+ * spmv_hll_axpby_bytes: -ENOTSUP.  The handle owns
  * no 4-byte JA and no pad bitmap.  The one-shot seam, the reference ABI names
  * and spmv_mgpu.h create 4-byte handles only.
  */
@@ -456,6 +457,49 @@ int spmv_hll_launch_multi(const spmv_hll_dev *H, const spmv_launch_opts *opts,
  * -EINVAL for k outside 1..8 */
 int64_t spmv_csr_multi_bytes(const spmv_csr_dev *A, int k);
 int64_t spmv_hll_multi_bytes(const spmv_hll_dev *H, int k);
+
+/*
+ * Y = alpha * A X + beta * Y in place, for the same 1..8 interleaved vectors
+ * (added after 0.7; spmv_version() is unchanged, detect it by the symbol):
+ *
+ * Y[r*ldy + j] = alpha * (sum_c A[r][c] * X[c*ldx + j]) + beta * Y[r*ldy + j].
+ *
+ * Layout, strides (0 = k), opts, the handle checks and every error code are
+ * those of spmv_*_launch_multi above -- one function checks both (a compact
+ * handle: -ENOTSUP; a row-major HLL handle: -EINVAL; after
+ * spmv_*_release_source(): -ENODATA; not a live handle: -EBADF / -ENODEV;
+ * M == 0: returns 0 and launches nothing).  The kernels are launch_multi's
+ * with an epilogue where the store is, in the lane or workgroup that owns the
+ * element: one pass over the matrix, no second pass over Y.  alpha and beta
+ * are passed by value and any double is accepted; a captured graph holds the
+ * values it was captured with.
+ *
+ * Result contract, to the bit.  Let s be what spmv_*_launch_multi stores for
+ * the element on the same handle with the same opts (every row: the sums of
+ * long rows and wide hack blocks are fixed-order too), rn() one rounding to
+ * fp64:
+ *   beta == 0:  Y = rn(alpha * s).  The old Y is NOT read: a NaN or inf in it
+ *               does not propagate and the memory may be uninitialised.
+ *   beta != 0:  Y = rn(rn(alpha * s) + rn(beta * y_old)): two products and
+ *               one sum, each rounded once, no fused multiply-add across them.
+ * So alpha = 1, beta = 0 gives the bits of launch_multi, and alpha = -1,
+ * beta = 1 gives y_old - s correctly rounded.  There is no special case for
+ * alpha == 0: the matrix is still read and 0 * NaN is NaN.  Only columns
+ * 0..k-1 of rows 0..M-1 of Y are read or written.  X and Y must not overlap.
+ */
+int spmv_csr_launch_axpby(const spmv_csr_dev *A, const spmv_launch_opts *opts,
+                          int k, double alpha, double beta,
+                          const double *d_X, int64_t ldx,
+                          double *d_Y, int64_t ldy, void *stream);
+int spmv_hll_launch_axpby(const spmv_hll_dev *H, const spmv_launch_opts *opts,
+                          int k, double alpha, double beta,
+                          const double *d_X, int64_t ldx,
+                          double *d_Y, int64_t ldy, void *stream);
+/* bytes one launch_axpby must move: spmv_*_multi_bytes(k), and 8*k*M more
+ * when reads_y != 0 (beta != 0: Y is read as well as written); -EINVAL and
+ * -ENOTSUP where multi_bytes answers so */
+int64_t spmv_csr_axpby_bytes(const spmv_csr_dev *A, int k, int reads_y);
+int64_t spmv_hll_axpby_bytes(const spmv_hll_dev *H, int k, int reads_y);
 
 /*
  * Pick the fastest kernel for this matrix by measurement (5 launches each):

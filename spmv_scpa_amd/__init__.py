@@ -568,6 +568,10 @@ _TWINS = (
      C.c_void_p, C.POINTER(LaunchOpts), C.c_int, C.c_void_p, C.c_int64,
      C.c_void_p, C.c_int64, C.c_void_p),
     ("multi_bytes", C.c_int64, C.c_void_p, C.c_int),
+    ("launch_axpby", C.c_int,
+     C.c_void_p, C.POINTER(LaunchOpts), C.c_int, C.c_double, C.c_double,
+     C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p),
+    ("axpby_bytes", C.c_int64, C.c_void_p, C.c_int, C.c_int),
     ("time", C.c_int,
      C.c_void_p, C.c_int, C.POINTER(LaunchOpts), C.c_void_p, C.c_void_p,
      C.c_int, C.c_int, C.c_size_t, _dp, C.c_void_p),
@@ -1296,6 +1300,33 @@ class _Device:
         read and k written"""
         return _check(self._fn("multi_bytes")(self.h, int(k)),
                       "spmv_%s_multi_bytes" % self._FMT)
+
+    def launch_axpby(self, alpha, beta, d_X, d_Y, k=1, ldx=0, ldy=0,
+                     waves_per_block=0, group=0, stream=None):
+        """Y = alpha * A X + beta * Y in place, layout and launch shape as
+        launch_multi (k = 1..8 interleaved vectors, ldx, ldy >= k or 0).  With
+        s what launch_multi stores: beta == 0 gives rn(alpha*s) and never
+        reads Y (NaN, inf or uninitialised memory in it do not matter), else
+        rn(rn(alpha*s) + rn(beta*y_old)) -- each operation rounded once, as
+        the numpy expression alpha*S + beta*Y does.  alpha == 0 still reads
+        the matrix (0 * NaN is NaN).  X and Y must not overlap.  A captured
+        graph keeps the alpha and beta it was captured with."""
+        k, ldx, ldy = int(k), int(ldx), int(ldy)
+        if not 1 <= k <= 8:
+            raise ValueError("k=%r: 1..8 vectors per launch" % (k,))
+        if (ldx and ldx < k) or (ldy and ldy < k):
+            raise ValueError("ldx=%d, ldy=%d: at least k=%d (or 0)"
+                             % (ldx, ldy, k))
+        o = _opts(waves_per_block, group if self._FMT == "csr" else 0)
+        self._call("launch_axpby", C.byref(o), k, float(alpha), float(beta),
+                   d_X, ldx, d_Y, ldy, stream)
+
+    def axpby_bytes(self, k, beta):
+        """bytes one launch_axpby(k) must move: multi_bytes(k), and Y once
+        more (8*k*M) when beta != 0"""
+        return _check(self._fn("axpby_bytes")(self.h, int(k),
+                                              int(float(beta) != 0.0)),
+                      "spmv_%s_axpby_bytes" % self._FMT)
 
     def build_panels(self, panel_cols=0, sched=None, tile_rows=0,
                      sweep_wgs_per_cu=0, reserve_cus=0, lds_min=0,

@@ -1678,6 +1678,19 @@ static int multi_direct(const spmv_hll_dev *H, const spmv_launch_opts *opts,
     return hll_launch_multi(H, pick_waves(opts, default_waves(g_hll_waves, H->M)),
                             k, X, ldx, Y, ldy, s);
 }
+static int axpby_direct(const spmv_csr_dev *A, const spmv_launch_opts *opts,
+                        int k, double alpha, double beta, const double *X,
+                        int64_t ldx, double *Y, int64_t ldy, hipStream_t s) {
+    return csr_launch_axpby(A, pick_waves(opts, default_waves(g_csr_waves, A->M)),
+                            opts ? opts->group : 0, k, alpha, beta, X, ldx, Y,
+                            ldy, s);
+}
+static int axpby_direct(const spmv_hll_dev *H, const spmv_launch_opts *opts,
+                        int k, double alpha, double beta, const double *X,
+                        int64_t ldx, double *Y, int64_t ldy, hipStream_t s) {
+    return hll_launch_axpby(H, pick_waves(opts, default_waves(g_hll_waves, H->M)),
+                            k, alpha, beta, X, ldx, Y, ldy, s);
+}
 static int64_t matrix_bytes(const spmv_csr_dev *A) {
     return (4 + A->value_bytes) * A->NZ + 4 * ((int64_t)A->M + 1);
 }
@@ -1685,10 +1698,12 @@ static int64_t matrix_bytes(const spmv_hll_dev *H) {
     return (4 + H->value_bytes) * H->slots + 12 * (int64_t)H->nb;
 }
 
+/* the checks of launch_multi and launch_axpby, one copy: 0 = launch (ldx, ldy
+ * resolved), 1 = nothing to do (M == 0), negative = the refusal */
 template <typename D>
-static int launch_multi(const D *d, const spmv_launch_opts *opts, int k,
-                        const double *d_X, int64_t ldx, double *d_Y,
-                        int64_t ldy, void *stream) {
+static int multi_check(const D *d, const spmv_launch_opts *opts, int k,
+                       const double *d_X, int64_t *ldx, double *d_Y,
+                       int64_t *ldy) {
     if (!d)
         return -EINVAL;
     if (!live_has(d)) /* without a device no handle can be live: -ENODEV is
@@ -1698,11 +1713,11 @@ static int launch_multi(const D *d, const spmv_launch_opts *opts, int k,
         return -ENOTSUP; /* the multi-vector kernels read 4-byte columns */
     if (k < 1 || k > 8)
         return -EINVAL;
-    if (ldx == 0)
-        ldx = k;
-    if (ldy == 0)
-        ldy = k;
-    if (ldx < k || ldy < k || !d_X || !d_Y)
+    if (*ldx == 0)
+        *ldx = k;
+    if (*ldy == 0)
+        *ldy = k;
+    if (*ldx < k || *ldy < k || !d_X || !d_Y)
         return -EINVAL;
     if (opts) {
         if (opts->waves_per_block < 0 || opts->waves_per_block > 16 ||
@@ -1716,9 +1731,30 @@ static int launch_multi(const D *d, const spmv_launch_opts *opts, int k,
         return -EINVAL;
     if (!has_source(d))
         return -ENODATA; /* spmv_*_release_source() */
-    if (d->M == 0)
-        return 0;
+    return d->M == 0 ? 1 : 0;
+}
+
+template <typename D>
+static int launch_multi(const D *d, const spmv_launch_opts *opts, int k,
+                        const double *d_X, int64_t ldx, double *d_Y,
+                        int64_t ldy, void *stream) {
+    const int rc = multi_check(d, opts, k, d_X, &ldx, d_Y, &ldy);
+    if (rc)
+        return rc < 0 ? rc : 0;
     return multi_direct(d, opts, k, d_X, ldx, d_Y, ldy, (hipStream_t)stream);
+}
+
+/* Y = alpha A X + beta Y in place: launch_multi's checks, launch shape and
+ * kernels, with the epilogue at the store */
+template <typename D>
+static int launch_axpby(const D *d, const spmv_launch_opts *opts, int k,
+                        double alpha, double beta, const double *d_X,
+                        int64_t ldx, double *d_Y, int64_t ldy, void *stream) {
+    const int rc = multi_check(d, opts, k, d_X, &ldx, d_Y, &ldy);
+    if (rc)
+        return rc < 0 ? rc : 0;
+    return axpby_direct(d, opts, k, alpha, beta, d_X, ldx, d_Y, ldy,
+                        (hipStream_t)stream);
 }
 
 /* what one launch_multi has to move at least: the matrix once, k vectors */
@@ -1729,6 +1765,13 @@ template <typename D> static int64_t multi_bytes(const D *d, int k) {
     if (k < 1 || k > 8)
         return -EINVAL;
     return matrix_bytes(d) + 8 * (int64_t)k * d->M + 8 * (int64_t)k * d->N;
+}
+
+/* ... and one launch_axpby: the same, and Y once more when it is read */
+template <typename D>
+static int64_t axpby_bytes(const D *d, int k, int reads_y) {
+    const int64_t b = multi_bytes(d, k);
+    return b < 0 || !reads_y ? b : b + 8 * (int64_t)k * d->M;
 }
 
 /* a new blocked copy in place of the old one: `build(&d->panels)` */
@@ -2281,6 +2324,16 @@ static int copy_tune_log(const D *d, char *buf, size_t len) {
     }                                                                          \
     int64_t spmv_##fmt##_multi_bytes(const D *d, int k) {                      \
         return multi_bytes(d, k);                                              \
+    }                                                                          \
+    int spmv_##fmt##_launch_axpby(const D *d, const spmv_launch_opts *opts,    \
+                                  int k, double alpha, double beta,            \
+                                  const double *d_X, int64_t ldx,              \
+                                  double *d_Y, int64_t ldy, void *stream) {    \
+        return launch_axpby(d, opts, k, alpha, beta, d_X, ldx, d_Y, ldy,       \
+                            stream);                                           \
+    }                                                                          \
+    int64_t spmv_##fmt##_axpby_bytes(const D *d, int k, int reads_y) {         \
+        return axpby_bytes(d, k, reads_y);                                     \
     }                                                                          \
     int spmv_##fmt##_time(const D *d, int kernel,                              \
                           const spmv_launch_opts *opts, const double *d_x,     \

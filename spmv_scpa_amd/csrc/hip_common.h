@@ -491,6 +491,14 @@ int csr_launch_multi(const spmv_csr_dev *A, int waves, int group, int k,
                      hipStream_t s);
 int hll_launch_multi(const spmv_hll_dev *H, int waves, int k, const double *X,
                      int64_t ldx, double *Y, int64_t ldy, hipStream_t s);
+/* ... and Y = alpha A X + beta Y in place, by the same kernels with an
+ * epilogue at the store (spmv_*_launch_axpby) */
+int csr_launch_axpby(const spmv_csr_dev *A, int waves, int group, int k,
+                     double alpha, double beta, const double *X, int64_t ldx,
+                     double *Y, int64_t ldy, hipStream_t s);
+int hll_launch_axpby(const spmv_hll_dev *H, int waves, int k, double alpha,
+                     double beta, const double *X, int64_t ldx, double *Y,
+                     int64_t ldy, hipStream_t s);
 
 /* kernel launchers (csr_kernels.hip / hll_kernels.hip) */
 int csr_launch_kernel(const spmv_csr_dev *A, int kernel, int waves, int group,
