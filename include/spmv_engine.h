@@ -343,8 +343,8 @@ int spmv_hll_value_bytes(const spmv_hll_dev *H); /* 8 or 4 */
  * one line in the tune log says so), _shape, _value_bytes, _algorithmic_bytes
  * / _kernel_bytes ((2 + value_bytes) S + 4 nb for the bases + 12 nb + 8 M +
  * 8 N), release / release_checked.  spmv_hll_build_panels*,
- * spmv_hll_launch_multi, spmv_hll_multi_bytes, spmv_hll_launch_axpby and
- * spmv_hll_axpby_bytes: -ENOTSUP.  The handle owns
+ * spmv_hll_launch_multi, spmv_hll_multi_bytes, spmv_hll_launch_axpby,
+ * spmv_hll_axpby_bytes and spmv_hll_cg: -ENOTSUP.  The handle owns
  * no 4-byte JA and no pad bitmap.  The one-shot seam, the reference ABI names
  * and spmv_mgpu.h create 4-byte handles only.
  */
@@ -500,6 +500,90 @@ int spmv_hll_launch_axpby(const spmv_hll_dev *H, const spmv_launch_opts *opts,
  * -ENOTSUP where multi_bytes answers so */
 int64_t spmv_csr_axpby_bytes(const spmv_csr_dev *A, int k, int reads_y);
 int64_t spmv_hll_axpby_bytes(const spmv_hll_dev *H, int k, int reads_y);
+
+/*
+ * Conjugate gradients on the device for A X = B (added after 0.7;
+ * spmv_version() is unchanged, detect it by the symbol).  A: square, symmetric
+ * positive definite, a CSR or column-major HLL handle of either value type.
+ * X, B: k = 1..8 interleaved vectors as in spmv_*_launch_multi; the k systems
+ * are independent: each column has its own scalars, its own convergence and
+ * its own status, and one launch_multi per iteration serves them all.  No
+ * preconditioner.
+ *
+ * d_X holds the initial guess on entry and the iterate on return; d_B is not
+ * written.  ldb, ldx >= k (0 = k); only columns 0..k-1 of rows 0..M-1 of X
+ * are read or written.  d_work == NULL: the library allocates and frees
+ * spmv_cg_work_bytes(M, k) bytes of device memory for the call; otherwise the
+ * caller's buffer is used (8-byte aligned, at least that many bytes, else
+ * -EINVAL) and a caller who solves repeatedly pays no allocation.  info: k
+ * entries in host memory.
+ *
+ * The call enqueues on `stream` and synchronises that stream at its checks:
+ * it BLOCKS and returns once the last check is done.  It cannot be captured
+ * into a graph: a stream that is capturing gets -EBUSY and nothing is
+ * enqueued.  The host enqueues check_every iterations (0 = 8), copies back k
+ * status words and synchronises, stops when no column is running or maxit is
+ * reached, and never enqueues an iteration beyond maxit.
+ *
+ * Checks: the handle, opts, k, the strides and the two pointers are checked by
+ * the function that serves launch_multi and launch_axpby, with the same
+ * answers (dead handle -EBADF / -ENODEV, compact handle -ENOTSUP, row-major
+ * HLL -EINVAL, after spmv_*_release_source() -ENODATA).  Additionally
+ * -EINVAL: M != N, a tol that is negative or NaN, maxit < 0, check_every < 0,
+ * NULL info.  M == 0: returns 0 with every info[j] = {0, 0, 0.0, 0.0}.
+ *
+ * Result contract, to the bit.  Every operation below is rounded once, no
+ * fused multiply-add crosses a * and a +.  tol2 = tol * tol on the host.
+ *
+ *   R = B;  R = (-1) A X + 1 R  by the handle's launch_axpby;  P = R
+ *   bb = dot(B, B);  rr = dot(R, R)
+ *   column j: status 2 (iterations 0) if rr_j or bb_j is not finite, else
+ *             converged (iterations 0) if rr_j <= tol2 * bb_j, else running
+ *   repeat at most maxit times:
+ *       Q = A P  by the handle's launch_multi (all k columns, same opts)
+ *       pq = dot(P, Q)
+ *       running column with !(pq_j > 0 and finite): status 2, frozen
+ *       running column: alpha = rr / pq;  X = X + alpha * P;
+ *                       R = R - alpha * Q;  iterations += 1
+ *       rn = dot(R, R)
+ *       running column: rn_j <= tol2 * bb_j -> status 0, frozen (rr_j = rn_j)
+ *                       rn_j not finite     -> status 2, frozen
+ *       running column: beta = rn / rr;  P = R + beta * P;  rr = rn
+ *   columns still running: status 1
+ *
+ * X, R, P and rr of a frozen column are never written again, whatever happens
+ * to the other columns and however many more iterations were enqueued before
+ * the host noticed.  So X, iterations, status and rr do not depend on
+ * check_every, on d_work being NULL or supplied, or on waves_per_block, and
+ * column j of a k-column solve has the bits of the k = 1 solve of B[:, j],
+ * X0[:, j].
+ *
+ * dot(u, v), per column, in an order that depends on M alone (not on k, the
+ * device or a launch shape): with NWG workgroups of T threads
+ * (spmv_cg_dot_shape: 1024, 256), element i belongs to slot i mod (NWG * T);
+ * a slot starts at 0.0 and adds rn(u_i * v_i) in increasing i; the T slots
+ * t = 0..T-1 of workgroup w (slots w T + t) are combined by a halving tree,
+ * s[t] += s[t + h] for h = T/2 .. 1; the NWG workgroup sums by the same tree.
+ */
+typedef struct spmv_cg_info {
+    int status;      /* 0 converged, 1 maxit reached, 2 breakdown */
+    int iterations;  /* updates of x applied to this column */
+    double rr;       /* last r.r of the recurrence for this column */
+    double bb;       /* b.b */
+} spmv_cg_info;
+
+int64_t spmv_cg_work_bytes(int M, int k); /* -EINVAL: M < 0, k outside 1..8 */
+void spmv_cg_dot_shape(int *workgroups, int *threads);
+int spmv_csr_cg(const spmv_csr_dev *A, const spmv_launch_opts *opts, int k,
+                const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                double tol, int maxit, int check_every,
+                void *d_work, size_t work_bytes,
+                spmv_cg_info *info, void *stream);
+int spmv_hll_cg(const spmv_hll_dev *H, const spmv_launch_opts *opts, int k,
+                const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                double tol, int maxit, int check_every,
+                void *d_work, size_t work_bytes,
+                spmv_cg_info *info, void *stream);
 
 /*
  * Pick the fastest kernel for this matrix by measurement (5 launches each):

@@ -11,6 +11,7 @@ is missing the import fails, and without a GPU every ``*_hip`` call raises
 ``OSError(ENODEV)``.
 """
 import atexit
+import collections
 import ctypes as C
 import os
 import re
@@ -397,6 +398,12 @@ class PanelOpts(C.Structure):
                 ("bucket_order", C.c_int), ("deterministic", C.c_int)]
 
 
+class CgInfo(C.Structure):
+    """spmv_cg_info (include/spmv_engine.h): one column of a cg() solve"""
+    _fields_ = [("status", C.c_int), ("iterations", C.c_int),
+                ("rr", C.c_double), ("bb", C.c_double)]
+
+
 _CSRp = C.POINTER(SparseCSR)
 _HLLp = C.POINTER(SparseHLL)
 
@@ -539,6 +546,8 @@ _sig("spmv_hll_launch_blocks", C.c_int, C.c_void_p, C.c_int,
 _sig("spmv_hll_shape", C.c_int, C.c_void_p, _ip, _ip, C.POINTER(C.c_int64),
      _ip, C.POINTER(C.c_int64), _ip)
 _sig("spmv_hll_kernel_bytes", C.c_int64, C.c_void_p, C.c_int)
+_sig("spmv_cg_work_bytes", C.c_int64, C.c_int, C.c_int)
+_sig("spmv_cg_dot_shape", None, _ip, _ip)
 # spmv_csr_<name> and spmv_hll_<name>: the same argument types
 _TWINS = (
     ("release_checked", None, C.c_void_p, C.c_uint64),
@@ -572,6 +581,10 @@ _TWINS = (
      C.c_void_p, C.POINTER(LaunchOpts), C.c_int, C.c_double, C.c_double,
      C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p),
     ("axpby_bytes", C.c_int64, C.c_void_p, C.c_int, C.c_int),
+    ("cg", C.c_int,
+     C.c_void_p, C.POINTER(LaunchOpts), C.c_int, C.c_void_p, C.c_int64,
+     C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_int, C.c_void_p,
+     C.c_size_t, C.POINTER(CgInfo), C.c_void_p),
     ("time", C.c_int,
      C.c_void_p, C.c_int, C.POINTER(LaunchOpts), C.c_void_p, C.c_void_p,
      C.c_int, C.c_int, C.c_size_t, _dp, C.c_void_p),
@@ -632,6 +645,29 @@ def _opts(waves_per_block=0, group=0, variant=0):
     o.group = int(group)
     o.variant = int(variant)
     return o
+
+
+def _cg_dot_shape():
+    nwg, t = C.c_int(), C.c_int()
+    _lib.spmv_cg_dot_shape(C.byref(nwg), C.byref(t))
+    return nwg.value, t.value
+
+
+#: (workgroups, threads) of the solver's dot product: element i of a vector
+#: belongs to slot i mod (workgroups * threads) -- the order of a dot is a
+#: function of M and of these two constants (spmv_engine.h, spmv_*_cg)
+CG_DOT_SHAPE = _cg_dot_shape()
+#: spmv_cg_info.status
+CG_CONVERGED, CG_MAXIT, CG_BREAKDOWN = 0, 1, 2
+#: one column of a cg() solve
+CgResult = collections.namedtuple("CgResult", "status iterations rr bb")
+
+
+def cg_work_bytes(M, k):
+    """bytes of device memory one cg() solve of k systems with M rows needs
+    (what `work` must hold at least)"""
+    return _check(_lib.spmv_cg_work_bytes(int(M), int(k)),
+                  "spmv_cg_work_bytes")
 
 
 def version():
@@ -1327,6 +1363,33 @@ class _Device:
         return _check(self._fn("axpby_bytes")(self.h, int(k),
                                               int(float(beta) != 0.0)),
                       "spmv_%s_axpby_bytes" % self._FMT)
+
+    def cg(self, d_B, d_X, k=1, tol=1e-8, maxit=1000, check_every=0, ldb=0,
+           ldx=0, work=None, waves_per_block=0, group=0, stream=None):
+        """Conjugate gradients for A X = B on the device, A symmetric positive
+        definite, k = 1..8 independent systems stored interleaved as in
+        launch_multi (ldb, ldx >= k or 0).  d_X holds the initial guess and
+        receives the iterate; d_B is not written.  Stops a column when
+        r.r <= tol^2 b.b, after maxit iterations, or on a breakdown (p.Ap not
+        positive, a non-finite scalar).  The call BLOCKS (it synchronises
+        `stream` every check_every iterations, 0 = 8) and cannot be captured
+        into a graph.  `work`: a DevBuffer of at least cg_work_bytes(M, k)
+        bytes to solve without an allocation, None to let the library
+        allocate and free one.  -> [CgResult(status, iterations, rr, bb)] * k;
+        the result does not depend on check_every, work or waves_per_block."""
+        k, ldb, ldx = int(k), int(ldb), int(ldx)
+        if not 1 <= k <= 8:
+            raise ValueError("k=%r: 1..8 systems per solve" % (k,))
+        if (ldb and ldb < k) or (ldx and ldx < k):
+            raise ValueError("ldb=%d, ldx=%d: at least k=%d (or 0)"
+                             % (ldb, ldx, k))
+        o = _opts(waves_per_block, group if self._FMT == "csr" else 0)
+        info = (CgInfo * k)()
+        self._call("cg", C.byref(o), k, d_B, ldb, d_X, ldx, float(tol),
+                   int(maxit), int(check_every),
+                   work.ptr if work is not None else None,
+                   work.nbytes if work is not None else 0, info, stream)
+        return [CgResult(i.status, i.iterations, i.rr, i.bb) for i in info]
 
     def build_panels(self, panel_cols=0, sched=None, tile_rows=0,
                      sweep_wgs_per_cu=0, reserve_cus=0, lds_min=0,

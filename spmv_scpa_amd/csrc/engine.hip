@@ -1774,6 +1774,41 @@ static int64_t axpby_bytes(const D *d, int k, int reads_y) {
     return b < 0 || !reads_y ? b : b + 8 * (int64_t)k * d->M;
 }
 
+/* ---- conjugate gradients (cg_kernels.hip): the checked entry point ---- */
+template <typename D>
+static int cg_multi_of(const void *h, const spmv_launch_opts *opts, int k,
+                       const double *X, int64_t ldx, double *Y, int64_t ldy,
+                       hipStream_t s) {
+    return multi_direct((const D *)h, opts, k, X, ldx, Y, ldy, s);
+}
+template <typename D>
+static int cg_axpby_of(const void *h, const spmv_launch_opts *opts, int k,
+                       double alpha, double beta, const double *X, int64_t ldx,
+                       double *Y, int64_t ldy, hipStream_t s) {
+    return axpby_direct((const D *)h, opts, k, alpha, beta, X, ldx, Y, ldy, s);
+}
+
+template <typename D>
+static int cg(const D *d, const spmv_launch_opts *opts, int k,
+              const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+              double tol, int maxit, int check_every, void *d_work,
+              size_t work_bytes, spmv_cg_info *info, void *stream) {
+    const int rc = multi_check(d, opts, k, d_B, &ldb, d_X, &ldx);
+    if (rc < 0)
+        return rc;
+    if (d->M != d->N || !(tol >= 0.0) || maxit < 0 || check_every < 0 || !info)
+        return -EINVAL;
+    if (rc) { /* no rows */
+        for (int j = 0; j < k; ++j)
+            info[j] = spmv_cg_info{0, 0, 0.0, 0.0};
+        return 0;
+    }
+    const cg_matrix A = {d, opts, d->M, cg_multi_of<D>, cg_axpby_of<D>};
+    return cg_solve(&A, k, d_B, ldb, d_X, ldx, tol, maxit,
+                    check_every ? check_every : 8, d_work, work_bytes, info,
+                    (hipStream_t)stream);
+}
+
 /* a new blocked copy in place of the old one: `build(&d->panels)` */
 template <typename D, typename Build> static int rebuild(D *d, Build build) {
     if (d->value_bytes == 4)
@@ -2335,6 +2370,14 @@ static int copy_tune_log(const D *d, char *buf, size_t len) {
     int64_t spmv_##fmt##_axpby_bytes(const D *d, int k, int reads_y) {         \
         return axpby_bytes(d, k, reads_y);                                     \
     }                                                                          \
+    int spmv_##fmt##_cg(const D *d, const spmv_launch_opts *opts, int k,       \
+                        const double *d_B, int64_t ldb, double *d_X,           \
+                        int64_t ldx, double tol, int maxit, int check_every,   \
+                        void *d_work, size_t work_bytes, spmv_cg_info *info,   \
+                        void *stream) {                                        \
+        return cg(d, opts, k, d_B, ldb, d_X, ldx, tol, maxit, check_every,     \
+                  d_work, work_bytes, info, stream);                           \
+    }                                                                          \
     int spmv_##fmt##_time(const D *d, int kernel,                              \
                           const spmv_launch_opts *opts, const double *d_x,     \
                           double *d_y, int warmup, int iters,                  \
@@ -2390,6 +2433,14 @@ extern "C" {
 
 HANDLE_API(csr, spmv_csr_dev, launch_rows)
 HANDLE_API(hll, spmv_hll_dev, launch_blocks)
+
+int64_t spmv_cg_work_bytes(int M, int k) { return cg_work_bytes(M, k); }
+void spmv_cg_dot_shape(int *workgroups, int *threads) {
+    if (workgroups)
+        *workgroups = CG_NWG;
+    if (threads)
+        *threads = CG_T;
+}
 
 /* ------------------------------------------------------------------ */
 /* one-shot entry points: the reference's seam (hip_csr.h / hip_hll.h)  */

@@ -1,7 +1,7 @@
 /*
  * hip_common.h -- internals shared by the HIP translation units
  * (engine.hip, csr_kernels.hip, hll_kernels.hip, multi_kernels.hip,
- * panels.hip, mgpu.hip, and mat_ref.h on behalf of the first and the last).
+ * cg_kernels.hip, panels.hip, mgpu.hip, and mat_ref.h on behalf of the first and the last).
  * Not installed.
  */
 #ifndef SPMV_HIP_COMMON_H
@@ -499,6 +499,39 @@ int csr_launch_axpby(const spmv_csr_dev *A, int waves, int group, int k,
 int hll_launch_axpby(const spmv_hll_dev *H, int waves, int k, double alpha,
                      double beta, const double *X, int64_t ldx, double *Y,
                      int64_t ldy, hipStream_t s);
+
+/*
+ * Conjugate gradients (cg_kernels.hip; spmv_*_cg).  The shape of the dot
+ * product -- CG_NWG workgroups of CG_T threads, element i in slot
+ * i mod (CG_NWG * CG_T) -- is part of the result contract
+ * (spmv_cg_dot_shape): the order of a dot depends on M and on nothing else.
+ */
+#define CG_NWG 1024
+#define CG_T 256
+#define CG_STATE_BYTES 512                /* per-column state, cg_kernels.hip */
+#define CG_PART_BYTES (CG_NWG * 8 * 8)    /* CG_NWG workgroup sums of 8 columns */
+/* spmv_cg_info.status, and the one value only the device sees */
+#define CG_CONVERGED 0
+#define CG_MAXIT 1
+#define CG_BREAKDOWN 2
+#define CG_RUNNING 3
+/* the matrix as the solver sees it: the handle's launch_multi and
+ * launch_axpby with the caller's opts (engine.hip fills it in) */
+struct cg_matrix {
+    const void *handle;
+    const spmv_launch_opts *opts;
+    int M;
+    int (*multi)(const void *handle, const spmv_launch_opts *opts, int k,
+                 const double *X, int64_t ldx, double *Y, int64_t ldy,
+                 hipStream_t s);
+    int (*axpby)(const void *handle, const spmv_launch_opts *opts, int k,
+                 double alpha, double beta, const double *X, int64_t ldx,
+                 double *Y, int64_t ldy, hipStream_t s);
+};
+int64_t cg_work_bytes(int M, int k);
+int cg_solve(const cg_matrix *A, int k, const double *B, int64_t ldb, double *X,
+             int64_t ldx, double tol, int maxit, int check_every, void *d_work,
+             size_t work_bytes, spmv_cg_info *info, hipStream_t s);
 
 /* kernel launchers (csr_kernels.hip / hll_kernels.hip) */
 int csr_launch_kernel(const spmv_csr_dev *A, int kernel, int waves, int group,
