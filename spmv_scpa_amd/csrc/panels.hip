@@ -63,9 +63,8 @@
 
 #include "hip_common.h"
 #include "panel_launch.h"
+#include "panel_build.h"
 
-#define TILE_ROWS_STEPS 4096 /* "steps" schedule default: 32 KiB of LDS */
-#define SWEEP_WG_PER_CU 2
 #define SWEEP_SPIN_MAX 512   /* polls (~1 us each) before a wait gives up:
                                 perf only, see phase_wait */
 #define CNT_STRIDE 32        /* one phase counter per 128-B line */
@@ -126,17 +125,36 @@ struct spmv_panels : panel_shape {
                          arrivals): epoch_arrive, hip_common.h */
     unsigned launch_epoch;
 };
-/* threshold: the second launch costs ~8 us; a row inside the copy costs its
- * tile ~1.3 ns per entry of serialised accumulation -- power-law 1M x 3 with
- * one row of 8291 entries: 0.043 ms inside, 0.052 beside; a row of 30 000+
- * entries is worth the launch (4M rows: 0.155 -> 0.127 ms) */
-#define PANELS_LONG_ROW 16384
-#ifndef PANELS_LONG_SEG
-#define PANELS_LONG_SEG 1024
-#endif
-#define PANELS_LONG_MAX 4096 /* more such rows than this: keep them inside */
+/* (PANELS_LONG_ROW, PANELS_LONG_SEG, PANELS_LONG_MAX: panel_build.h) */
 
-static void big_free(void *p); /* block pool of a selector run, below */
+static hipError_t big_malloc(void **p, size_t bytes); /* block pool of a */
+static void big_free(void *p);                        /* selector run, below */
+
+/* a device block that frees itself, move-only: POOLED from the block pool
+ * (big_malloc / big_free), else plain hipMalloc / hipFree */
+template <bool POOLED> struct dev_block {
+    void *p = NULL;
+    dev_block() = default;
+    dev_block(dev_block &&o) : p(o.p) { o.p = NULL; }
+    dev_block &operator=(dev_block &&o) {
+        std::swap(p, o.p);
+        return *this;
+    }
+    ~dev_block() { reset(); }
+    hipError_t alloc(size_t bytes) {
+        return POOLED ? big_malloc(&p, bytes) : hipMalloc(&p, bytes);
+    }
+    void reset() {
+        if (POOLED)
+            big_free(p);
+        else
+            (void)hipFree(p);
+        p = NULL;
+    }
+    template <typename T> T *as() const { return (T *)p; }
+};
+typedef dev_block<true> pooled_block;
+typedef dev_block<false> plain_block;
 
 void panels_free(spmv_panels *p) {
     if (!p)
@@ -483,13 +501,6 @@ extern "C" int spmv_set_panel_schedule(int sched) {
     return 0;
 }
 
-/* rows of y one workgroup can hold when `per_cu` of them share a CU's LDS */
-static int sweep_tile_rows_max(int per_cu) {
-    /* the workgroups of a CU share 160 KiB; each carries a 128-byte static
-     * ring besides its tile */
-    return (int)((160 * 1024 - 128 * per_cu) / per_cu / 8 / 32 * 32);
-}
-
 /* compute units of the current device; -ENODEV unless it is a gfx950 (the
  * XCD count and dispatch order the sweep schedule relies on, NUM_XCD, are
  * facts of that chip; the code objects are built for it alone anyway) */
@@ -502,16 +513,6 @@ static int device_cus(void) {
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return -ENODEV;
     return prop.multiProcessorCount;
-}
-
-/* tile height of the sweep schedule: the fewest rounds of (grid x tile_max)
- * rows that cover M, rows spread evenly over them */
-static long long sweep_tile_rows(int M, int grid, int tile_max) {
-    const long long rounds = ((long long)M + (long long)grid * tile_max - 1) /
-                             ((long long)grid * tile_max);
-    const long long wg = (rounds > 0 ? rounds : 1) * grid;
-    long long tr = (((long long)M + wg - 1) / wg + 31) / 32 * 32;
-    return tr < 32 ? 32 : tr;
 }
 
 /* Tile height of the chain / steps schedules with one workgroup per CU (tall
@@ -537,53 +538,22 @@ __global__ void k_tile_starts(int tiles, int panels,
         out[t] = bptr[(int64_t)t * panels];
 }
 
-/* contiguous tile ranges of about equal entry counts, one per XCD */
+/* contiguous tile ranges of about equal entry counts, one per XCD
+ * (panel_xcd_ranges) */
 static int balance_xcd_ranges(spmv_panels *P) {
-    int rc = 0;
-    int64_t *d_st = NULL;
     const int tiles = P->tiles;
     std::vector<int64_t> st((size_t)tiles + 1, 0);
+    plain_block d_st;
     if (tiles > 0) {
-        HIP_TRY(hipMalloc((void **)&d_st, ((size_t)tiles + 1) * sizeof(int64_t)));
+        HIP_RET(d_st.alloc(st.size() * sizeof(int64_t)));
         hipLaunchKernelGGL(k_tile_starts, dim3((tiles + 256) / 256), dim3(256),
-                           0, 0, tiles, P->panels, P->bptr, d_st);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpy(st.data(), d_st, ((size_t)tiles + 1) * sizeof(int64_t),
+                           0, 0, tiles, P->panels, P->bptr, d_st.as<int64_t>());
+        HIP_RET(hipGetLastError());
+        HIP_RET(hipMemcpy(st.data(), d_st.p, st.size() * sizeof(int64_t),
                           hipMemcpyDeviceToHost));
     }
-    {
-        const int64_t total = st[tiles] - st[0];
-        P->xcd_first[0] = 0;
-        for (int k = 1; k < NUM_XCD; ++k) {
-            /* first tile whose start reaches k/8 of the entries; every tile
-             * also counts one slot so that empty tiles spread evenly */
-            const double want = (double)(total + tiles) * k / NUM_XCD;
-            int lo = P->xcd_first[k - 1], hi = tiles;
-            while (lo < hi) {
-                const int mid = lo + (hi - lo) / 2;
-                if ((double)(st[mid] - st[0] + mid) < want)
-                    lo = mid + 1;
-                else
-                    hi = mid;
-            }
-            P->xcd_first[k] = lo;
-        }
-        P->xcd_first[NUM_XCD] = tiles;
-        P->xcd_max = 0;
-        for (int k = 0; k < NUM_XCD; ++k)
-            if (P->xcd_first[k + 1] - P->xcd_first[k] > P->xcd_max)
-                P->xcd_max = P->xcd_first[k + 1] - P->xcd_first[k];
-    }
-fail:
-    (void)hipFree(d_st);
-    return rc;
-}
-
-static int bits_for(long long n) { /* smallest b with 2^b >= n */
-    int b = 0;
-    while ((1ll << b) < n)
-        ++b;
-    return b;
+    P->xcd_max = panel_xcd_ranges(st.data(), tiles, P->xcd_first);
+    return 0;
 }
 
 /* ------------------------------------------------------------------ */
@@ -736,96 +706,82 @@ __global__ void __launch_bounds__(256)
     }
 }
 
+/* what a blocked copy is built from: the arrays of a CSR handle (irp) or of
+ * an HLL handle (off, padmask) */
+struct build_src {
+    int M, nb;
+    int64_t slots; /* entries (CSR) / stored slots, padding included (HLL) */
+    const int *irp;
+    const int64_t *off;
+    int col_major;
+    const int *ja;
+    const double *as;
+    const unsigned *padmask;
+};
+
 /* find the long rows of the source and copy them beside the (future) copy;
  * P->nlong stays 0 when there are none (or absurdly many: then they stay in
- * the buckets).  Called before the keys are made. */
-static int long_rows_extract(spmv_panels *P, int M, int nb,
-                             const int *irp_or_null, const int64_t *off_or_null,
-                             int col_major, const int *ja, const double *as,
-                             const unsigned *padmask) {
-    int rc = 0;
-    int *d_list = NULL;
+ * the buckets; panel_long_segments).  Called before the keys are made. */
+static int long_rows_extract(spmv_panels *P, const build_src &s) {
+    const int M = s.M;
     std::vector<int> list((size_t)2 * PANELS_LONG_MAX + 1, 0);
-    std::vector<std::pair<int, int>> rows; /* (row, length) */
-    std::vector<int> h_row, h_ptr, h_seg0;
-    std::vector<int2> h_seg;
-    (void)nb;
+    panel_long_rows L;
+    static_assert(sizeof(panel_long_seg) == sizeof(int2), "uploaded in one copy");
     if (M <= 0)
         return 0;
-    HIP_TRY(hipMalloc((void **)&d_list, list.size() * sizeof(int)));
-    HIP_TRY(hipMemset(d_list, 0, sizeof(int)));
-    if (irp_or_null)
-        hipLaunchKernelGGL(k_long_rows_csr, dim3((M + 255) / 256), dim3(256), 0,
-                           0, M, PANELS_LONG_ROW, PANELS_LONG_MAX, irp_or_null,
-                           d_list);
+    plain_block d_list;
+    HIP_RET(d_list.alloc(list.size() * sizeof(int)));
+    HIP_RET(hipMemset(d_list.p, 0, sizeof(int)));
+    if (s.irp)
+        hipLaunchKernelGGL(k_long_rows_csr, dim3((M + 255) / 256), dim3(256),
+                           0, 0, M, PANELS_LONG_ROW, PANELS_LONG_MAX, s.irp,
+                           d_list.as<int>());
     else
         hipLaunchKernelGGL(k_long_rows_hll,
                            dim3((unsigned)std::min<long long>(
                                ((long long)M * WAVE + 255) / 256, 1 << 22)),
-                           dim3(256), 0, 0, M, PANELS_LONG_ROW, PANELS_LONG_MAX,
-                           col_major, off_or_null, padmask, d_list);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(list.data(), d_list, list.size() * sizeof(int),
+                           dim3(256), 0, 0, M, PANELS_LONG_ROW,
+                           PANELS_LONG_MAX, s.col_major, s.off, s.padmask,
+                           d_list.as<int>());
+    HIP_RET(hipGetLastError());
+    HIP_RET(hipMemcpy(list.data(), d_list.p, list.size() * sizeof(int),
                       hipMemcpyDeviceToHost));
-    if (list[0] <= 0 || list[0] > PANELS_LONG_MAX)
-        goto fail; /* none / too many: nothing beside the copy */
-    for (int k = 0; k < list[0]; ++k)
-        rows.push_back({list[1 + 2 * k], list[2 + 2 * k]});
-    std::sort(rows.begin(), rows.end());
-    {
-        int64_t at = 0;
-        for (size_t h = 0; h < rows.size(); ++h) {
-            h_row.push_back(rows[h].first);
-            h_ptr.push_back((int)at);
-            h_seg0.push_back((int)h_seg.size());
-            for (int b = 0; b < rows[h].second; b += PANELS_LONG_SEG)
-                h_seg.push_back(make_int2((int)h, (int)at + b));
-            at += rows[h].second;
-            if (at > (int64_t)INT32_MAX)
-                goto fail; /* keep them inside */
-        }
-        h_ptr.push_back((int)at);
-        P->long_nnz = at;
-    }
-    P->nlong = (int)rows.size();
-    P->nlong_seg = (int)h_seg.size();
-    HIP_TRY(hipMalloc((void **)&P->long_row, h_row.size() * sizeof(int)));
-    HIP_TRY(hipMalloc((void **)&P->long_ptr, h_ptr.size() * sizeof(int)));
-    HIP_TRY(hipMalloc((void **)&P->long_seg0, h_seg0.size() * sizeof(int)));
-    HIP_TRY(hipMalloc((void **)&P->long_seg, h_seg.size() * sizeof(int2)));
-    HIP_TRY(hipMalloc((void **)&P->long_ja, (size_t)P->long_nnz * sizeof(int)));
-    HIP_TRY(hipMalloc((void **)&P->long_as, (size_t)P->long_nnz * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&P->long_part, h_seg.size() * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&P->long_cnt,
-                      h_row.size() * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(P->long_part, 0, h_seg.size() * sizeof(double)));
-    HIP_TRY(hipMemset(P->long_cnt, 0,
-                      h_row.size() * sizeof(unsigned long long)));
-    HIP_TRY(hipMemcpy(P->long_row, h_row.data(), h_row.size() * sizeof(int),
+    if (!panel_long_segments(list.data(), &L))
+        return 0; /* nothing beside the copy */
+    P->long_nnz = L.nnz;
+    P->nlong = (int)L.row.size();
+    P->nlong_seg = (int)L.seg.size();
+    HIP_RET(hipMalloc((void **)&P->long_row, L.row.size() * sizeof(int)));
+    HIP_RET(hipMalloc((void **)&P->long_ptr, L.ptr.size() * sizeof(int)));
+    HIP_RET(hipMalloc((void **)&P->long_seg0, L.seg0.size() * sizeof(int)));
+    HIP_RET(hipMalloc((void **)&P->long_seg, L.seg.size() * sizeof(int2)));
+    HIP_RET(hipMalloc((void **)&P->long_ja, (size_t)P->long_nnz * sizeof(int)));
+    HIP_RET(hipMalloc((void **)&P->long_as, (size_t)P->long_nnz * sizeof(double)));
+    HIP_RET(hipMalloc((void **)&P->long_part, L.seg.size() * sizeof(double)));
+    HIP_RET(hipMalloc((void **)&P->long_cnt,
+                      L.row.size() * sizeof(unsigned long long)));
+    HIP_RET(hipMemset(P->long_part, 0, L.seg.size() * sizeof(double)));
+    HIP_RET(hipMemset(P->long_cnt, 0,
+                      L.row.size() * sizeof(unsigned long long)));
+    HIP_RET(hipMemcpy(P->long_row, L.row.data(), L.row.size() * sizeof(int),
                       hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(P->long_ptr, h_ptr.data(), h_ptr.size() * sizeof(int),
+    HIP_RET(hipMemcpy(P->long_ptr, L.ptr.data(), L.ptr.size() * sizeof(int),
                       hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(P->long_seg0, h_seg0.data(), h_seg0.size() * sizeof(int),
+    HIP_RET(hipMemcpy(P->long_seg0, L.seg0.data(), L.seg0.size() * sizeof(int),
                       hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(P->long_seg, h_seg.data(), h_seg.size() * sizeof(int2),
+    HIP_RET(hipMemcpy(P->long_seg, L.seg.data(), L.seg.size() * sizeof(int2),
                       hipMemcpyHostToDevice));
-    if (irp_or_null)
+    if (s.irp)
         hipLaunchKernelGGL(k_long_copy_csr, dim3(P->nlong), dim3(256), 0, 0,
-                           P->long_row, P->long_ptr, irp_or_null, ja, as,
+                           P->long_row, P->long_ptr, s.irp, s.ja, s.as,
                            P->long_ja, P->long_as);
     else
         hipLaunchKernelGGL(k_long_copy_hll, dim3(P->nlong), dim3(WAVE), 0, 0, M,
-                           col_major, P->long_row, P->long_ptr, off_or_null, ja,
-                           as, padmask, P->long_ja, P->long_as);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-fail:
-    (void)hipFree(d_list);
-    if (rc) {
-        P->nlong = P->nlong_seg = 0;
-        P->long_nnz = 0;
-    }
-    return rc;
+                           s.col_major, P->long_row, P->long_ptr, s.off, s.ja,
+                           s.as, s.padmask, P->long_ja, P->long_as);
+    HIP_RET(hipGetLastError());
+    HIP_RET(hipDeviceSynchronize());
+    return 0;
 }
 
 /*
@@ -916,372 +872,365 @@ static double build_now_s(void) {
     return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec;
 }
 
-static int panels_build(int M, int N, int64_t slots, const spmv_panel_opts *o,
-                        int nb, const int *irp_or_null,
-                        const int64_t *off_or_null, int col_major,
-                        const int *ja, const double *as,
-                        const unsigned *padmask, spmv_panels **out) {
-    int rc = 0;
-    *out = NULL;
-    if (slots > (int64_t)INT32_MAX)
-        return -EOVERFLOW;
-    spmv_panel_opts dflt;
-    spmv_panel_opts_default(&dflt);
-    if (!o)
-        o = &dflt;
-    if (o->struct_size != (int)sizeof(spmv_panel_opts))
-        return -EINVAL; /* caller built against another header (ABI note) */
-    if (o->sched > 2 || o->panel_cols < 0 || o->tile_rows < 0 ||
-        o->sweep_wgs_per_cu < 0 || o->sweep_wgs_per_cu > 8 ||
-        o->reserve_cus < 0 || o->lds_min < 0 || o->lds_min > BIG_LDS_BYTES ||
-        o->tile_order < 0 || o->tile_order > 2 || o->sweep_layout < -1 ||
-        o->sweep_layout > 1 || o->bucket_order < 0 || o->bucket_order > 1 ||
-        o->deterministic < 0 || o->deterministic > 2)
-        return -EINVAL;
-    const int panel_cols = o->panel_cols, tile_rows = o->tile_rows;
-    int sched = o->sched;
-    if (sched < 0)
-        sched = g_panel_sched.load(std::memory_order_relaxed);
-    const int sweep = sched == 1;
-    /* tile height.  steps: the taller the tile, the more entries of a bucket
-     * share a line of x (fewer L2 requests) but the fewer workgroups there
-     * are and the more LDS each holds; best measured per matrix: 2048 rows
-     * for a band of 2^14 columns (0.68 ms), 8192 for 2^17 (0.84), 16384 for
-     * 2^20 (1.18) and for skewed rows (0.21) -- spmv_*_autotune tries these.
-     * sweep: sweep_tile_rows(). */
-    long long tr = TILE_ROWS_STEPS;
-    int grid = 0, tile_max = 20448 /* steps: 160 KiB of LDS */, per_cu = 0;
-    int want_shift = 18; /* 2^18 columns = 2 MiB of x: half of an XCD's L2 */
-    if (panel_cols > 0)
-        want_shift = bits_for((long long)panel_cols + 1) - 1; /* floor(log2) */
-    if (sweep) {
-        /* one 1024-lane workgroup per CU with a 160 KiB tile, or two of up
-         * to 512 lanes with 80 KiB tiles.  The tall tile halves the panel
-         * (row and column index share 32 bits) but puts twice the entries
-         * on a line of x, which the column-sorted buckets turn into fewer
-         * L2 requests: 1.61 vs 1.77 ms on config 3.  It needs buckets that
-         * fill its 4096-slot chunks, so it is taken only above 4000 entries
-         * per bucket (80 M columns, 1071 per bucket: 4.85 vs 3.35 ms). */
-        int cus = device_cus();
-        if (cus < 0)
-            return cus;
-        if (o->reserve_cus > 0) /* keep at least one XCD's worth of CUs */
-            cus = cus - o->reserve_cus >= NUM_XCD ? cus - o->reserve_cus : NUM_XCD;
-        per_cu = o->sweep_wgs_per_cu;
-        if (per_cu == 0) {
-            const int tm = sweep_tile_rows_max(1);
-            const long long tr1 = sweep_tile_rows(M, cus, tm);
-            int sh = want_shift;
-            if (sh > 32 - bits_for(tr1))
-                sh = 32 - bits_for(tr1);
-            const double tiles1 = (double)(((long long)M + tr1 - 1) / tr1);
-            const double panels1 =
-                (double)((((int64_t)(N > 0 ? N : 1) - 1) >> sh) + 1);
-            per_cu = (double)slots / (tiles1 * panels1) >= 4000.0
-                         ? 1 : SWEEP_WG_PER_CU;
-        }
-        grid = cus * per_cu;
-        tile_max = sweep_tile_rows_max(per_cu);
-        tr = sweep_tile_rows(M, grid, tile_max);
-#ifdef SPMV_ABLATIONS
-        /* round-6 probe (tools/tall_tile_probe.py): a sweep copy with tiles
-         * TALLER than a CU's LDS can hold, launched with variant ablation 5 / 6
-         * (LDS index aliased, y WRONG by design): the L2 request pattern of
-         * accumulators that do not exist yet */
-        if (const char *e = getenv("SPMV_ABL_SWEEP_TILE_ROWS")) {
-            const long long v = atoll(e) / 32 * 32;
-            if (v >= 32 && v < (1 << 20)) {
-                per_cu = 1;
-                grid = cus;
-                tr = v;
-            }
-        }
-#endif
-    }
-    if (!sweep && tile_rows >= 32 && tile_rows <= tile_max)
-        tr = tile_rows / 32 * 32;
-    const int rbits = bits_for(tr);
-    int shift = want_shift;
-    if (shift > 32 - rbits) /* row-in-tile and column-in-panel share a word */
-        shift = 32 - rbits;
-    const int panels = (int)((((int64_t)(N > 0 ? N : 1) - 1) >> shift) + 1);
-    const int tiles = (int)(((long long)M + tr - 1) / tr);
-    /* bucket tables are indexed with int (hipCUB scan length) */
-    if ((uint64_t)(tiles > 0 ? tiles : 1) * (uint64_t)panels >=
-        (uint64_t)INT32_MAX)
-        return -EOVERFLOW;
+/* ---- the stages of a build, in the order panels_build runs them.  Each
+ * gets the geometry and the blocks it reads or fills; a block's owner frees
+ * it, so a stage that fails just returns ---- */
 
-    spmv_panels *P = (spmv_panels *)calloc(1, sizeof *P);
-    if (!P)
-        return -ENOMEM;
-    P->N = N;
-    P->shift = shift;
-    P->panels = panels;
-    P->tile_rows = (int)tr;
-    P->tiles = tiles;
-    P->sweep = sweep;
-    P->chain = sched == 2;
-    P->grid = sweep ? (grid < tiles ? grid : (tiles > 0 ? tiles : 1)) : 0;
-    P->wgs_per_cu = per_cu;
-    P->reserve_cus = sweep ? o->reserve_cus : 0;
-    /* panel-major is the default (-1): 1.448 vs 1.464 ms on config 3, 2.88
-     * vs 2.96 ms on one shard of the 80M-column problem, and the masked tail
-     * blocks re-read a cached line instead of fetching another bucket */
-    P->pmajor = sweep && o->sweep_layout != 0;
-    P->lds_min = o->lds_min;
-    P->bucket_order = o->bucket_order;
-    /* 0 = default: ordered additions on sweep layouts (free there: the
-     * hand-offs hide under the request-bound loop, +-2 %), arrival order on
-     * chain / steps (+3..+10 % there); 1 = always, 2 = never */
-    P->det = o->deterministic == 1 || (o->deterministic == 0 && sweep);
-    P->order = sweep ? 0 : o->tile_order;
-    /* bucket ids: tile-major, or panel-major inside rounds of P->grid tiles */
-    const int pm_grid = P->pmajor ? P->grid : 0;
-    const int64_t nbuckets =
-        pm_grid ? (int64_t)((tiles + pm_grid - 1) / pm_grid) * panels * pm_grid
-                : (int64_t)tiles * panels;
-    if ((uint64_t)nbuckets >= (uint64_t)INT32_MAX) {
-        free(P);
-        return -EOVERFLOW;
+/* HLL source: flag the slots that hold entries and count them (see
+ * k_hll_keep_flags) */
+static int hll_flag_kept(const build_src &s, const spmv_panels *P,
+                         pooled_block &flag, plain_block &count,
+                         int64_t *kept) {
+    unsigned long long h_count = 0;
+    HIP_RET(flag.alloc((size_t)s.slots));
+    HIP_RET(count.alloc(sizeof h_count));
+    HIP_RET(hipMemset(count.p, 0, sizeof h_count));
+    hipLaunchKernelGGL(k_hll_keep_flags,
+                       dim3((unsigned)std::min<int64_t>((s.slots + 255) / 256,
+                                                        8192)),
+                       dim3(256), 0, 0, s.M, s.nb, s.slots, P->long_row,
+                       P->nlong, s.col_major, s.off, s.padmask,
+                       flag.as<unsigned char>(),
+                       count.as<unsigned long long>());
+    HIP_RET(hipGetLastError());
+    HIP_RET(hipMemcpy(&h_count, count.p, sizeof h_count, hipMemcpyDeviceToHost));
+    *kept = (int64_t)h_count;
+    return 0;
+}
+
+/* the double buffers of the sort and, for an HLL source that pads, the list
+ * of kept slots */
+static int alloc_sort_buffers(int64_t n_sort, bool want_idx,
+                              pooled_block (&key)[2], pooled_block (&sv)[2],
+                              pooled_block &idx) {
+    const size_t na = (size_t)(n_sort > 0 ? n_sort : 1);
+    for (int k = 0; k < 2; ++k) {
+        HIP_RET(key[k].alloc(na * sizeof(uint64_t)));
+        HIP_RET(sv[k].alloc(na * sizeof(double)));
     }
-    uint64_t *key[2] = {NULL, NULL};
-    double *sv[2] = {NULL, NULL}; /* the values the sort carries */
-    unsigned *idx = NULL;         /* HLL source with pads: kept slots */
-    uint64_t *skey = NULL;
-    double *sval = NULL;
-    void *tmp = NULL;
+    if (want_idx)
+        HIP_RET(idx.alloc(na * sizeof(unsigned)));
+    return 0;
+}
+
+static int keys_from_csr(const panel_geometry &g, const build_src &s,
+                         const spmv_panels *P, uint64_t *key, double *val) {
+    hipLaunchKernelGGL(k_keys_from_csr,
+                       dim3((unsigned)std::min<long long>(
+                           ((long long)s.M * 8 + 255) / 256, 1 << 23)),
+                       dim3(256), 0, 0, s.M, g.tile_rows, g.panels, g.shift,
+                       g.rbits, g.pm_grid, (uint64_t)g.nbuckets, P->long_row,
+                       P->nlong, s.irp, s.ja, s.as, key, val);
+    HIP_RET(hipGetLastError());
+    HIP_RET(hipDeviceSynchronize());
+    return 0;
+}
+
+/* the flagged slots' indices compacted (ascending) into idx -- unless the
+ * format padded nothing: idx is empty and every slot is kept -- then their
+ * keys; the flags go back to the pool in between */
+static int keys_from_hll(const panel_geometry &g, const build_src &s,
+                         int64_t n_sort, pooled_block &flag,
+                         const plain_block &count, const pooled_block &idx,
+                         uint64_t *key, double *val) {
+    if (n_sort > 0) {
+        if (idx.p) {
+            pooled_block st;
+            size_t stb = 0;
+            hipcub::CountingInputIterator<unsigned> every_slot(0u);
+            /* the count is known: d_count is only written again */
+            HIP_RET(hipcub::DeviceSelect::Flagged(
+                NULL, stb, every_slot, flag.as<unsigned char>(),
+                idx.as<unsigned>(), count.as<unsigned long long>(),
+                (int)s.slots, 0));
+            HIP_RET(st.alloc(stb ? stb : 16));
+            hipError_t e1 = hipcub::DeviceSelect::Flagged(
+                st.p, stb, every_slot, flag.as<unsigned char>(),
+                idx.as<unsigned>(), count.as<unsigned long long>(),
+                (int)s.slots, 0);
+            if (e1 == hipSuccess)
+                e1 = hipDeviceSynchronize();
+            st.reset();
+            HIP_RET(e1);
+        }
+        flag.reset(); /* 1 byte per stored slot: not needed any more */
+        hipLaunchKernelGGL(k_keys_from_hll,
+                           dim3((unsigned)((n_sort + 255) / 256)), dim3(256), 0,
+                           0, s.M, s.nb, n_sort, g.tile_rows, g.panels, g.shift,
+                           g.rbits, g.pm_grid, s.col_major, s.off, s.ja, s.as,
+                           idx.p == NULL, idx.as<unsigned>(), key, val);
+    }
+    HIP_RET(hipGetLastError());
+    HIP_RET(hipDeviceSynchronize());
+    return 0;
+}
+
+/* radix sort of the (key, value) pairs over the bits in use
+ * (panel_geometry.end_bit); tmp holds hipCUB's temporaries */
+static int sort_keys(const panel_geometry &g, int64_t n_sort,
+                     pooled_block (&key)[2], pooled_block (&sv)[2],
+                     pooled_block &tmp, uint64_t **skey, double **sval) {
     size_t tmp_bytes = 0;
-    int64_t *raw = NULL, *padded = NULL; /* unpadded bucket starts, scan input */
-    int *span = NULL;                    /* per-tile first / last panel */
-    int64_t n_sort = slots; /* sorted pairs: every CSR entry / every KEPT HLL slot */
-    unsigned char *flag = NULL;
-    unsigned long long *d_count = NULL;
-    int64_t total = 0;
-    double tp[5] = {build_now_s(), 0, 0, 0, 0};
-    g_build_phases[0] = 0;
+    hipcub::DoubleBuffer<uint64_t> dk(key[0].as<uint64_t>(),
+                                      key[1].as<uint64_t>());
+    hipcub::DoubleBuffer<double> dv(sv[0].as<double>(), sv[1].as<double>());
+    HIP_RET(hipcub::DeviceRadixSort::SortPairs(NULL, tmp_bytes, dk, dv,
+                                               (int)n_sort, g.rbits, g.end_bit,
+                                               0));
+    HIP_RET(tmp.alloc(tmp_bytes ? tmp_bytes : 16));
+    HIP_RET(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, dk, dv,
+                                               (int)n_sort, g.rbits, g.end_bit,
+                                               0));
+    HIP_RET(hipDeviceSynchronize());
+    *skey = dk.Current();
+    *sval = dv.Current();
+    return 0;
+}
 
-    rc = long_rows_extract(P, M, nb, irp_or_null, off_or_null, col_major, ja,
-                           as, padmask);
-    if (rc)
-        goto fail;
-    if (!irp_or_null && slots > 0) {
-        /* HLL source: flag the slots that hold entries, count them, compact
-         * their indices (ascending) into idx[0] -- see k_hll_keep_flags */
-        unsigned long long h_count = 0;
-        HIP_TRY(big_malloc((void **)&flag, (size_t)slots));
-        HIP_TRY(hipMalloc((void **)&d_count, sizeof *d_count));
-        HIP_TRY(hipMemset(d_count, 0, sizeof *d_count));
-        hipLaunchKernelGGL(k_hll_keep_flags,
-                           dim3((unsigned)std::min<int64_t>((slots + 255) / 256,
-                                                            8192)),
-                           dim3(256), 0,
-                           0, M, nb, slots, P->long_row, P->nlong, col_major,
-                           off_or_null, padmask, flag, d_count);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpy(&h_count, d_count, sizeof h_count,
+/* bptr / blen of the copy from the sorted keys; raw: unpadded bucket starts,
+ * padded: the scan's input */
+static int bucket_tables(const panel_geometry &g, int64_t n_sort,
+                         const uint64_t *skey, spmv_panels *P, plain_block &raw,
+                         plain_block &padded) {
+    const int64_t buckets = g.nbuckets;
+    const unsigned gb = (unsigned)((buckets + 256) / 256);
+    HIP_RET(raw.alloc(((size_t)buckets + 1) * sizeof(int64_t)));
+    HIP_RET(padded.alloc(((size_t)buckets + 1) * sizeof(int64_t)));
+    HIP_RET(hipMalloc((void **)&P->bptr, ((size_t)buckets + 1) * sizeof(int64_t)));
+    HIP_RET(hipMalloc((void **)&P->blen, ((size_t)buckets + 1) * sizeof(int)));
+    hipLaunchKernelGGL(k_bucket_bounds, dim3(gb), dim3(256), 0, 0, buckets,
+                       n_sort, g.shift + g.rbits, skey, raw.as<int64_t>());
+    hipLaunchKernelGGL(k_bucket_sizes, dim3(gb), dim3(256), 0, 0, buckets,
+                       (int64_t)256, raw.as<int64_t>(), P->blen,
+                       padded.as<int64_t>());
+    HIP_RET(hipGetLastError());
+    plain_block t2;
+    size_t t2b = 0;
+    HIP_RET(hipcub::DeviceScan::ExclusiveSum(NULL, t2b, padded.as<int64_t>(),
+                                             P->bptr, (int)(buckets + 1), 0));
+    HIP_RET(t2.alloc(t2b ? t2b : 16));
+    hipError_t e2 = hipcub::DeviceScan::ExclusiveSum(
+        t2.p, t2b, padded.as<int64_t>(), P->bptr, (int)(buckets + 1), 0);
+    (void)hipDeviceSynchronize();
+    t2.reset();
+    HIP_RET(e2);
+    return 0;
+}
+
+/* compacted per-tile bucket lists of the chain / steps schedules.  A sweep
+ * copy has none (its kernel reads bptr / blen only): cb, cpanel and nbk stay
+ * NULL and panels_launch / the setters refuse to run such a copy in another
+ * schedule. */
+static int compact_lists(const panel_geometry &g, spmv_panels *P,
+                         plain_block &span_block) {
+    const int tiles = g.tiles, panels = g.panels;
+    HIP_RET(hipMalloc((void **)&P->cb,
+                      ((size_t)g.nbuckets + 1) * 2 * sizeof(int64_t)));
+    HIP_RET(hipMalloc((void **)&P->cpanel,
+                      ((size_t)g.nbuckets + 1) * sizeof(int)));
+    HIP_RET(hipMalloc((void **)&P->nbk, ((size_t)tiles + 1) * sizeof(int)));
+    HIP_RET(hipMemset(P->nbk, 0, ((size_t)tiles + 1) * sizeof(int)));
+    if (tiles > 0) {
+        /* span[0] first, [tiles] last, [2 tiles] widest span */
+        HIP_RET(span_block.alloc((2 * (size_t)tiles + 1) * sizeof(int)));
+        int *span = span_block.as<int>();
+        HIP_RET(hipMemset(span + 2 * (size_t)tiles, 0, sizeof(int)));
+        hipLaunchKernelGGL(k_tile_span, dim3((tiles + 255) / 256), dim3(256), 0,
+                           0, tiles, panels, P->blen, span, span + tiles,
+                           span + 2 * (size_t)tiles);
+        HIP_RET(hipGetLastError());
+        HIP_RET(hipMemcpy(&P->span, span + 2 * (size_t)tiles, sizeof(int),
                           hipMemcpyDeviceToHost));
-        n_sort = (int64_t)h_count;
+        /* residue order whenever the tiles do not touch every panel (see
+         * k_compact_buckets; with span == panels it would be the identity);
+         * bucket_order 1 keeps ascending panels */
+        P->residue = P->bucket_order != 1 && P->span > 1 && P->span < panels;
+        hipLaunchKernelGGL(k_compact_buckets, dim3((tiles + 255) / 256),
+                           dim3(256), 0, 0, tiles, panels,
+                           P->residue ? P->span : panels, P->bptr, P->blen, span,
+                           span + tiles, P->cb, P->cpanel, P->nbk);
+        hipLaunchKernelGGL(k_max_int, dim3(64), dim3(256), 0, 0, tiles, P->nbk,
+                           P->nbk + tiles);
+        HIP_RET(hipGetLastError());
     }
-    {
-        const size_t na = (size_t)(n_sort > 0 ? n_sort : 1);
-        for (int k = 0; k < 2; ++k) {
-            HIP_TRY(big_malloc((void **)&key[k], na * sizeof(uint64_t)));
-            HIP_TRY(big_malloc((void **)&sv[k], na * sizeof(double)));
-        }
-        if (!irp_or_null && n_sort != slots)
-            HIP_TRY(big_malloc((void **)&idx, na * sizeof(unsigned)));
-    }
-    skey = key[0];
-    sval = sv[0];
-    if (slots > 0) {
-        if (irp_or_null) {
-            hipLaunchKernelGGL(k_keys_from_csr,
-                               dim3((unsigned)std::min<long long>(
-                                   ((long long)M * 8 + 255) / 256, 1 << 23)),
-                               dim3(256), 0, 0, M, (int)tr, panels, shift,
-                               rbits, pm_grid, (uint64_t)nbuckets, P->long_row,
-                               P->nlong, irp_or_null, ja, as, key[0], sv[0]);
-        } else if (n_sort > 0) {
-            const int identity = n_sort == slots; /* the format padded nothing */
-            if (!identity) {
-                void *st = NULL;
-                size_t stb = 0;
-                hipcub::CountingInputIterator<unsigned> every_slot(0u);
-                /* the count is known: d_count is only written again */
-                HIP_TRY(hipcub::DeviceSelect::Flagged(st, stb, every_slot, flag,
-                                                      idx, d_count,
-                                                      (int)slots, 0));
-                HIP_TRY(big_malloc(&st, stb ? stb : 16));
-                hipError_t e1 = hipcub::DeviceSelect::Flagged(
-                    st, stb, every_slot, flag, idx, d_count, (int)slots, 0);
-                if (e1 == hipSuccess)
-                    e1 = hipDeviceSynchronize();
-                big_free(st);
-                HIP_TRY(e1);
-            }
-            big_free(flag); /* 1 byte per stored slot: not needed any more */
-            flag = NULL;
-            hipLaunchKernelGGL(k_keys_from_hll,
-                               dim3((unsigned)((n_sort + 255) / 256)), dim3(256),
-                               0, 0, M, nb, n_sort, (int)tr, panels, shift,
-                               rbits, pm_grid, col_major, off_or_null, ja, as,
-                               identity, idx, key[0], sv[0]);
-        }
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipDeviceSynchronize());
-        tp[1] = build_now_s();
-        {
-            big_free(idx); /* the keys are built: the list is not needed */
-            idx = NULL;
-            hipcub::DoubleBuffer<uint64_t> dk(key[0], key[1]);
-            hipcub::DoubleBuffer<double> dv(sv[0], sv[1]);
-            /* sort only the bits in use: bucket ids up to tiles*panels (the
-             * id of dropped slots) above `shift` column bits; the row field
-             * below them rides along unsorted (entry_key) */
-            const int kb = shift + rbits;
-            int end_bit = kb + 1;
-            while (end_bit < 64 && (((uint64_t)nbuckets) >> (end_bit - kb)))
-                ++end_bit;
-            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(
-                NULL, tmp_bytes, dk, dv, (int)n_sort, rbits, end_bit, 0));
-            HIP_TRY(big_malloc(&tmp, tmp_bytes ? tmp_bytes : 16));
-            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(
-                tmp, tmp_bytes, dk, dv, (int)n_sort, rbits, end_bit, 0));
-            HIP_TRY(hipDeviceSynchronize());
-            skey = dk.Current();
-            sval = dv.Current();
-        }
-    }
-    tp[2] = build_now_s();
-    {
-        const int64_t buckets = nbuckets;
-        const unsigned gb = (unsigned)((buckets + 256) / 256);
-        HIP_TRY(hipMalloc((void **)&raw, ((size_t)buckets + 1) * sizeof(int64_t)));
-        HIP_TRY(hipMalloc((void **)&padded,
-                          ((size_t)buckets + 1) * sizeof(int64_t)));
-        HIP_TRY(hipMalloc((void **)&P->bptr,
-                          ((size_t)buckets + 1) * sizeof(int64_t)));
-        HIP_TRY(hipMalloc((void **)&P->blen, ((size_t)buckets + 1) * sizeof(int)));
-        hipLaunchKernelGGL(k_bucket_bounds, dim3(gb), dim3(256), 0, 0, buckets,
-                           n_sort, shift + rbits, skey, raw);
-        hipLaunchKernelGGL(k_bucket_sizes, dim3(gb), dim3(256), 0, 0, buckets,
-                           (int64_t)256, raw, P->blen, padded);
-        HIP_TRY(hipGetLastError());
-        {
-            void *t2 = NULL;
-            size_t t2b = 0;
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(t2, t2b, padded, P->bptr,
-                                                     (int)(buckets + 1), 0));
-            HIP_TRY(hipMalloc(&t2, t2b ? t2b : 16));
-            hipError_t e2 = hipcub::DeviceScan::ExclusiveSum(
-                t2, t2b, padded, P->bptr, (int)(buckets + 1), 0);
-            (void)hipDeviceSynchronize();
-            (void)hipFree(t2);
-            HIP_TRY(e2);
-        }
-        /* compacted per-tile bucket lists of the chain / steps schedules.
-         * A sweep copy has none (its kernel reads bptr / blen only): cb,
-         * cpanel and nbk stay NULL and panels_launch / the setters refuse to
-         * run such a copy in another schedule. */
-        if (!sweep) {
-            HIP_TRY(hipMalloc((void **)&P->cb,
-                              ((size_t)buckets + 1) * 2 * sizeof(int64_t)));
-            HIP_TRY(hipMalloc((void **)&P->cpanel,
-                              ((size_t)buckets + 1) * sizeof(int)));
-            HIP_TRY(hipMalloc((void **)&P->nbk,
-                              ((size_t)tiles + 1) * sizeof(int)));
-            HIP_TRY(hipMemset(P->nbk, 0, ((size_t)tiles + 1) * sizeof(int)));
-            if (tiles > 0) {
-                /* span[0] first, [tiles] last, [2 tiles] widest span */
-                HIP_TRY(hipMalloc((void **)&span,
-                                  (2 * (size_t)tiles + 1) * sizeof(int)));
-                HIP_TRY(hipMemset(span + 2 * (size_t)tiles, 0, sizeof(int)));
-                hipLaunchKernelGGL(k_tile_span, dim3((tiles + 255) / 256),
-                                   dim3(256), 0, 0, tiles, panels, P->blen,
-                                   span, span + tiles, span + 2 * (size_t)tiles);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipMemcpy(&P->span, span + 2 * (size_t)tiles,
-                                  sizeof(int), hipMemcpyDeviceToHost));
-                /* residue order whenever the tiles do not touch every panel
-                 * (see k_compact_buckets; with span == panels it would be the
-                 * identity); bucket_order 1 keeps ascending panels */
-                P->residue = o->bucket_order != 1 && P->span > 1 &&
-                             P->span < panels;
-                hipLaunchKernelGGL(k_compact_buckets, dim3((tiles + 255) / 256),
-                                   dim3(256), 0, 0, tiles, panels,
-                                   P->residue ? P->span : panels, P->bptr,
-                                   P->blen, span, span + tiles, P->cb,
-                                   P->cpanel, P->nbk);
-                hipLaunchKernelGGL(k_max_int, dim3(64), dim3(256), 0, 0, tiles,
-                                   P->nbk, P->nbk + tiles);
-                HIP_TRY(hipGetLastError());
-            }
-            HIP_TRY(hipMemcpy(&P->max_nbk, P->nbk + tiles, sizeof(int),
-                              hipMemcpyDeviceToHost));
-        }
-        /* dropped slots sort behind the last bucket */
-        HIP_TRY(hipMemcpy(&P->nnz, raw + buckets, sizeof(int64_t),
-                          hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(&total, P->bptr + buckets, sizeof total,
-                          hipMemcpyDeviceToHost));
-    }
+    HIP_RET(hipMemcpy(&P->max_nbk, P->nbk + tiles, sizeof(int),
+                      hipMemcpyDeviceToHost));
+    return 0;
+}
+
+/* entries kept (dropped slots sort behind the last bucket) and slots of the
+ * copy, bucket padding included */
+static int bucket_totals(const panel_geometry &g, const int64_t *raw,
+                         spmv_panels *P) {
+    HIP_RET(hipMemcpy(&P->nnz, raw + g.nbuckets, sizeof(int64_t),
+                      hipMemcpyDeviceToHost));
+    HIP_RET(hipMemcpy(&P->total, P->bptr + g.nbuckets, sizeof(int64_t),
+                      hipMemcpyDeviceToHost));
     /* The kernels index the copy's slots with UNSIGNED 32 bits (fk / fe /
      * blk, `fk + CH >= fe`): room for every matrix the API can describe
      * (INT32_MAX entries) plus its bucket padding, as long as `slot + chunk`
      * cannot wrap -- 3e9 leaves 1.29e9 of head room for a chunk of 16 Ki. */
-    if (total + SWEEP_TAIL > (int64_t)3000000000LL) {
-        rc = -EOVERFLOW;
-        goto fail;
-    }
-    P->total = total;
-    tp[3] = build_now_s();
-    {
-        const size_t m = (size_t)total + SWEEP_TAIL; /* zeros behind the data */
-        HIP_TRY(big_malloc((void **)&P->ent, m * sizeof(unsigned)));
-        HIP_TRY(big_malloc((void **)&P->val, m * sizeof(double)));
-        HIP_TRY(hipMemset(P->ent, 0, m * sizeof(unsigned)));
-        HIP_TRY(hipMemset(P->val, 0, m * sizeof(double)));
-    }
+    return P->total + SWEEP_TAIL > (int64_t)3000000000LL ? -EOVERFLOW : 0;
+}
+
+/* the copy itself: the sorted pairs streamed to their padded places */
+static int place_entries(const panel_geometry &g, const uint64_t *skey,
+                         const double *sval, const int64_t *raw,
+                         spmv_panels *P) {
+    const size_t m = (size_t)P->total + SWEEP_TAIL; /* zeros behind the data */
+    HIP_RET(big_malloc((void **)&P->ent, m * sizeof(unsigned)));
+    HIP_RET(big_malloc((void **)&P->val, m * sizeof(double)));
+    HIP_RET(hipMemset(P->ent, 0, m * sizeof(unsigned)));
+    HIP_RET(hipMemset(P->val, 0, m * sizeof(double)));
     if (P->nnz > 0) {
-        const unsigned g = (unsigned)((P->nnz + 255) / 256);
-        hipLaunchKernelGGL(k_place, dim3(g), dim3(256), 0, 0, P->nnz, shift,
-                           rbits, skey, sval, raw, P->bptr, P->ent, P->val);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipDeviceSynchronize());
+        const unsigned grid = (unsigned)((P->nnz + 255) / 256);
+        hipLaunchKernelGGL(k_place, dim3(grid), dim3(256), 0, 0, P->nnz, g.shift,
+                           g.rbits, skey, sval, raw, P->bptr, P->ent, P->val);
+        HIP_RET(hipGetLastError());
+        HIP_RET(hipDeviceSynchronize());
     }
-    if (!sweep) {
-        rc = balance_xcd_ranges(P);
+    return 0;
+}
+
+/* sweep: the per-XCD arrival counters of every (round, panel) */
+static int alloc_phase_counters(const panel_geometry &g, spmv_panels *P) {
+    const size_t rounds = ((size_t)g.tiles + g.grid - 1) / g.grid;
+    P->phase_cnt_bytes = NUM_XCD * (rounds ? rounds : 1) * (size_t)g.panels *
+                         CNT_STRIDE * sizeof(int);
+    HIP_RET(hipMalloc((void **)&P->phase_cnt, P->phase_cnt_bytes));
+    return 0;
+}
+
+/* the scratch of one build.  Blocks go back to the pool of a selector run
+ * in this order, which is the order the next build finds them in */
+struct build_scratch {
+    pooled_block key[2], sv[2]; /* the sort's double buffers: keys, values */
+    pooled_block idx;           /* HLL source with pads: kept slots */
+    pooled_block tmp;           /* the sort's temporaries */
+    pooled_block flag;          /* HLL source: 1 = the slot holds an entry */
+    plain_block count;          /* ... and how many do */
+    plain_block raw, padded;    /* unpadded bucket starts, scan input */
+    plain_block span;           /* per-tile first / last panel */
+    ~build_scratch() {
+        for (int k = 0; k < 2; ++k) {
+            key[k].reset();
+            sv[k].reset();
+        }
+        idx.reset();
+        tmp.reset();
+        flag.reset();
+        count.reset();
+        raw.reset();
+        padded.reset();
+        span.reset();
+    }
+};
+
+/* fills the copy P, whose geometry is set, from the source; P stays the
+ * caller's to free */
+static int build_stages(const panel_geometry &g, const build_src &s,
+                        spmv_panels *P) {
+    int rc;
+    build_scratch b;
+    const bool hll = !s.irp;
+    int64_t n_sort = s.slots; /* sorted pairs: every CSR entry / every KEPT HLL slot */
+    uint64_t *skey;
+    double *sval;
+    double tp[5] = {build_now_s(), 0, 0, 0, 0};
+
+    if ((rc = long_rows_extract(P, s)))
+        return rc;
+    if (hll && s.slots > 0 &&
+        (rc = hll_flag_kept(s, P, b.flag, b.count, &n_sort)))
+        return rc;
+    if ((rc = alloc_sort_buffers(n_sort, hll && n_sort != s.slots, b.key, b.sv,
+                                 b.idx)))
+        return rc;
+    skey = b.key[0].as<uint64_t>();
+    sval = b.sv[0].as<double>();
+    if (s.slots > 0) {
+        rc = hll ? keys_from_hll(g, s, n_sort, b.flag, b.count, b.idx, skey, sval)
+                 : keys_from_csr(g, s, P, skey, sval);
         if (rc)
-            goto fail;
+            return rc;
+        tp[1] = build_now_s();
+        b.idx.reset(); /* the keys are built: the list is not needed */
+        if ((rc = sort_keys(g, n_sort, b.key, b.sv, b.tmp, &skey, &sval)))
+            return rc;
     }
-    if (sweep) {
-        const size_t rounds = ((size_t)tiles + P->grid - 1) / P->grid;
-        P->phase_cnt_bytes = NUM_XCD * (rounds ? rounds : 1) * (size_t)panels *
-                             CNT_STRIDE * sizeof(int);
-        HIP_TRY(hipMalloc((void **)&P->phase_cnt, P->phase_cnt_bytes));
-    }
+    tp[2] = build_now_s();
+    if ((rc = bucket_tables(g, n_sort, skey, P, b.raw, b.padded)))
+        return rc;
+    if (!g.sweep && (rc = compact_lists(g, P, b.span)))
+        return rc;
+    if ((rc = bucket_totals(g, b.raw.as<int64_t>(), P)))
+        return rc;
+    tp[3] = build_now_s();
+    if ((rc = place_entries(g, skey, sval, b.raw.as<int64_t>(), P)))
+        return rc;
+    if ((rc = g.sweep ? alloc_phase_counters(g, P) : balance_xcd_ranges(P)))
+        return rc;
     tp[4] = build_now_s();
     snprintf(g_build_phases, sizeof g_build_phases,
              "%lld of %lld slots sorted: alloc+keys %.3f s, sort %.3f, bucket "
              "tables %.3f, place %.3f",
-             (long long)n_sort, (long long)slots, tp[1] > 0 ? tp[1] - tp[0] : 0.0,
-             tp[1] > 0 ? tp[2] - tp[1] : 0.0, tp[3] - tp[2], tp[4] - tp[3]);
-    *out = P;
-    P = NULL;
-fail:
-    for (int k = 0; k < 2; ++k) {
-        big_free(key[k]);
-        big_free(sv[k]);
+             (long long)n_sort, (long long)s.slots,
+             tp[1] > 0 ? tp[1] - tp[0] : 0.0, tp[1] > 0 ? tp[2] - tp[1] : 0.0,
+             tp[3] - tp[2], tp[4] - tp[3]);
+    return 0;
+}
+
+static int panels_build(int N, const build_src &s, const spmv_panel_opts *o,
+                        spmv_panels **out) {
+    *out = NULL;
+    spmv_panel_opts dflt;
+    spmv_panel_opts_default(&dflt);
+    if (!o)
+        o = &dflt;
+    long long tall_rows = 0;
+#ifdef SPMV_ABLATIONS
+    /* round-6 probe (tools/tall_tile_probe.py): a sweep copy with tiles
+     * TALLER than a CU's LDS can hold, launched with variant ablation 5 / 6
+     * (LDS index aliased, y WRONG by design): the L2 request pattern of
+     * accumulators that do not exist yet */
+    if (const char *e = getenv("SPMV_ABL_SWEEP_TILE_ROWS")) {
+        const long long v = atoll(e) / 32 * 32;
+        if (v >= 32 && v < (1 << 20))
+            tall_rows = v;
     }
-    big_free(idx);
-    big_free(tmp);
-    big_free(flag);
-    (void)hipFree(d_count);
-    (void)hipFree(raw);
-    (void)hipFree(padded);
-    (void)hipFree(span);
-    panels_free(P);
-    return rc;
+#endif
+    panel_geometry g;
+    int rc = panel_build_plan(s.M, N, s.slots, *o,
+                              g_panel_sched.load(std::memory_order_relaxed),
+                              device_cus, tall_rows, &g);
+    if (rc)
+        return rc;
+    spmv_panels *P = (spmv_panels *)calloc(1, sizeof *P);
+    if (!P)
+        return -ENOMEM;
+    P->N = N;
+    P->shift = g.shift;
+    P->panels = g.panels;
+    P->tile_rows = g.tile_rows;
+    P->tiles = g.tiles;
+    P->sweep = g.sweep;
+    P->chain = g.chain;
+    P->grid = g.grid;
+    P->wgs_per_cu = g.wgs_per_cu;
+    P->reserve_cus = g.reserve_cus;
+    P->pmajor = g.pmajor;
+    P->lds_min = o->lds_min;
+    P->bucket_order = o->bucket_order;
+    P->det = g.det;
+    P->order = g.order;
+    g_build_phases[0] = 0;
+    rc = build_stages(g, s, P);
+    if (rc) {
+        panels_free(P);
+        return rc;
+    }
+    *out = P;
+    return 0;
 }
 
 /* ------------------------------------------------------------------ */
@@ -2026,8 +1975,8 @@ static int panels_launch_tiles(const spmv_panels *P, int M, int waves,
  * default, up to 16384) */
 int panels_from_csr_opts(const spmv_csr_dev *A, const spmv_panel_opts *o,
                          spmv_panels **out) {
-    return panels_build(A->M, A->N, A->NZ, o, 0, A->irp, NULL, 0, A->ja, A->as,
-                        NULL, out);
+    const build_src s = {A->M, 0, A->NZ, A->irp, NULL, 0, A->ja, A->as, NULL};
+    return panels_build(A->N, s, o, out);
 }
 
 int panels_from_hll_opts(const spmv_hll_dev *H, const spmv_panel_opts *o,
@@ -2036,8 +1985,9 @@ int panels_from_hll_opts(const spmv_hll_dev *H, const spmv_panel_opts *o,
         return -ENOTSUP; /* compact handle: neither 4-byte columns nor padmask */
     if (H->slots > 0 && !H->padmask)
         return -ENODATA;
-    return panels_build(H->M, H->N, H->slots, o, H->nb, NULL, H->off,
-                        H->col_major, H->ja, H->as, H->padmask, out);
+    const build_src s = {H->M,  H->nb, H->slots, NULL,      H->off,
+                         H->col_major, H->ja, H->as, H->padmask};
+    return panels_build(H->N, s, o, out);
 }
 
 extern "C" void spmv_panel_opts_default(spmv_panel_opts *o) {

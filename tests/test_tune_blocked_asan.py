@@ -81,3 +81,33 @@ def test_panel_launch_plans_under_asan(tmp_path):
     assert r.returncode == 0, r.stdout + r.stderr
     assert "every plan names an instantiated kernel" in r.stdout
     assert "FAILED" not in r.stdout and "ERROR" not in r.stderr
+
+
+def test_panel_build_geometry_under_asan(tmp_path):
+    """the host arithmetic of a blocked build (panel_build.h: schedule, tile
+    height, row / column bit split, panels, tiles, grid, bucket numbering,
+    the sort's bits and the overflow guards per (M, N, slots, options, CUs);
+    the segments of the long rows; the XCDs' tile ranges): a table of
+    geometries written out from the panels_build() the header was lifted
+    from, invariants over 4000 seeded random inputs"""
+    exe = str(tmp_path / "panel_build_asan")
+    # the constants the library is compiled with (hip_common.h)
+    import re
+    hdr = open(os.path.join(ROOT, "spmv_scpa_amd", "csrc", "hip_common.h")).read()
+    defs = []
+    for name in ("NUM_XCD", "SPMV_VARIANT_TIMING_BITS"):
+        m = re.search(r"#define\s+%s\s+(\d+|\([^)]*\))" % name, hdr)
+        assert m, name
+        defs.append("-D%s=%s" % (name, m.group(1)))
+    subprocess.run(
+        ["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined",
+         "-fno-omit-frame-pointer", "-fno-sanitize-recover=all"] + defs +
+        ["-I", os.path.join(ROOT, "spmv_scpa_amd", "csrc"),
+         "-I", os.path.join(ROOT, "include"),
+         os.path.join(ROOT, "tests", "asan", "panel_build_asan.cc"),
+         "-o", exe], check=True)
+    r = subprocess.run([exe, "4000"], capture_output=True, text=True)
+    sys.stdout.write(r.stdout)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "expected geometries reproduced" in r.stdout
+    assert "FAILED" not in r.stdout and "ERROR" not in r.stderr
