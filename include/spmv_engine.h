@@ -344,7 +344,8 @@ int spmv_hll_value_bytes(const spmv_hll_dev *H); /* 8 or 4 */
  * / _kernel_bytes ((2 + value_bytes) S + 4 nb for the bases + 12 nb + 8 M +
  * 8 N), release / release_checked.  spmv_hll_build_panels*,
  * spmv_hll_launch_multi, spmv_hll_multi_bytes, spmv_hll_launch_axpby,
- * spmv_hll_axpby_bytes and spmv_hll_cg: -ENOTSUP.  The handle owns
+ * spmv_hll_axpby_bytes, spmv_hll_cg, spmv_hll_pcg and spmv_hll_diag:
+ * -ENOTSUP.  The handle owns
  * no 4-byte JA and no pad bitmap.  The one-shot seam, the reference ABI names
  * and spmv_mgpu.h create 4-byte handles only.
  */
@@ -508,7 +509,7 @@ int64_t spmv_hll_axpby_bytes(const spmv_hll_dev *H, int k, int reads_y);
  * X, B: k = 1..8 interleaved vectors as in spmv_*_launch_multi; the k systems
  * are independent: each column has its own scalars, its own convergence and
  * its own status, and one launch_multi per iteration serves them all.  No
- * preconditioner.
+ * preconditioner here: spmv_*_pcg below takes a diagonal one.
  *
  * d_X holds the initial guess on entry and the iterate on return; d_B is not
  * written.  ldb, ldx >= k (0 = k); only columns 0..k-1 of rows 0..M-1 of X
@@ -584,6 +585,86 @@ int spmv_hll_cg(const spmv_hll_dev *H, const spmv_launch_opts *opts, int k,
                 double tol, int maxit, int check_every,
                 void *d_work, size_t work_bytes,
                 spmv_cg_info *info, void *stream);
+
+/*
+ * The diagonal of a handle (added after 0.7; detect it by the symbol).
+ * d_out[r], r < min(M, N), is the fp64 sum of the stored entries of row r
+ * whose column is r: the sum starts from 0.0, an f32 handle widens each value
+ * first.  A row that stores no diagonal entry gives 0.0; a row that stores it
+ * once gives that value exactly; a row that stores it more than once gives a
+ * sum whose order is fixed for the handle and does not depend on the launch
+ * (which order is not specified).  HLL pads carry the value 0.0 and v + 0.0
+ * keeps the bits of v, so a column-major HLL handle gives the bits of the CSR
+ * handle it was made from.  invert != 0 stores rn(1.0 / d) instead -- one
+ * correctly rounded division, inf for a zero diagonal: the Jacobi
+ * preconditioner spmv_*_pcg takes.  Only d_out[0 .. min(M, N)) is written.
+ * Asynchronous on `stream`, capturable.
+ *
+ * The handle is checked by the function that serves launch_multi, launch_axpby
+ * and cg, with the same answers: dead handle -EBADF / -ENODEV, compact handle
+ * -ENOTSUP, row-major HLL -EINVAL, after spmv_*_release_source() -ENODATA.
+ * NULL d_out: -EINVAL.  M == 0: returns 0.
+ */
+int spmv_csr_diag(const spmv_csr_dev *A, double *d_out, int invert,
+                  void *stream);
+int spmv_hll_diag(const spmv_hll_dev *H, double *d_out, int invert,
+                  void *stream);
+
+/*
+ * Preconditioned conjugate gradients with a diagonal preconditioner (added
+ * after 0.7; detect it by the symbol): spmv_*_cg with z = M^-1 r applied as
+ * z_i = minv_i * r_i.  d_minv: M doubles, one per row, shared by the k columns,
+ * never written.  Any positive vector is allowed; spmv_*_diag(invert = 1)
+ * gives Jacobi.
+ *
+ * d_X, d_B, the strides, d_work (spmv_pcg_work_bytes(M, k) bytes: the state,
+ * three sets of partial sums, R, P and Q), the blocking, -EBUSY on a capturing
+ * stream, check_every, maxit, M == 0 and the argument checks are those of
+ * spmv_*_cg above, word for word.  One check is added: NULL d_minv, -EINVAL.
+ *
+ * Result contract, to the bit.  Every operation is rounded once, no fused
+ * multiply-add; dot is the dot of spmv_cg_dot_shape; z(R) is the vector with
+ * z_i = rn(minv_i * r_i) in every column.
+ *
+ *   R = B;  R = (-1) A X + 1 R  by launch_axpby;  P = z(R)
+ *   bb = dot(B, B);  rr = dot(R, R);  rz = dot(R, z(R))
+ *   column j: status 2 (iterations 0) if rr, bb or rz is not finite,
+ *             else converged (iterations 0) if rr <= tol2 * bb,
+ *             else status 2 if not rz > 0,  else running
+ *   repeat at most maxit times:
+ *       Q = A P  by launch_multi;  pq = dot(P, Q)
+ *       running column with !(pq > 0 and finite): status 2, frozen
+ *       running column: alpha = rz / pq;  X = X + alpha * P;
+ *                       R = R - alpha * Q;  iterations += 1
+ *       rn = dot(R, R);  zn = dot(R, z(R))          (the updated R)
+ *       running column: rn <= tol2 * bb -> status 0, frozen (rr = rn)
+ *                       rn not finite or !(zn > 0 and finite)
+ *                                       -> status 2, frozen
+ *       running column: beta = zn / rz;  P = z(R) + beta * P;
+ *                       rr = rn;  rz = zn
+ *   columns still running: status 1
+ *
+ * Frozen columns are never written again, exactly as in spmv_*_cg: X, the
+ * iteration counts, the statuses and rr do not depend on check_every, on the
+ * owner of the work buffer, on waves_per_block, or on the other columns.
+ * minv of all 1.0 gives z(R) = R and rz = rr, every test above reduces to
+ * cg's, and the call returns the bits of spmv_*_cg on the same handle (X,
+ * status, iterations, rr, bb): a property of the contract, not a special
+ * case.  Z is never stored: z(R) is recomputed in the kernels that use it.
+ */
+int64_t spmv_pcg_work_bytes(int M, int k); /* -EINVAL: M < 0, k outside 1..8 */
+int spmv_csr_pcg(const spmv_csr_dev *A, const spmv_launch_opts *opts, int k,
+                 const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                 const double *d_minv,
+                 double tol, int maxit, int check_every,
+                 void *d_work, size_t work_bytes,
+                 spmv_cg_info *info, void *stream);
+int spmv_hll_pcg(const spmv_hll_dev *H, const spmv_launch_opts *opts, int k,
+                 const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                 const double *d_minv,
+                 double tol, int maxit, int check_every,
+                 void *d_work, size_t work_bytes,
+                 spmv_cg_info *info, void *stream);
 
 /*
  * Pick the fastest kernel for this matrix by measurement (5 launches each):

@@ -548,6 +548,7 @@ _sig("spmv_hll_shape", C.c_int, C.c_void_p, _ip, _ip, C.POINTER(C.c_int64),
 _sig("spmv_hll_kernel_bytes", C.c_int64, C.c_void_p, C.c_int)
 _sig("spmv_cg_work_bytes", C.c_int64, C.c_int, C.c_int)
 _sig("spmv_cg_dot_shape", None, _ip, _ip)
+_sig("spmv_pcg_work_bytes", C.c_int64, C.c_int, C.c_int)
 # spmv_csr_<name> and spmv_hll_<name>: the same argument types
 _TWINS = (
     ("release_checked", None, C.c_void_p, C.c_uint64),
@@ -585,6 +586,11 @@ _TWINS = (
      C.c_void_p, C.POINTER(LaunchOpts), C.c_int, C.c_void_p, C.c_int64,
      C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_int, C.c_void_p,
      C.c_size_t, C.POINTER(CgInfo), C.c_void_p),
+    ("pcg", C.c_int,
+     C.c_void_p, C.POINTER(LaunchOpts), C.c_int, C.c_void_p, C.c_int64,
+     C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_int, C.c_int,
+     C.c_void_p, C.c_size_t, C.POINTER(CgInfo), C.c_void_p),
+    ("diag", C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p),
     ("time", C.c_int,
      C.c_void_p, C.c_int, C.POINTER(LaunchOpts), C.c_void_p, C.c_void_p,
      C.c_int, C.c_int, C.c_size_t, _dp, C.c_void_p),
@@ -668,6 +674,13 @@ def cg_work_bytes(M, k):
     (what `work` must hold at least)"""
     return _check(_lib.spmv_cg_work_bytes(int(M), int(k)),
                   "spmv_cg_work_bytes")
+
+
+def pcg_work_bytes(M, k):
+    """bytes of device memory one pcg() solve of k systems with M rows needs:
+    cg_work_bytes and one more set of partial sums"""
+    return _check(_lib.spmv_pcg_work_bytes(int(M), int(k)),
+                  "spmv_pcg_work_bytes")
 
 
 def version():
@@ -1390,6 +1403,35 @@ class _Device:
                    work.ptr if work is not None else None,
                    work.nbytes if work is not None else 0, info, stream)
         return [CgResult(i.status, i.iterations, i.rr, i.bb) for i in info]
+
+    def pcg(self, d_B, d_X, d_minv, k=1, tol=1e-8, maxit=1000, check_every=0,
+            ldb=0, ldx=0, work=None, waves_per_block=0, group=0, stream=None):
+        """cg() preconditioned with z_i = minv_i * r_i: d_minv holds M
+        doubles, one per row, shared by the k columns and never written.  Any
+        positive vector; diag(d_minv, invert=True) gives Jacobi.  Everything
+        else as cg() (`work`: at least pcg_work_bytes(M, k) bytes); a vector
+        of ones returns the bits of cg().  A column whose r.z is not positive
+        is a breakdown.  -> [CgResult(status, iterations, rr, bb)] * k"""
+        k, ldb, ldx = int(k), int(ldb), int(ldx)
+        if not 1 <= k <= 8:
+            raise ValueError("k=%r: 1..8 systems per solve" % (k,))
+        if (ldb and ldb < k) or (ldx and ldx < k):
+            raise ValueError("ldb=%d, ldx=%d: at least k=%d (or 0)"
+                             % (ldb, ldx, k))
+        o = _opts(waves_per_block, group if self._FMT == "csr" else 0)
+        info = (CgInfo * k)()
+        self._call("pcg", C.byref(o), k, d_B, ldb, d_X, ldx, d_minv,
+                   float(tol), int(maxit), int(check_every),
+                   work.ptr if work is not None else None,
+                   work.nbytes if work is not None else 0, info, stream)
+        return [CgResult(i.status, i.iterations, i.rr, i.bb) for i in info]
+
+    def diag(self, d_out, invert=False, stream=None):
+        """d_out[r] = the fp64 sum of the stored entries of row r in column
+        r, for r < min(M, N) (0.0 where the row stores none); invert=True
+        stores 1.0 / that sum instead (inf for a zero diagonal): the Jacobi
+        preconditioner of pcg().  Asynchronous on `stream`, capturable."""
+        self._call("diag", d_out, int(bool(invert)), stream)
 
     def build_panels(self, panel_cols=0, sched=None, tile_rows=0,
                      sweep_wgs_per_cu=0, reserve_cus=0, lds_min=0,

@@ -1809,6 +1809,49 @@ static int cg(const D *d, const spmv_launch_opts *opts, int k,
                     (hipStream_t)stream);
 }
 
+/* ... preconditioned: cg's checks and one more pointer */
+template <typename D>
+static int pcg(const D *d, const spmv_launch_opts *opts, int k,
+               const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+               const double *d_minv, double tol, int maxit, int check_every,
+               void *d_work, size_t work_bytes, spmv_cg_info *info,
+               void *stream) {
+    const int rc = multi_check(d, opts, k, d_B, &ldb, d_X, &ldx);
+    if (rc < 0)
+        return rc;
+    if (d->M != d->N || !(tol >= 0.0) || maxit < 0 || check_every < 0 ||
+        !info || !d_minv)
+        return -EINVAL;
+    if (rc) { /* no rows */
+        for (int j = 0; j < k; ++j)
+            info[j] = spmv_cg_info{0, 0, 0.0, 0.0};
+        return 0;
+    }
+    const cg_matrix A = {d, opts, d->M, cg_multi_of<D>, cg_axpby_of<D>};
+    return pcg_solve(&A, k, d_B, ldb, d_X, ldx, d_minv, tol, maxit,
+                     check_every ? check_every : 8, d_work, work_bytes, info,
+                     (hipStream_t)stream);
+}
+
+/* ---- the diagonal (diag_kernels.hip): launch_multi's handle checks ---- */
+static int diag_direct(const spmv_csr_dev *A, double *out, int invert,
+                       hipStream_t s) {
+    return csr_diag(A, out, invert, s);
+}
+static int diag_direct(const spmv_hll_dev *H, double *out, int invert,
+                       hipStream_t s) {
+    return hll_diag(H, out, invert, s);
+}
+template <typename D>
+static int diag(const D *d, double *d_out, int invert, void *stream) {
+    int64_t ldx = 1, ldy = 1; /* one vector; d_out stands for both pointers */
+    const int rc = multi_check(d, (const spmv_launch_opts *)NULL, 1, d_out, &ldx,
+                               d_out, &ldy);
+    if (rc)
+        return rc < 0 ? rc : 0;
+    return diag_direct(d, d_out, invert, (hipStream_t)stream);
+}
+
 /* a new blocked copy in place of the old one: `build(&d->panels)` */
 template <typename D, typename Build> static int rebuild(D *d, Build build) {
     if (d->value_bytes == 4)
@@ -2378,6 +2421,19 @@ static int copy_tune_log(const D *d, char *buf, size_t len) {
         return cg(d, opts, k, d_B, ldb, d_X, ldx, tol, maxit, check_every,     \
                   d_work, work_bytes, info, stream);                           \
     }                                                                          \
+    int spmv_##fmt##_pcg(const D *d, const spmv_launch_opts *opts, int k,      \
+                         const double *d_B, int64_t ldb, double *d_X,          \
+                         int64_t ldx, const double *d_minv, double tol,        \
+                         int maxit, int check_every, void *d_work,             \
+                         size_t work_bytes, spmv_cg_info *info,                \
+                         void *stream) {                                       \
+        return pcg(d, opts, k, d_B, ldb, d_X, ldx, d_minv, tol, maxit,         \
+                   check_every, d_work, work_bytes, info, stream);             \
+    }                                                                          \
+    int spmv_##fmt##_diag(const D *d, double *d_out, int invert,               \
+                          void *stream) {                                      \
+        return diag(d, d_out, invert, stream);                                 \
+    }                                                                          \
     int spmv_##fmt##_time(const D *d, int kernel,                              \
                           const spmv_launch_opts *opts, const double *d_x,     \
                           double *d_y, int warmup, int iters,                  \
@@ -2435,6 +2491,7 @@ HANDLE_API(csr, spmv_csr_dev, launch_rows)
 HANDLE_API(hll, spmv_hll_dev, launch_blocks)
 
 int64_t spmv_cg_work_bytes(int M, int k) { return cg_work_bytes(M, k); }
+int64_t spmv_pcg_work_bytes(int M, int k) { return pcg_work_bytes(M, k); }
 void spmv_cg_dot_shape(int *workgroups, int *threads) {
     if (workgroups)
         *workgroups = CG_NWG;

@@ -1,7 +1,7 @@
 /*
  * hip_common.h -- internals shared by the HIP translation units
  * (engine.hip, csr_kernels.hip, hll_kernels.hip, multi_kernels.hip,
- * cg_kernels.hip, panels.hip, mgpu.hip, and mat_ref.h on behalf of the first and the last).
+ * cg_kernels.hip, diag_kernels.hip, panels.hip, mgpu.hip, and mat_ref.h on behalf of the first and the last).
  * Not installed.
  */
 #ifndef SPMV_HIP_COMMON_H
@@ -532,6 +532,19 @@ int64_t cg_work_bytes(int M, int k);
 int cg_solve(const cg_matrix *A, int k, const double *B, int64_t ldb, double *X,
              int64_t ldx, double tol, int maxit, int check_every, void *d_work,
              size_t work_bytes, spmv_cg_info *info, hipStream_t s);
+/* ... preconditioned with z = minv .* r, minv[M] (spmv_*_pcg): the same loop,
+ * one more set of partial sums in the work buffer */
+int64_t pcg_work_bytes(int M, int k);
+int pcg_solve(const cg_matrix *A, int k, const double *B, int64_t ldb,
+              double *X, int64_t ldx, const double *minv, double tol, int maxit,
+              int check_every, void *d_work, size_t work_bytes,
+              spmv_cg_info *info, hipStream_t s);
+
+/* out[r] = the sum of row r's stored entries in column r, or 1 / that sum,
+ * r < min(M, N) (diag_kernels.hip; spmv_*_diag); the caller has checked the
+ * handle */
+int csr_diag(const spmv_csr_dev *A, double *out, int invert, hipStream_t s);
+int hll_diag(const spmv_hll_dev *H, double *out, int invert, hipStream_t s);
 
 /* kernel launchers (csr_kernels.hip / hll_kernels.hip) */
 int csr_launch_kernel(const spmv_csr_dev *A, int kernel, int waves, int group,
