@@ -1390,19 +1390,8 @@ class _Device:
         bytes to solve without an allocation, None to let the library
         allocate and free one.  -> [CgResult(status, iterations, rr, bb)] * k;
         the result does not depend on check_every, work or waves_per_block."""
-        k, ldb, ldx = int(k), int(ldb), int(ldx)
-        if not 1 <= k <= 8:
-            raise ValueError("k=%r: 1..8 systems per solve" % (k,))
-        if (ldb and ldb < k) or (ldx and ldx < k):
-            raise ValueError("ldb=%d, ldx=%d: at least k=%d (or 0)"
-                             % (ldb, ldx, k))
-        o = _opts(waves_per_block, group if self._FMT == "csr" else 0)
-        info = (CgInfo * k)()
-        self._call("cg", C.byref(o), k, d_B, ldb, d_X, ldx, float(tol),
-                   int(maxit), int(check_every),
-                   work.ptr if work is not None else None,
-                   work.nbytes if work is not None else 0, info, stream)
-        return [CgResult(i.status, i.iterations, i.rr, i.bb) for i in info]
+        return self._cg("cg", d_B, d_X, (), k, tol, maxit, check_every, ldb,
+                        ldx, work, waves_per_block, group, stream)
 
     def pcg(self, d_B, d_X, d_minv, k=1, tol=1e-8, maxit=1000, check_every=0,
             ldb=0, ldx=0, work=None, waves_per_block=0, group=0, stream=None):
@@ -1412,6 +1401,14 @@ class _Device:
         else as cg() (`work`: at least pcg_work_bytes(M, k) bytes); a vector
         of ones returns the bits of cg().  A column whose r.z is not positive
         is a breakdown.  -> [CgResult(status, iterations, rr, bb)] * k"""
+        return self._cg("pcg", d_B, d_X, (d_minv,), k, tol, maxit,
+                        check_every, ldb, ldx, work, waves_per_block, group,
+                        stream)
+
+    def _cg(self, name, d_B, d_X, minv, k, tol, maxit, check_every, ldb, ldx,
+            work, waves_per_block, group, stream):
+        """cg() and pcg(): `minv` is () or (d_minv,), the argument only
+        spmv_*_pcg takes"""
         k, ldb, ldx = int(k), int(ldb), int(ldx)
         if not 1 <= k <= 8:
             raise ValueError("k=%r: 1..8 systems per solve" % (k,))
@@ -1420,8 +1417,8 @@ class _Device:
                              % (ldb, ldx, k))
         o = _opts(waves_per_block, group if self._FMT == "csr" else 0)
         info = (CgInfo * k)()
-        self._call("pcg", C.byref(o), k, d_B, ldb, d_X, ldx, d_minv,
-                   float(tol), int(maxit), int(check_every),
+        self._call(name, C.byref(o), k, d_B, ldb, d_X, ldx, *minv, float(tol),
+                   int(maxit), int(check_every),
                    work.ptr if work is not None else None,
                    work.nbytes if work is not None else 0, info, stream)
         return [CgResult(i.status, i.iterations, i.rr, i.bb) for i in info]

@@ -1788,39 +1788,18 @@ static int cg_axpby_of(const void *h, const spmv_launch_opts *opts, int k,
     return axpby_direct((const D *)h, opts, k, alpha, beta, X, ldx, Y, ldy, s);
 }
 
+/* pre: spmv_*_pcg, which needs d_minv; spmv_*_cg passes NULL */
 template <typename D>
 static int cg(const D *d, const spmv_launch_opts *opts, int k,
               const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
-              double tol, int maxit, int check_every, void *d_work,
-              size_t work_bytes, spmv_cg_info *info, void *stream) {
-    const int rc = multi_check(d, opts, k, d_B, &ldb, d_X, &ldx);
-    if (rc < 0)
-        return rc;
-    if (d->M != d->N || !(tol >= 0.0) || maxit < 0 || check_every < 0 || !info)
-        return -EINVAL;
-    if (rc) { /* no rows */
-        for (int j = 0; j < k; ++j)
-            info[j] = spmv_cg_info{0, 0, 0.0, 0.0};
-        return 0;
-    }
-    const cg_matrix A = {d, opts, d->M, cg_multi_of<D>, cg_axpby_of<D>};
-    return cg_solve(&A, k, d_B, ldb, d_X, ldx, tol, maxit,
-                    check_every ? check_every : 8, d_work, work_bytes, info,
-                    (hipStream_t)stream);
-}
-
-/* ... preconditioned: cg's checks and one more pointer */
-template <typename D>
-static int pcg(const D *d, const spmv_launch_opts *opts, int k,
-               const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
-               const double *d_minv, double tol, int maxit, int check_every,
-               void *d_work, size_t work_bytes, spmv_cg_info *info,
-               void *stream) {
+              bool pre, const double *d_minv, double tol, int maxit,
+              int check_every, void *d_work, size_t work_bytes,
+              spmv_cg_info *info, void *stream) {
     const int rc = multi_check(d, opts, k, d_B, &ldb, d_X, &ldx);
     if (rc < 0)
         return rc;
     if (d->M != d->N || !(tol >= 0.0) || maxit < 0 || check_every < 0 ||
-        !info || !d_minv)
+        !info || (pre && !d_minv))
         return -EINVAL;
     if (rc) { /* no rows */
         for (int j = 0; j < k; ++j)
@@ -1828,9 +1807,9 @@ static int pcg(const D *d, const spmv_launch_opts *opts, int k,
         return 0;
     }
     const cg_matrix A = {d, opts, d->M, cg_multi_of<D>, cg_axpby_of<D>};
-    return pcg_solve(&A, k, d_B, ldb, d_X, ldx, d_minv, tol, maxit,
-                     check_every ? check_every : 8, d_work, work_bytes, info,
-                     (hipStream_t)stream);
+    return cg_solve(&A, k, d_B, ldb, d_X, ldx, d_minv, tol, maxit,
+                    check_every ? check_every : 8, d_work, work_bytes, info,
+                    (hipStream_t)stream);
 }
 
 /* ---- the diagonal (diag_kernels.hip): launch_multi's handle checks ---- */
@@ -2418,8 +2397,8 @@ static int copy_tune_log(const D *d, char *buf, size_t len) {
                         int64_t ldx, double tol, int maxit, int check_every,   \
                         void *d_work, size_t work_bytes, spmv_cg_info *info,   \
                         void *stream) {                                        \
-        return cg(d, opts, k, d_B, ldb, d_X, ldx, tol, maxit, check_every,     \
-                  d_work, work_bytes, info, stream);                           \
+        return cg(d, opts, k, d_B, ldb, d_X, ldx, false, NULL, tol, maxit,     \
+                  check_every, d_work, work_bytes, info, stream);              \
     }                                                                          \
     int spmv_##fmt##_pcg(const D *d, const spmv_launch_opts *opts, int k,      \
                          const double *d_B, int64_t ldb, double *d_X,          \
@@ -2427,8 +2406,8 @@ static int copy_tune_log(const D *d, char *buf, size_t len) {
                          int maxit, int check_every, void *d_work,             \
                          size_t work_bytes, spmv_cg_info *info,                \
                          void *stream) {                                       \
-        return pcg(d, opts, k, d_B, ldb, d_X, ldx, d_minv, tol, maxit,         \
-                   check_every, d_work, work_bytes, info, stream);             \
+        return cg(d, opts, k, d_B, ldb, d_X, ldx, true, d_minv, tol, maxit,    \
+                  check_every, d_work, work_bytes, info, stream);              \
     }                                                                          \
     int spmv_##fmt##_diag(const D *d, double *d_out, int invert,               \
                           void *stream) {                                      \
@@ -2490,8 +2469,8 @@ extern "C" {
 HANDLE_API(csr, spmv_csr_dev, launch_rows)
 HANDLE_API(hll, spmv_hll_dev, launch_blocks)
 
-int64_t spmv_cg_work_bytes(int M, int k) { return cg_work_bytes(M, k); }
-int64_t spmv_pcg_work_bytes(int M, int k) { return pcg_work_bytes(M, k); }
+int64_t spmv_cg_work_bytes(int M, int k) { return cg_work_bytes(M, k, 0); }
+int64_t spmv_pcg_work_bytes(int M, int k) { return cg_work_bytes(M, k, 1); }
 void spmv_cg_dot_shape(int *workgroups, int *threads) {
     if (workgroups)
         *workgroups = CG_NWG;

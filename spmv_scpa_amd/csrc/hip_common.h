@@ -528,17 +528,14 @@ struct cg_matrix {
                  double alpha, double beta, const double *X, int64_t ldx,
                  double *Y, int64_t ldy, hipStream_t s);
 };
-int64_t cg_work_bytes(int M, int k);
+/* minv == NULL: plain (spmv_*_cg); else preconditioned with z = minv .* r,
+ * minv[M] (spmv_*_pcg, pre != 0): the same loop, one more set of partial sums
+ * in the work buffer */
+int64_t cg_work_bytes(int M, int k, int pre);
 int cg_solve(const cg_matrix *A, int k, const double *B, int64_t ldb, double *X,
-             int64_t ldx, double tol, int maxit, int check_every, void *d_work,
-             size_t work_bytes, spmv_cg_info *info, hipStream_t s);
-/* ... preconditioned with z = minv .* r, minv[M] (spmv_*_pcg): the same loop,
- * one more set of partial sums in the work buffer */
-int64_t pcg_work_bytes(int M, int k);
-int pcg_solve(const cg_matrix *A, int k, const double *B, int64_t ldb,
-              double *X, int64_t ldx, const double *minv, double tol, int maxit,
-              int check_every, void *d_work, size_t work_bytes,
-              spmv_cg_info *info, hipStream_t s);
+             int64_t ldx, const double *minv, double tol, int maxit,
+             int check_every, void *d_work, size_t work_bytes,
+             spmv_cg_info *info, hipStream_t s);
 
 /* out[r] = the sum of row r's stored entries in column r, or 1 / that sum,
  * r < min(M, N) (diag_kernels.hip; spmv_*_diag); the caller has checked the
