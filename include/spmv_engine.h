@@ -65,7 +65,10 @@ typedef struct spmv_launch_opts {
                             read-modify-write cache flush of rounds 1 / 2.
                             Blocked path: bit 0 launches a chain copy as steps
                             and vice versa, bits 1 / 2 force the tile order
-                            (else spmv_panel_opts.tile_order).  Any other bit:
+                            (else spmv_panel_opts.tile_order), bits 16-17
+                            name the sweep kernel's chunk: 1 = 576 lanes x 2
+                            groups, 2 = 384 x 3 (4608 slots both), 3 = the
+                            built-in shape.  Any other bit:
                             -EINVAL, except in an ablations build
                             (spmv_build_flavour) */
     int reserved[5];     /* must be 0 */
@@ -385,6 +388,24 @@ int spmv_csr_panels_layout(const spmv_csr_dev *A, spmv_panel_opts *o, int *waves
 int spmv_hll_panels_layout(const spmv_hll_dev *H, spmv_panel_opts *o, int *waves);
 int spmv_csr_panels_set_waves(spmv_csr_dev *A, int waves); /* 0..16 */
 int spmv_hll_panels_set_waves(spmv_hll_dev *H, int waves);
+/* sweep copies.  fit_steps: the steps one launch takes over all buckets with
+ * the chunk of the built-in launch shape and with the 4608-slot chunk, counted
+ * on the device at the end of the build; a copy whose second count is at
+ * least 10 % lower launches the 4608-slot shape unless waves_per_block or
+ * the variant ask for another.  set_fit_steps(h, 0, 0) makes the copy one
+ * whose steps were never counted: the built-in shape (this is what a
+ * layout string without chunk_fit rebuilds).  panels_plan: threads per
+ * workgroup, groups of 4 entries per lane and ordered additions (0 / 1) of
+ * the tile kernel that a blocked launch with `opts` (may be NULL) would run;
+ * nothing is launched.  -ENOENT: no copy. */
+int spmv_csr_panels_fit_steps(const spmv_csr_dev *A, int64_t *builtin, int64_t *fit);
+int spmv_hll_panels_fit_steps(const spmv_hll_dev *H, int64_t *builtin, int64_t *fit);
+int spmv_csr_panels_set_fit_steps(spmv_csr_dev *A, int64_t builtin, int64_t fit);
+int spmv_hll_panels_set_fit_steps(spmv_hll_dev *H, int64_t builtin, int64_t fit);
+int spmv_csr_panels_plan(const spmv_csr_dev *A, const spmv_launch_opts *opts,
+                         int *threads, int *groups, int *ordered);
+int spmv_hll_panels_plan(const spmv_hll_dev *H, const spmv_launch_opts *opts,
+                         int *threads, int *groups, int *ordered);
 int spmv_hll_panels_tile_rows(const spmv_hll_dev *H);
 int spmv_hll_panels_describe(const spmv_hll_dev *H, char *buf, size_t len);
 int spmv_hll_build_panels_as(spmv_hll_dev *H, int panel_cols, int sched,

@@ -563,6 +563,11 @@ _TWINS = (
     ("panels_layout", C.c_int,
      C.c_void_p, C.POINTER(PanelOpts), C.POINTER(C.c_int)),
     ("panels_set_waves", C.c_int, C.c_void_p, C.c_int),
+    ("panels_fit_steps", C.c_int,
+     C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)),
+    ("panels_set_fit_steps", C.c_int, C.c_void_p, C.c_int64, C.c_int64),
+    ("panels_plan", C.c_int,
+     C.c_void_p, C.POINTER(LaunchOpts), _ip, _ip, _ip),
     ("build_panels_opts", C.c_int, C.c_void_p, C.POINTER(PanelOpts)),
     ("build_panels", C.c_int, C.c_void_p, C.c_int),
     ("panels_describe", C.c_int, C.c_void_p, C.c_char_p, C.c_size_t),
@@ -778,9 +783,12 @@ _PIN_FIELDS = ("sched", "panel_cols", "tile_rows", "sweep_wgs_per_cu",
                "bucket_order", "deterministic")
 
 
-def _layout_pin(fn_layout, h):
+def _layout_pin(fn_layout, h, chunk_fit=0):
     """the blocked copy's layout as one string, "sched=2,tile_rows=4096,...,
-    waves=16" (None when there is no copy): what `build_panels_pinned` takes"""
+    waves=16" (None when there is no copy): what `build_panels_pinned` takes.
+    chunk_fit=1 is appended for a sweep copy that carries its counted steps
+    (panels_fit_steps): a string without it rebuilds a copy that launches the
+    built-in shape, as every string written before the count existed"""
     o, w = PanelOpts(), C.c_int()
     o.struct_size = C.sizeof(PanelOpts)
     rc = fn_layout(h, C.byref(o), C.byref(w))
@@ -788,24 +796,27 @@ def _layout_pin(fn_layout, h):
         return None
     _check(rc, "spmv_*_panels_layout")
     return ",".join(["%s=%d" % (f, getattr(o, f)) for f in _PIN_FIELDS]
-                    + ["waves=%d" % w.value])
+                    + ["waves=%d" % w.value]
+                    + (["chunk_fit=1"] if chunk_fit else []))
 
 
 def _pinned_opts(pin):
-    """-> (PanelOpts, waves) of a `panels_pin()` string; unknown keys are an
-    error (a pin of another library version must not half-apply)"""
+    """-> (PanelOpts, waves, chunk_fit) of a `panels_pin()` string; unknown
+    keys are an error (a pin of another library version must not half-apply)"""
     o = PanelOpts()
     _lib.spmv_panel_opts_default(C.byref(o))
-    waves = 0
+    waves = chunk_fit = 0
     for kv in pin.split(","):
         k, v = kv.split("=")
         if k == "waves":
             waves = int(v)
+        elif k == "chunk_fit":
+            chunk_fit = int(v)
         elif k in _PIN_FIELDS:
             setattr(o, k, int(v))
         else:
             raise ValueError("unknown field %r in blocked-layout pin" % k)
-    return o, waves
+    return o, waves, chunk_fit
 
 
 def _panel_opts(panel_cols=0, sched=None, tile_rows=0, sweep_wgs_per_cu=0,
@@ -1456,12 +1467,36 @@ class _Device:
     def panels_pin(self):
         """the layout of the blocked copy (schedule, tile height, orders,
         waves) as a string that `build_panels_pinned` rebuilds exactly"""
-        return _layout_pin(self._fn("panels_layout"), self.h)
+        fit = self.panels_fit_steps() if self.panels_describe() else None
+        return _layout_pin(self._fn("panels_layout"), self.h,
+                           bool(fit and fit[0] > 0))
 
     def build_panels_pinned(self, pin):
-        o, waves = _pinned_opts(pin)
+        o, waves, chunk_fit = _pinned_opts(pin)
         self._call("build_panels_opts", C.byref(o))
         self._call("panels_set_waves", waves)
+        if not chunk_fit:
+            self.panels_set_fit_steps(0, 0)
+
+    def panels_fit_steps(self):
+        """sweep copy: (steps with the built-in shape's chunk, steps with the
+        4608-slot chunk) counted at the build; (0, 0): not counted"""
+        a, b = C.c_int64(), C.c_int64()
+        self._call("panels_fit_steps", C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def panels_set_fit_steps(self, builtin, fit):
+        """(0, 0): launch the built-in shape (a copy without the count)"""
+        self._call("panels_set_fit_steps", builtin, fit)
+
+    def panels_plan(self, waves_per_block=0, variant=0):
+        """-> (threads, groups per lane, ordered) of the tile kernel a blocked
+        launch with these options would run"""
+        o = _opts(waves_per_block, 0, variant)
+        t, q, d = C.c_int(), C.c_int(), C.c_int()
+        self._call("panels_plan", C.byref(o), C.byref(t), C.byref(q),
+                   C.byref(d))
+        return t.value, q.value, d.value
 
     def build_panels_like(self, model):
         self._call("build_panels_like", model.h)

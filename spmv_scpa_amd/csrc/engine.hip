@@ -1972,6 +1972,42 @@ template <typename D> static int set_waves_of(D *d, int waves) {
     return 0;
 }
 
+/* sweep copies: the steps counted at the build (panel_launch.h "Chunk fit") */
+template <typename D>
+static int fit_steps_of(const D *d, int64_t *builtin, int64_t *fit) {
+    HANDLE_OK(d);
+    if (!d->panels)
+        return -ENOENT;
+    if (!builtin || !fit)
+        return -EINVAL;
+    panels_fit_steps(d->panels, builtin, fit);
+    return 0;
+}
+
+template <typename D>
+static int set_fit_steps_of(D *d, int64_t builtin, int64_t fit) {
+    HANDLE_OK(d);
+    if (!d->panels)
+        return -ENOENT;
+    if (builtin < 0 || fit < 0)
+        return -EINVAL;
+    panels_set_fit_steps(d->panels, builtin, fit);
+    return 0;
+}
+
+/* which tile kernel the blocked launch with these options would run */
+template <typename D>
+static int plan_of(const D *d, const spmv_launch_opts *opts, int *threads,
+                   int *groups, int *ordered) {
+    HANDLE_OK(d);
+    if (!d->panels)
+        return -ENOENT;
+    if (!threads || !groups || !ordered)
+        return -EINVAL;
+    return panels_plan_kernel(d->panels, opts ? opts->waves_per_block : 0,
+                              opts ? opts->variant : 0, threads, groups,
+                              ordered);
+}
 
 /* ------------------------------------------------------------------ */
 /* event-timed loops                                                    */
@@ -2450,6 +2486,18 @@ static int copy_tune_log(const D *d, char *buf, size_t len) {
     }                                                                          \
     int spmv_##fmt##_panels_set_waves(D *d, int waves) {                       \
         return set_waves_of(d, waves);                                         \
+    }                                                                          \
+    int spmv_##fmt##_panels_fit_steps(const D *d, int64_t *builtin,            \
+                                      int64_t *fit) {                          \
+        return fit_steps_of(d, builtin, fit);                                  \
+    }                                                                          \
+    int spmv_##fmt##_panels_set_fit_steps(D *d, int64_t builtin,               \
+                                          int64_t fit) {                       \
+        return set_fit_steps_of(d, builtin, fit);                              \
+    }                                                                          \
+    int spmv_##fmt##_panels_plan(const D *d, const spmv_launch_opts *opts,     \
+                                 int *threads, int *groups, int *ordered) {    \
+        return plan_of(d, opts, threads, groups, ordered);                     \
     }                                                                          \
     int spmv_##fmt##_autotune(D *d, const double *d_x, double *d_y,            \
                               int allow_panels, int *best_kernel,              \

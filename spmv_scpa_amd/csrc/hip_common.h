@@ -575,6 +575,10 @@ void panels_set_waves(spmv_panels *P, int waves);
 int panels_debug_stale_arrivals(spmv_panels *P);
 void panels_set_order(spmv_panels *P, int order);
 int panels_waves(const spmv_panels *P);
+void panels_fit_steps(const spmv_panels *P, int64_t *builtin, int64_t *fit);
+void panels_set_fit_steps(spmv_panels *P, int64_t builtin, int64_t fit);
+int panels_plan_kernel(const spmv_panels *P, int waves, int variant,
+                       int *threads, int *groups, int *ordered);
 int panels_launch(const spmv_panels *P, int M, int waves, int variant,
                   const double *x, double *y, hipStream_t s);
 void panels_free(spmv_panels *p);

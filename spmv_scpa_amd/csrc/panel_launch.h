@@ -46,6 +46,11 @@ struct panel_shape {
                         0 grouped, 1 hardware order, 2 XCD-contiguous ranges */
     int grid;        /* sweep: workgroups of the launch */
     int xcd_max;     /* longest range: the launch has NUM_XCD * xcd_max groups */
+    int64_t fit_steps[2]; /* sweep: steps of one pass over every bucket, the sum
+                        of ceil(entries / chunk) (an empty bucket: 1), [0]
+                        with the chunk of the built-in shape, [1] with
+                        PANEL_FIT_CHUNK (counted on the device at the end of
+                        a build); 0 = not counted: the built-in shape */
 };
 
 enum panel_family { PANEL_SWEEP, PANEL_CHAIN, PANEL_STEPS };
@@ -63,6 +68,9 @@ constexpr panel_kernel PANEL_SWEEP_KERNELS[] = {
     {256, 1, 0, 0},  {256, 1, 1, 0},  {256, 2, 0, 0},  {256, 2, 1, 0},
     {512, 1, 0, 0},  {512, 1, 1, 0},  {512, 2, 0, 0},  {512, 2, 1, 0},
     {1024, 1, 0, 0}, {1024, 1, 1, 0}, {1024, 2, 0, 0}, {1024, 2, 1, 0},
+    /* chunks of 4608 slots, which no power of two is a multiple of: 9
+     * wavefronts x 2 groups, 6 wavefronts x 3 groups (panel_fit_kernel) */
+    {576, 2, 0, 0},  {576, 2, 1, 0},  {384, 3, 0, 0},  {384, 3, 1, 0},
     /* timing ablations (results WRONG by design for 2, 3, 7) */
     {256, 1, 0, 1},  {256, 1, 0, 2},  {256, 1, 0, 3},  {256, 1, 0, 4},
     {256, 1, 0, 7},
@@ -70,7 +78,7 @@ constexpr panel_kernel PANEL_SWEEP_KERNELS[] = {
     {256, 1, 0, 8},  {256, 2, 0, 8},  {512, 1, 0, 8},  {512, 2, 0, 8},
     {1024, 1, 0, 8}, {1024, 2, 0, 8},
 };
-constexpr int PANEL_SWEEP_PRODUCT = 12;
+constexpr int PANEL_SWEEP_PRODUCT = 16;
 constexpr int panel_sweep_kernels(bool ablations) {
     return ablations ? (int)(sizeof PANEL_SWEEP_KERNELS / sizeof(panel_kernel))
                      : PANEL_SWEEP_PRODUCT;
@@ -126,6 +134,39 @@ static inline int panel_threads_of_waves(int waves) {
 }
 
 /*
+ * Chunk fit.  A bucket of n entries takes ceil(n / chunk) steps of the sweep
+ * kernel, each a full set of stream loads and, in ordered mode, a full chain
+ * of turns, however few entries the last one holds.  With 2^17-column
+ * panels and N / 512 rows per tile a bucket holds 32 * 2^17 / 512 = 8192
+ * entries on average whatever N is -- a multiple of every power-of-two chunk,
+ * so about half of the buckets spill a few dozen entries into one more step.
+ * A chunk of 4608 slots takes such a bucket in two steps.  The rule: a copy
+ * that fills a CU by itself and whose COUNTED steps (panel_shape.fit_steps)
+ * fall by PANEL_FIT_GAIN_PCT or more takes PANEL_FIT_SHAPE instead of
+ * 512 x 2.  Variant bits 16-17 ask for a shape whatever was counted:
+ * 1 = 576 x 2, 2 = 384 x 3, 3 = the built-in shape.
+ */
+constexpr int PANEL_FIT_CHUNK = 4608;
+constexpr int PANEL_FIT_GAIN_PCT = 10;
+constexpr int PANEL_FIT_VARIANT_SHIFT = 16;
+constexpr int PANEL_FIT_VARIANT_BITS = 3 << PANEL_FIT_VARIANT_SHIFT;
+/* which = 1: 9 wavefronts x 2 groups, 2: 6 wavefronts x 3 groups */
+constexpr panel_kernel panel_fit_kernel(int which) {
+    return which == 2 ? panel_kernel{384, 3, 0, 0} : panel_kernel{576, 2, 0, 0};
+}
+/* the sibling the rule names.  Headline copy, medians of 20 launches, shapes
+ * alternating (profiles/sweep_chunk_fit.md), 512 x 2 / 576 x 2 / 384 x 3:
+ * ordered additions, a sweep copy's default, 1.4337 / 1.4165 / 1.3941 ms (six
+ * hand-offs per chain of turns instead of nine); arrival order 1.4518 /
+ * 1.4196 / 1.4307 */
+constexpr int PANEL_FIT_SHAPE = 2;
+
+static inline bool panel_fit_pays(const panel_shape &P) {
+    return P.fit_steps[0] > 0 && P.fit_steps[1] > 0 &&
+           P.fit_steps[1] * 100 <= P.fit_steps[0] * (100 - PANEL_FIT_GAIN_PCT);
+}
+
+/*
  * The complete plan of one panels_launch_tiles() call, or -EINVAL.
  * `ablations`: the build carries the experiment arms (-DSPMV_ABLATIONS).
  */
@@ -133,12 +174,14 @@ static inline int panel_launch_plan(const panel_shape &P, int waves,
                                     int variant, bool ablations,
                                     panel_plan *out) {
     /* product build: bit 0 flips chain <-> steps, bits 1 / 2 force a tile
-     * order (spmv_engine.h).  Everything else this function understands --
+     * order, bits 16-17 name a chunk-fit shape of the sweep (spmv_engine.h).
+     * Everything else this function understands --
      * lag override (4-6), no phase wait (7), the ABL arms whose result is
      * WRONG by design (8-10), group counts (11), staggered panels (12),
      * group sizes (14-15) -- exists only in a -DSPMV_ABLATIONS build
      * (`make abl`; tools/sweep.py, tools/pmc.sh load that flavour) */
-    if (!ablations && (variant & ~(1 | 2 | 4 | SPMV_VARIANT_TIMING_BITS)))
+    if (!ablations && (variant & ~(1 | 2 | 4 | PANEL_FIT_VARIANT_BITS |
+                                   SPMV_VARIANT_TIMING_BITS)))
         return -EINVAL;
     panel_plan p = {};
     p.lds = (size_t)P.tile_rows * sizeof(double);
@@ -167,6 +210,7 @@ static inline int panel_launch_plan(const panel_shape &P, int waves,
         /* timing ablations (results WRONG by design for 2, 3, 7): compiled
          * only by `make abl` */
         const int abl = ablations ? (variant >> 8) & 7 : 0;
+        const int fit = (variant >> PANEL_FIT_VARIANT_SHIFT) & 3;
         if (abl == 5 || abl == 6) {
             /* tall-tile probe, the production launch shapes */
             p.k = {panel_threads_of_waves(waves), abl == 5 ? 2 : 1, 0, 8};
@@ -177,6 +221,13 @@ static inline int panel_launch_plan(const panel_shape &P, int waves,
              * (1.53 ms on config 3; 1024 x 1: 1.60); bit 11 flips the groups */
             const int threads = panel_threads_of_waves(waves);
             p.k = {threads, (threads == 1024) != bit11 ? 1 : 2, 0, 0};
+            /* nobody asked for a shape and the buckets are of the 512 x 2
+             * class: the chunk that fits them (panel_fit_pays) */
+            const double per_bucket =
+                (double)P.nnz / ((double)P.tiles * (double)P.panels);
+            if (waves <= 0 && !bit11 && fit == 0 && per_bucket >= 6000.0 &&
+                panel_fit_pays(P))
+                p.k = panel_fit_kernel(PANEL_FIT_SHAPE);
         } else if (waves > 0) { /* 2 groups of 4 per lane; bit 11: 1 */
             p.k = {waves < 8 ? 256 : 512, bit11 ? 1 : 2, 0, 0};
         } else {
@@ -192,6 +243,8 @@ static inline int panel_launch_plan(const panel_shape &P, int waves,
             else
                 p.k = {256, 1, 0, 0};
         }
+        if (p.k.abl == 0 && (fit == 1 || fit == 2))
+            p.k = panel_fit_kernel(fit);
         p.k.det = P.det && p.k.abl == 0;
     } else {
         if (P.tiles <= 0 || P.xcd_max <= 0) {

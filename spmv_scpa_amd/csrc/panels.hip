@@ -489,6 +489,24 @@ __global__ void k_max_int(int n, const int *__restrict__ v, int *out) {
     atomicMax(out, m);
 }
 
+/* steps the sweep kernel takes over n buckets with chunks of ch0 / ch1 slots:
+ * a bucket of b entries is walked in ceil(b / ch) steps, an empty one in one
+ * (k_tiles_sweep: `last = fk + CH >= fe`) */
+__global__ void k_chunk_steps(int64_t n, const int *__restrict__ blen, int ch0,
+                              int ch1, unsigned long long *out) {
+    unsigned long long s0 = 0, s1 = 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const int b = blen[i];
+        s0 += b > ch0 ? (unsigned)(b + ch0 - 1) / (unsigned)ch0 : 1u;
+        s1 += b > ch1 ? (unsigned)(b + ch1 - 1) / (unsigned)ch1 : 1u;
+    }
+    if (s0)
+        atomicAdd(out, s0);
+    if (s1)
+        atomicAdd(out + 1, s1);
+}
+
 /* process default of spmv_*_build_panels(): 0 steps, 1 sweep, 2 chain.  The
  * only process-wide setting of this file; builds that must not depend on it
  * pass spmv_panel_opts.sched (spmv_*_build_panels_opts / _as). */
@@ -1092,6 +1110,28 @@ static int place_entries(const panel_geometry &g, const uint64_t *skey,
     return 0;
 }
 
+/* sweep: panel_shape.fit_steps from the bucket lengths as built, for the
+ * chunk of the shape the plan takes WITHOUT them and for PANEL_FIT_CHUNK */
+static int count_chunk_steps(const panel_geometry &g, spmv_panels *P) {
+    P->fit_steps[0] = P->fit_steps[1] = 0;
+    panel_plan pl;
+    if (g.nbuckets <= 0 || P->nnz <= 0 ||
+        panel_launch_plan(*P, 0, 0, false, &pl) || pl.family != PANEL_SWEEP)
+        return 0;
+    plain_block sums;
+    HIP_RET(sums.alloc(2 * sizeof(unsigned long long)));
+    HIP_RET(hipMemset(sums.p, 0, 2 * sizeof(unsigned long long)));
+    hipLaunchKernelGGL(k_chunk_steps, dim3(64), dim3(256), 0, 0,
+                       (int64_t)g.nbuckets, P->blen, pl.k.threads * pl.k.q * 4,
+                       PANEL_FIT_CHUNK, sums.as<unsigned long long>());
+    HIP_RET(hipGetLastError());
+    unsigned long long h[2] = {0, 0};
+    HIP_RET(hipMemcpy(h, sums.p, sizeof h, hipMemcpyDeviceToHost));
+    P->fit_steps[0] = (int64_t)h[0];
+    P->fit_steps[1] = (int64_t)h[1];
+    return 0;
+}
+
 /* sweep: the per-XCD arrival counters of every (round, panel) */
 static int alloc_phase_counters(const panel_geometry &g, spmv_panels *P) {
     const size_t rounds = ((size_t)g.tiles + g.grid - 1) / g.grid;
@@ -1169,6 +1209,8 @@ static int build_stages(const panel_geometry &g, const build_src &s,
     if ((rc = place_entries(g, skey, sval, b.raw.as<int64_t>(), P)))
         return rc;
     if ((rc = g.sweep ? alloc_phase_counters(g, P) : balance_xcd_ranges(P)))
+        return rc;
+    if (g.sweep && (rc = count_chunk_steps(g, P)))
         return rc;
     tp[4] = build_now_s();
     snprintf(g_build_phases, sizeof g_build_phases,
@@ -2085,6 +2127,30 @@ void panels_set_waves(spmv_panels *P, int waves) {
         P->waves_hint = waves > 0 ? waves : 0;
 }
 int panels_tile_rows(const spmv_panels *P) { return P ? P->tile_rows : 0; }
+void panels_fit_steps(const spmv_panels *P, int64_t *builtin, int64_t *fit) {
+    *builtin = P ? P->fit_steps[0] : 0;
+    *fit = P ? P->fit_steps[1] : 0;
+}
+/* (0, 0): as a copy whose steps were never counted -- the built-in shape */
+void panels_set_fit_steps(spmv_panels *P, int64_t builtin, int64_t fit) {
+    if (P) {
+        P->fit_steps[0] = builtin > 0 ? builtin : 0;
+        P->fit_steps[1] = fit > 0 ? fit : 0;
+    }
+}
+/* the tile kernel a launch with (waves, variant) would run */
+int panels_plan_kernel(const spmv_panels *P, int waves, int variant,
+                       int *threads, int *groups, int *ordered) {
+    panel_plan pl;
+    if (!P)
+        return -EINVAL;
+    if (int rc = panel_launch_plan(*P, waves, variant, ABLATIONS, &pl))
+        return rc;
+    *threads = pl.k.threads;
+    *groups = pl.k.q;
+    *ordered = pl.k.det;
+    return 0;
+}
 
 /* test hook (spmv_*_debug_stale_arrivals): what a launch that never
  * completed leaves in the long rows' arrival counters */
