@@ -347,8 +347,8 @@ int spmv_hll_value_bytes(const spmv_hll_dev *H); /* 8 or 4 */
  * / _kernel_bytes ((2 + value_bytes) S + 4 nb for the bases + 12 nb + 8 M +
  * 8 N), release / release_checked.  spmv_hll_build_panels*,
  * spmv_hll_launch_multi, spmv_hll_multi_bytes, spmv_hll_launch_axpby,
- * spmv_hll_axpby_bytes, spmv_hll_cg, spmv_hll_pcg and spmv_hll_diag:
- * -ENOTSUP.  The handle owns
+ * spmv_hll_axpby_bytes, spmv_hll_cg, spmv_hll_pcg, spmv_hll_bicgstab and
+ * spmv_hll_diag: -ENOTSUP.  The handle owns
  * no 4-byte JA and no pad bitmap.  The one-shot seam, the reference ABI names
  * and spmv_mgpu.h create 4-byte handles only.
  */
@@ -686,6 +686,83 @@ int spmv_hll_pcg(const spmv_hll_dev *H, const spmv_launch_opts *opts, int k,
                  double tol, int maxit, int check_every,
                  void *d_work, size_t work_bytes,
                  spmv_cg_info *info, void *stream);
+
+/*
+ * BiCGStab on the device for A X = B with a nonsymmetric A (added after 0.7;
+ * spmv_version() is unchanged, detect it by the symbol).  A: square, otherwise
+ * arbitrary, a CSR or column-major HLL handle of either value type.  Only A x
+ * is used (two launch_multi per iteration), never a transposed product.
+ * k = 1..8 independent systems stored interleaved as in spmv_*_launch_multi.
+ *
+ * d_minv: M doubles, one per row, shared by the k columns, never written: a
+ * RIGHT diagonal preconditioner, A M^-1 (M x) = b with z(u)_i = minv_i * u_i.
+ * Any sign is allowed; spmv_*_diag(invert = 1) gives Jacobi.  NULL: none.
+ *
+ * d_X, d_B, the strides, the spmv_cg_info records (iterations counts the full
+ * steps applied to X), the blocking, -EBUSY on a capturing stream before
+ * anything is allocated or enqueued, check_every (0 = 8), maxit, d_work (NULL:
+ * the library allocates and frees it; else 8-byte aligned and at least
+ * spmv_bicgstab_work_bytes(M, k) bytes, else -EINVAL), M == 0 and the argument
+ * checks are those of spmv_*_pcg above, word for word, except that d_minv may
+ * be NULL.  spmv_bicgstab_work_bytes(M, k) = a base that depends on neither
+ * argument (the state block, two sets of partial sums) + 6 * 8 * k * M: R,
+ * the shadow residual Rh, P, V, T and the preconditioned vector launch_multi
+ * reads.
+ *
+ * Result contract, to the bit.  Every operation is rounded once, no fused
+ * multiply-add, divisions are correctly rounded; dot is the dot of
+ * spmv_cg_dot_shape; z(U) is rn(minv_i * u_i) in every column, U itself
+ * without d_minv; tol2 = tol * tol on the host.
+ *
+ *   R = B;  R = (-1) A X + 1 R  by the handle's launch_axpby;  Rh = R;  P = R
+ *   bb = dot(B, B);  rr = dot(R, R);  rho = rr
+ *   column j: status 2 (iterations 0) if rr or bb is not finite,
+ *             else converged (iterations 0) if rr <= tol2 * bb, else running
+ *   repeat at most maxit times:
+ *       Z = z(P);  V = A Z   by launch_multi (all k columns, the caller's opts)
+ *       rv = dot(Rh, V)
+ *       running column with !(rv != 0 and finite): status 2, frozen
+ *       running column: alpha = rho / rv;  S = R - alpha * V
+ *       Zs = z(S);  T = A Zs  by launch_multi
+ *       ts = dot(T, S);  tt = dot(T, T)
+ *       running column with ts or tt not finite: status 2, frozen
+ *       running column: omega = tt > 0 ? ts / tt : 0.0
+ *                       X = (X + alpha * Z) + omega * Zs
+ *                       R = S - omega * T;   iterations += 1
+ *       rn = dot(R, R);  rhon = dot(Rh, R)
+ *       running column: rn <= tol2 * bb -> status 0, frozen (rr = rn)
+ *                       rn not finite   -> status 2, frozen
+ *       running column: beta = (rhon / rho) * (alpha / omega)
+ *                       P = R + beta * (P - omega * V);  rho = rhon;  rr = rn
+ *   columns still running: status 1
+ *
+ * omega == 0 and rhon == 0 get no rule of their own: they make beta infinite,
+ * NaN or zero, and plain arithmetic carries the column to the rv test of the
+ * next iteration, or on.  S == 0 exactly makes tt == 0, omega = 0 and R = 0:
+ * the column converges in that step.
+ *
+ * X, iterations, status and rr of a frozen column are never written again,
+ * however many iterations were enqueued after it stopped and whatever the
+ * other columns hold.  So the results do not depend on check_every, on who
+ * owns the work buffer, on waves_per_block or on the other columns, and
+ * column j of a k-column solve has the bits of the k = 1 solve of that column.
+ * d_minv of all 1.0 gives the bits of d_minv == NULL (rn(1.0 * u) = u): a
+ * property of the contract.  The internal vectors are not observable: S lives
+ * in R's storage, Z and Zs share one buffer.
+ */
+int64_t spmv_bicgstab_work_bytes(int M, int k); /* -EINVAL: M < 0, k outside 1..8 */
+int spmv_csr_bicgstab(const spmv_csr_dev *A, const spmv_launch_opts *opts,
+                      int k, const double *d_B, int64_t ldb, double *d_X,
+                      int64_t ldx, const double *d_minv,
+                      double tol, int maxit, int check_every,
+                      void *d_work, size_t work_bytes,
+                      spmv_cg_info *info, void *stream);
+int spmv_hll_bicgstab(const spmv_hll_dev *H, const spmv_launch_opts *opts,
+                      int k, const double *d_B, int64_t ldb, double *d_X,
+                      int64_t ldx, const double *d_minv,
+                      double tol, int maxit, int check_every,
+                      void *d_work, size_t work_bytes,
+                      spmv_cg_info *info, void *stream);
 
 /*
  * Pick the fastest kernel for this matrix by measurement (5 launches each):

@@ -549,6 +549,7 @@ _sig("spmv_hll_kernel_bytes", C.c_int64, C.c_void_p, C.c_int)
 _sig("spmv_cg_work_bytes", C.c_int64, C.c_int, C.c_int)
 _sig("spmv_cg_dot_shape", None, _ip, _ip)
 _sig("spmv_pcg_work_bytes", C.c_int64, C.c_int, C.c_int)
+_sig("spmv_bicgstab_work_bytes", C.c_int64, C.c_int, C.c_int)
 # spmv_csr_<name> and spmv_hll_<name>: the same argument types
 _TWINS = (
     ("release_checked", None, C.c_void_p, C.c_uint64),
@@ -592,6 +593,10 @@ _TWINS = (
      C.c_void_p, C.c_int64, C.c_double, C.c_int, C.c_int, C.c_void_p,
      C.c_size_t, C.POINTER(CgInfo), C.c_void_p),
     ("pcg", C.c_int,
+     C.c_void_p, C.POINTER(LaunchOpts), C.c_int, C.c_void_p, C.c_int64,
+     C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_int, C.c_int,
+     C.c_void_p, C.c_size_t, C.POINTER(CgInfo), C.c_void_p),
+    ("bicgstab", C.c_int,
      C.c_void_p, C.POINTER(LaunchOpts), C.c_int, C.c_void_p, C.c_int64,
      C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_int, C.c_int,
      C.c_void_p, C.c_size_t, C.POINTER(CgInfo), C.c_void_p),
@@ -686,6 +691,13 @@ def pcg_work_bytes(M, k):
     cg_work_bytes and one more set of partial sums"""
     return _check(_lib.spmv_pcg_work_bytes(int(M), int(k)),
                   "spmv_pcg_work_bytes")
+
+
+def bicgstab_work_bytes(M, k):
+    """bytes of device memory one bicgstab() solve of k systems with M rows
+    needs: a base that depends on neither, and six vectors of 8 k M bytes"""
+    return _check(_lib.spmv_bicgstab_work_bytes(int(M), int(k)),
+                  "spmv_bicgstab_work_bytes")
 
 
 def version():
@@ -1416,10 +1428,27 @@ class _Device:
                         check_every, ldb, ldx, work, waves_per_block, group,
                         stream)
 
+    def bicgstab(self, d_B, d_X, k=1, d_minv=None, tol=1e-8, maxit=1000,
+                 check_every=0, ldb=0, ldx=0, work=None, waves_per_block=0,
+                 group=0, stream=None):
+        """BiCGStab for A X = B on the device, A square and otherwise
+        arbitrary (nonsymmetric, indefinite): only A x is used, twice per
+        iteration.  k, the layout, d_X / d_B, the blocking, check_every and
+        `work` (at least bicgstab_work_bytes(M, k) bytes) as cg().  d_minv:
+        M doubles of a right diagonal preconditioner (any sign;
+        diag(d_minv, invert=True) gives Jacobi), never written; None: none,
+        with the bits a vector of ones gives.  Stops a column when
+        r.r <= tol^2 b.b, after maxit iterations, or on a breakdown (rh.v
+        zero, a non-finite scalar).
+        -> [CgResult(status, iterations, rr, bb)] * k"""
+        return self._cg("bicgstab", d_B, d_X, (d_minv,), k, tol, maxit,
+                        check_every, ldb, ldx, work, waves_per_block, group,
+                        stream)
+
     def _cg(self, name, d_B, d_X, minv, k, tol, maxit, check_every, ldb, ldx,
             work, waves_per_block, group, stream):
-        """cg() and pcg(): `minv` is () or (d_minv,), the argument only
-        spmv_*_pcg takes"""
+        """cg(), pcg() and bicgstab(): `minv` is () or (d_minv,), the
+        argument spmv_*_cg does not take"""
         k, ldb, ldx = int(k), int(ldb), int(ldx)
         if not 1 <= k <= 8:
             raise ValueError("k=%r: 1..8 systems per solve" % (k,))

@@ -16,14 +16,8 @@
  * final_rz -- are in cg_body.h, written once and included twice below: the
  * k_cg_* and the k_pcg_* kernel of a pair are one text.
  *
- * DOT ORDER, a function of M alone (CG_NWG, CG_T are constants of the
- * library, exported to the tests as spmv_cg_dot_shape):
- *   element i belongs to slot i mod (CG_NWG * CG_T); slot s is slot s % CG_T
- *   of workgroup s / CG_T.  A slot starts at 0.0 and adds rn(u_i * v_i) in
- *   increasing i.  The CG_T slots of a workgroup are combined by a halving
- *   tree, s[t] += s[t + h] for h = CG_T / 2 .. 1; the CG_NWG workgroup sums by
- *   the same tree.  Workgroups whose slots hold no element are not launched:
- *   their sum is the 0.0 the tree would have given.
+ * The dot order, the tile of a vector kernel (cg_lanes), the halving trees and
+ * the launch macros are in cg_common.h, shared with bicgstab_kernels.hip.
  *
  * STATE.  alpha, beta, rr, bb, status and the iteration count of every column
  * live in one cg_state block at the head of the work buffer.  It is written
@@ -38,10 +32,7 @@
  * however many iterations are enqueued after it stopped, and whatever the
  * other columns hold.
  */
-#include "hip_common.h"
-
-#define CG_MAXK 8
-#define CG_FINAL_T 1024 /* threads of a finalising workgroup, >= CG_NWG */
+#include "cg_common.h"
 
 /* per-column state, device memory (CG_STATE_BYTES at the head of the work
  * buffer) */
@@ -56,35 +47,6 @@ struct cg_state {
                               only; behind the fields the plain kernels use) */
 };
 static_assert(sizeof(cg_state) <= CG_STATE_BYTES, "state block");
-static_assert(CG_FINAL_T >= CG_NWG && (CG_NWG & (CG_NWG - 1)) == 0 &&
-                  (CG_T & (CG_T - 1)) == 0,
-              "the halving trees need powers of two");
-
-/*
- * LANES.  A workgroup's share of one sweep is a tile of CG_T rows x K columns
- * -- CG_T * K consecutive doubles in R, P, Q (ld = K).  Which lane holds which
- * slot is no part of the dot order, so the tile is read the way memory wants
- * it: in pass n = 0..K-1 thread p takes element f = p + n CG_T of the tile,
- * row t = f / K, column j = f % K -- a wavefront's load is 512 consecutive
- * bytes, whatever K.  (One row per thread was measured first: at K = 8 a load
- * touched 64 lines for 8 bytes each and the three kernels ran at 1.5 TB/s.)
- * (t, j) of a pass is the same in every sweep, so acc[n] is the slot sum of
- * (slot t, column j).  The loads are unconditional, at a row clamped to M - 1,
- * so all K passes are in flight together; sums and stores are predicated.  A
- * frozen column shares its cache lines with the running ones: it may be read,
- * it is never written.
- */
-template <int K> struct cg_lanes {
-    int t[K], j[K];
-    __device__ __forceinline__ cg_lanes() {
-#pragma unroll
-        for (int n = 0; n < K; ++n) {
-            const int f = threadIdx.x + n * CG_T;
-            t[n] = f / K;
-            j[n] = f % K;
-        }
-    }
-};
 
 /* running[n]: the column of pass n is running */
 template <int K>
@@ -95,35 +57,6 @@ __device__ __forceinline__ void running_passes(const cg_state *st,
     for (int n = 0; n < K; ++n)
         running[n] = st->status[l.j[n]] == CG_RUNNING;
 }
-
-/* The slot sums of a workgroup -> part[blockIdx.x * K + j]: the halving tree
- * of the dot order.  All CG_T threads call. */
-template <int K>
-__device__ __forceinline__ void slots_to_partial(const cg_lanes<K> &l,
-                                                 const double (&acc)[K],
-                                                 double *__restrict__ part) {
-    __shared__ double s[K][CG_T];
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int n = 0; n < K; ++n)
-        s[l.j[n]][l.t[n]] = acc[n];
-    __syncthreads();
-    for (int h = CG_T / 2; h > 0; h >>= 1) {
-        if (t < h) {
-#pragma unroll
-            for (int j = 0; j < K; ++j)
-                s[j][t] += s[j][t + h];
-        }
-        __syncthreads();
-    }
-    if (t < K)
-        part[(size_t)blockIdx.x * K + t] = s[t][0];
-}
-
-/* the sweeps of a workgroup: `base` = first row of its tile */
-#define CG_SWEEPS(base, M)                                                    \
-    for (int64_t base = (int64_t)blockIdx.x * CG_T; base < (M);               \
-         base += (int64_t)CG_NWG * CG_T)
 
 /* dst[i * ldd + j] = src[i * lds + j], j < K (R = B, P = R) */
 template <int K>
@@ -174,29 +107,6 @@ k_cg_dot(int M, const double *__restrict__ U, int64_t ldu,
     slots_to_partial<K>(l, acc, part);
 }
 
-/* ---- helpers of the finalising kernels (cg_body.h) ---- */
-
-/* column j of the nwg workgroup sums (0.0 for the workgroups that were not
- * launched) by the halving tree over CG_NWG; the total in every thread */
-__device__ __forceinline__ double final_sum(const double *__restrict__ part,
-                                            int nwg, int k, int j, double *s) {
-    const int t = threadIdx.x;
-    s[t] = t < nwg ? part[(size_t)t * k + j] : 0.0;
-    __syncthreads();
-    for (int h = CG_NWG / 2; h > 0; h >>= 1) {
-        if (t < h)
-            s[t] += s[t + h];
-        __syncthreads();
-    }
-    const double v = s[0];
-    __syncthreads(); /* s is reused for the next column */
-    return v;
-}
-
-__device__ __forceinline__ bool cg_finite(double v) {
-    return __builtin_fabs(v) <= 1.7976931348623157e308; /* false for NaN */
-}
-
 /* preconditioned only (z(R) = rn(minv_i * r_i) per row, cg_body.h):
  * dst = z(src) (P = z(R)) and the partials of src . z(src), both interleaved
  * with ld = K; all columns (nothing is frozen before the first classification) */
@@ -238,34 +148,6 @@ k_pcg_first(int M, const double *__restrict__ minv,
 /* launches, and the kernels of an iteration (cg_body.h)                */
 /* ------------------------------------------------------------------ */
 
-/* workgroups whose slots hold an element */
-static unsigned cg_grid(int M) {
-    const int64_t g = ((int64_t)M + CG_T - 1) / CG_T;
-    return (unsigned)(g < CG_NWG ? g : CG_NWG);
-}
-
-#define CG_K_SWITCH(k, CALL, ...)                                             \
-    switch (k) {                                                              \
-    case 1: CALL(1, __VA_ARGS__); break;                                      \
-    case 2: CALL(2, __VA_ARGS__); break;                                      \
-    case 3: CALL(3, __VA_ARGS__); break;                                      \
-    case 4: CALL(4, __VA_ARGS__); break;                                      \
-    case 5: CALL(5, __VA_ARGS__); break;                                      \
-    case 6: CALL(6, __VA_ARGS__); break;                                      \
-    case 7: CALL(7, __VA_ARGS__); break;                                      \
-    default: CALL(8, __VA_ARGS__); break;                                     \
-    }
-
-/* kernel<k>(M, ...) over the slots of M rows on stream s: every vector kernel */
-#define CG_LAUNCH_K(KK, kernel, M, s, ...)                                    \
-    hipLaunchKernelGGL((kernel<KK>), dim3(cg_grid(M)), dim3(CG_T), 0, s, M,    \
-                       __VA_ARGS__)
-#define CG_LAUNCH(kernel, k, M, s, ...)                                       \
-    CG_K_SWITCH(k, CG_LAUNCH_K, kernel, M, s, __VA_ARGS__)
-/* kernel(...) in one workgroup on stream s: every finalising kernel */
-#define CG_FINAL(kernel, s, ...)                                              \
-    hipLaunchKernelGGL(kernel, dim3(1), dim3(CG_FINAL_T), 0, s, __VA_ARGS__)
-
 /* one solve as its launches see it: the sizes, the caller's vectors and the
  * work buffer cut up (cg_solve() below) */
 struct cg_run {
@@ -290,6 +172,17 @@ struct cg_run {
 /* ------------------------------------------------------------------ */
 /* host                                                                 */
 /* ------------------------------------------------------------------ */
+
+/* the two kernels every solver launches, for the other translation units
+ * (hip_common.h) */
+void cg_launch_copy(int k, int M, const double *src, int64_t lds, double *dst,
+                    int64_t ldd, hipStream_t s) {
+    CG_LAUNCH(k_cg_copy, k, M, s, src, lds, dst, ldd);
+}
+void cg_launch_dot(int k, int M, const double *U, int64_t ldu, const double *V,
+                   int64_t ldv, double *part, hipStream_t s) {
+    CG_LAUNCH(k_cg_dot, k, M, s, U, ldu, V, ldv, part);
+}
 
 /* state, the sets of partial sums (pq, rn; preconditioned: and zn, which is
  * live together with rn), R, P, Q */

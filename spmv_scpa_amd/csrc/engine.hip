@@ -1812,6 +1812,30 @@ static int cg(const D *d, const spmv_launch_opts *opts, int k,
                     (hipStream_t)stream);
 }
 
+/* BiCGStab (bicgstab_kernels.hip): cg's checks and cg's view of the matrix;
+ * d_minv may be NULL (no preconditioner) */
+template <typename D>
+static int bicgstab(const D *d, const spmv_launch_opts *opts, int k,
+                    const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                    const double *d_minv, double tol, int maxit,
+                    int check_every, void *d_work, size_t work_bytes,
+                    spmv_cg_info *info, void *stream) {
+    const int rc = multi_check(d, opts, k, d_B, &ldb, d_X, &ldx);
+    if (rc < 0)
+        return rc;
+    if (d->M != d->N || !(tol >= 0.0) || maxit < 0 || check_every < 0 || !info)
+        return -EINVAL;
+    if (rc) { /* no rows */
+        for (int j = 0; j < k; ++j)
+            info[j] = spmv_cg_info{0, 0, 0.0, 0.0};
+        return 0;
+    }
+    const cg_matrix A = {d, opts, d->M, cg_multi_of<D>, cg_axpby_of<D>};
+    return bicgstab_solve(&A, k, d_B, ldb, d_X, ldx, d_minv, tol, maxit,
+                          check_every ? check_every : 8, d_work, work_bytes,
+                          info, (hipStream_t)stream);
+}
+
 /* ---- the diagonal (diag_kernels.hip): launch_multi's handle checks ---- */
 static int diag_direct(const spmv_csr_dev *A, double *out, int invert,
                        hipStream_t s) {
@@ -2445,6 +2469,15 @@ static int copy_tune_log(const D *d, char *buf, size_t len) {
         return cg(d, opts, k, d_B, ldb, d_X, ldx, true, d_minv, tol, maxit,    \
                   check_every, d_work, work_bytes, info, stream);              \
     }                                                                          \
+    int spmv_##fmt##_bicgstab(const D *d, const spmv_launch_opts *opts,        \
+                              int k, const double *d_B, int64_t ldb,           \
+                              double *d_X, int64_t ldx, const double *d_minv,  \
+                              double tol, int maxit, int check_every,          \
+                              void *d_work, size_t work_bytes,                 \
+                              spmv_cg_info *info, void *stream) {              \
+        return bicgstab(d, opts, k, d_B, ldb, d_X, ldx, d_minv, tol, maxit,    \
+                        check_every, d_work, work_bytes, info, stream);        \
+    }                                                                          \
     int spmv_##fmt##_diag(const D *d, double *d_out, int invert,               \
                           void *stream) {                                      \
         return diag(d, d_out, invert, stream);                                 \
@@ -2519,6 +2552,9 @@ HANDLE_API(hll, spmv_hll_dev, launch_blocks)
 
 int64_t spmv_cg_work_bytes(int M, int k) { return cg_work_bytes(M, k, 0); }
 int64_t spmv_pcg_work_bytes(int M, int k) { return cg_work_bytes(M, k, 1); }
+int64_t spmv_bicgstab_work_bytes(int M, int k) {
+    return bicgstab_work_bytes(M, k);
+}
 void spmv_cg_dot_shape(int *workgroups, int *threads) {
     if (workgroups)
         *workgroups = CG_NWG;

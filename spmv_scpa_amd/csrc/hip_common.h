@@ -1,7 +1,7 @@
 /*
  * hip_common.h -- internals shared by the HIP translation units
  * (engine.hip, csr_kernels.hip, hll_kernels.hip, multi_kernels.hip,
- * cg_kernels.hip, diag_kernels.hip, panels.hip, mgpu.hip, and mat_ref.h on behalf of the first and the last).
+ * cg_kernels.hip, bicgstab_kernels.hip, diag_kernels.hip, panels.hip, mgpu.hip, and mat_ref.h on behalf of the first and the last).
  * Not installed.
  */
 #ifndef SPMV_HIP_COMMON_H
@@ -536,6 +536,24 @@ int cg_solve(const cg_matrix *A, int k, const double *B, int64_t ldb, double *X,
              int64_t ldx, const double *minv, double tol, int maxit,
              int check_every, void *d_work, size_t work_bytes,
              spmv_cg_info *info, hipStream_t s);
+/* the kernels every solver launches (k_cg_copy, k_cg_dot; k = 1..8): dst = src
+ * over M rows of k interleaved columns, and the partial sums of U . V in the
+ * dot order -> part[workgroup * k + column] */
+void cg_launch_copy(int k, int M, const double *src, int64_t lds, double *dst,
+                    int64_t ldd, hipStream_t s);
+void cg_launch_dot(int k, int M, const double *U, int64_t ldu, const double *V,
+                   int64_t ldv, double *part, hipStream_t s);
+
+/*
+ * BiCGStab for nonsymmetric A (bicgstab_kernels.hip; spmv_*_bicgstab): the
+ * matrix, the dot, the state block and the records of cg; minv == NULL is no
+ * preconditioner, else Z = minv .* P is what the matrix multiplies.
+ */
+int64_t bicgstab_work_bytes(int M, int k);
+int bicgstab_solve(const cg_matrix *A, int k, const double *B, int64_t ldb,
+                   double *X, int64_t ldx, const double *minv, double tol,
+                   int maxit, int check_every, void *d_work, size_t work_bytes,
+                   spmv_cg_info *info, hipStream_t s);
 
 /* out[r] = the sum of row r's stored entries in column r, or 1 / that sum,
  * r < min(M, N) (diag_kernels.hip; spmv_*_diag); the caller has checked the
