@@ -241,6 +241,58 @@ int spmv_csr_upload(const sparse_csr *A, spmv_csr_dev **out);
 int spmv_csr_upload_f32(const sparse_csr *A, spmv_csr_dev **out);
 int spmv_csr_to_f32(const spmv_csr_dev *A, spmv_csr_dev **out);
 int spmv_csr_value_bytes(const spmv_csr_dev *A); /* 8 or 4 */
+/*
+ * Transposition on the device: spmv_csr_transpose makes a NEW, ordinary CSR
+ * handle T = A^T -- N x M for an M x N source, the same NZ, the same value
+ * type (f64 or f32) -- that owns all its arrays.  A is unchanged and may be
+ * released afterwards.  Every kernel id, launch_multi, launch_axpby, diag,
+ * autotune, the blocked path, spmv_hll_from_csr, spmv_csr_to_f32 and the
+ * solvers work on T as on any handle: y = A^T x is a launch of T.
+ *
+ * THE RESULT IS DEFINED TO THE BYTE: it is the stable counting sort of A's
+ * entries, in stored order, by column.  With rows[k] the row of A's k-th
+ * stored entry and `order` the stable argsort of JA:
+ *     IRP_T[c] = number of entries with a column below c   (IRP_T[N] = NZ)
+ *     JA_T = rows[order],  AS_T = AS[order]
+ * So row c of T lists its source rows in ascending order; duplicate entries
+ * (r, c) keep their source order; values are moved, never computed (NaN
+ * payloads, infinities, -0.0 and subnormals arrive with their bits); explicit
+ * zeros stay; duplicates are NOT summed.  (A^T)^T is A with every row stably
+ * ordered by column -- A itself, byte for byte, when A's rows are sorted.  The
+ * bytes do not depend on scheduling: no position comes from an atomic.
+ *
+ * Errors, in this order: NULL A or out -EINVAL; no device -ENODEV; a dead
+ * handle -EBADF; after spmv_csr_release_source -ENODATA; a column of A
+ * outside [0, N) -EDOM; a failed allocation -ENOMEM.  On any error nothing is
+ * created and *out is NULL.  M, N or NZ may be 0 (T's IRP is then N + 1
+ * zeros).  The call blocks until T is complete.
+ *
+ * Peak device memory: T itself (4 (N + 1) + (4 + value bytes) NZ bytes and
+ * the launch tables of any handle) plus the scratch that
+ * spmv_transpose_plan reports, freed before the call returns: two buffers of
+ * 8 NZ bytes and the counters, 4 * 2^digit_bits bytes per workgroup.  spmv_transpose_plan is host arithmetic and needs no
+ * device; any out-pointer may be NULL; -EINVAL for N < 0 or NZ < 0 (or NZ
+ * beyond INT32_MAX, which no handle holds).
+ *   passes      max(1, ceil(bits(N - 1) / digit_bits)) counting sorts
+ *   tile        entries one workgroup owns in each of them
+ *   workgroups  ceil(NZ / tile)
+ *
+ * spmv_csr_symmetry: *out = 0 (none), 1 (the pattern is symmetric) or 2 (the
+ * stored values are too).  M != N gives 0.  Otherwise T = A^T and C = T^T are
+ * built and released; IRP and JA of C and T equal gives at least 1, and the
+ * stored values comparing equal with == as well gives 2: a NaN is never
+ * symmetric, -0.0 equals 0.0.  Entries are compared POSITION BY POSITION
+ * after the stable ordering; duplicates are not summed, so a matrix that
+ * stores (r, c) twice and (c, r) once is not pattern-symmetric, and two
+ * duplicates whose values are swapped in the mirror entry do not compare
+ * equal although their sums would.  Peak memory: two transposes and one
+ * scratch.  Errors as spmv_csr_transpose.  spmv_*_cg / spmv_*_pcg do not
+ * call it.
+ */
+int spmv_csr_transpose(const spmv_csr_dev *A, spmv_csr_dev **out);
+int spmv_transpose_plan(int N, int64_t NZ, int *passes, int *digit_bits,
+                        int *tile, int64_t *workgroups, int64_t *scratch_bytes);
+int spmv_csr_symmetry(const spmv_csr_dev *A, int *out);
 /* Build a synthetic matrix (spmv_synth.h) directly in device memory. */
 int spmv_csr_generate(int kind, int M, int N, int K, int64_t W, int64_t row0,
                       uint64_t seed, spmv_csr_dev **out);

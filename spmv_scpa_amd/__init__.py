@@ -528,6 +528,10 @@ _sig("spmv_dev_fill_synth", C.c_int, C.c_void_p, C.c_int64, C.c_uint64,
 _sig("spmv_csr_upload", C.c_int, _CSRp, C.POINTER(C.c_void_p))
 _sig("spmv_csr_upload_f32", C.c_int, _CSRp, C.POINTER(C.c_void_p))
 _sig("spmv_csr_to_f32", C.c_int, C.c_void_p, C.POINTER(C.c_void_p))
+_sig("spmv_csr_transpose", C.c_int, C.c_void_p, C.POINTER(C.c_void_p))
+_sig("spmv_transpose_plan", C.c_int, C.c_int, C.c_int64, _ip, _ip, _ip,
+     C.POINTER(C.c_int64), C.POINTER(C.c_int64))
+_sig("spmv_csr_symmetry", C.c_int, C.c_void_p, _ip)
 _sig("spmv_csr_generate", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
      C.c_int64, C.c_int64, C.c_uint64, C.POINTER(C.c_void_p))
 _sig("spmv_csr_launch_rows", C.c_int, C.c_void_p, C.c_int,
@@ -698,6 +702,23 @@ def bicgstab_work_bytes(M, k):
     needs: a base that depends on neither, and six vectors of 8 k M bytes"""
     return _check(_lib.spmv_bicgstab_work_bytes(int(M), int(k)),
                   "spmv_bicgstab_work_bytes")
+
+
+#: CsrDevice.symmetry()
+SYM_NONE, SYM_PATTERN, SYM_VALUES = 0, 1, 2
+
+
+def transpose_plan(N, NZ):
+    """the geometry CsrDevice.transpose() uses for a source of N columns and
+    NZ entries (host arithmetic, no device): dict(passes, digit_bits, tile,
+    workgroups, scratch_bytes)"""
+    p, d, t = C.c_int(), C.c_int(), C.c_int()
+    w, s = C.c_int64(), C.c_int64()
+    _check(_lib.spmv_transpose_plan(int(N), int(NZ), C.byref(p), C.byref(d),
+                                    C.byref(t), C.byref(w), C.byref(s)),
+           "spmv_transpose_plan")
+    return dict(passes=p.value, digit_bits=d.value, tile=t.value,
+                workgroups=w.value, scratch_bytes=s.value)
 
 
 def version():
@@ -1604,6 +1625,24 @@ class CsrDevice(_Device):
         h = C.c_void_p()
         _check(_lib.spmv_csr_to_f32(self.h, C.byref(h)), "spmv_csr_to_f32")
         return CsrDevice(h)
+
+    def transpose(self):
+        """a new N x M handle T = A^T built on the device: this handle's
+        entries in the stable order by column (spmv_engine.h), the same value
+        type; y = A^T x is a launch of T.  This handle stays valid"""
+        h = C.c_void_p()
+        _check(_lib.spmv_csr_transpose(self.h, C.byref(h)),
+               "spmv_csr_transpose")
+        return CsrDevice(h)
+
+    def symmetry(self):
+        """SYM_NONE, SYM_PATTERN or SYM_VALUES: entries compared position by
+        position after the stable ordering, duplicates not summed, values
+        with == (a NaN is never symmetric)"""
+        out = C.c_int()
+        _check(_lib.spmv_csr_symmetry(self.h, C.byref(out)),
+               "spmv_csr_symmetry")
+        return out.value
 
     @classmethod
     def generate(cls, kind, M, N, K, W, row0=0, seed=42):

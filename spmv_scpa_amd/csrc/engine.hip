@@ -27,6 +27,7 @@
 #include "mat_ref.h"
 #include "spmv_synth.h"
 #include "stream_table.h"
+#include "transpose_plan.h"
 #include "tune_blocked.h"
 #include "utils.h"
 
@@ -962,6 +963,83 @@ fail:
     (void)hipFree(d_over);
     spmv_csr_release(d);
     return rc;
+}
+
+/* the geometry a transposition of N columns and NZ entries would use
+ * (transpose_plan.h); host arithmetic, no device needed */
+int spmv_transpose_plan(int N, int64_t NZ, int *passes, int *digit_bits,
+                        int *tile, int64_t *workgroups,
+                        int64_t *scratch_bytes) {
+    transpose_plan pl;
+    int rc = transpose_plan_make(N, NZ, &pl);
+    if (rc)
+        return rc;
+    if (passes)
+        *passes = pl.passes;
+    if (digit_bits)
+        *digit_bits = pl.digit_bits;
+    if (tile)
+        *tile = pl.tile;
+    if (workgroups)
+        *workgroups = pl.workgroups;
+    if (scratch_bytes)
+        *scratch_bytes = pl.scratch_bytes;
+    return 0;
+}
+
+/* a new N x M handle: A's entries in the stable order by column
+ * (transpose_kernels.hip) */
+int spmv_csr_transpose(const spmv_csr_dev *A, spmv_csr_dev **out) {
+    if (!A || !out)
+        return -EINVAL;
+    *out = NULL;
+    if (spmv_device_count() == 0)
+        return -ENODEV; /* no handle can be live: the more useful answer */
+    HANDLE_OK(A);
+    if (!A->ja && A->NZ > 0)
+        return -ENODATA; /* spmv_csr_release_source() */
+    spmv_csr_dev *d = NULL;
+    int rc = csr_alloc_dev(A->N, A->M, A->NZ, A->value_bytes, &d);
+    if (rc)
+        return rc;
+    rc = csr_transpose_dev(A, d, 0);
+    if (rc)
+        goto fail;
+    rc = finish_csr_handle(d, NULL);
+    if (rc)
+        goto fail;
+    *out = d;
+    return 0;
+fail:
+    spmv_csr_release(d);
+    return rc;
+}
+
+/* 0: not symmetric, 1: the pattern is, 2: the stored values are too */
+int spmv_csr_symmetry(const spmv_csr_dev *A, int *out) {
+    if (!A || !out)
+        return -EINVAL;
+    *out = 0;
+    if (spmv_device_count() == 0)
+        return -ENODEV;
+    HANDLE_OK(A);
+    if (!A->ja && A->NZ > 0)
+        return -ENODATA; /* spmv_csr_release_source() */
+    if (A->M != A->N)
+        return 0;
+    spmv_csr_dev *T = NULL, *C = NULL;
+    int pattern = 0, values = 0;
+    int rc = spmv_csr_transpose(A, &T);
+    if (!rc)
+        rc = spmv_csr_transpose(T, &C);
+    if (!rc)
+        rc = csr_equal_dev(C, T, &pattern, &values, 0);
+    spmv_csr_release(C); /* NULL: ignored */
+    spmv_csr_release(T);
+    if (rc)
+        return rc;
+    *out = values ? 2 : pattern ? 1 : 0;
+    return 0;
 }
 
 int spmv_csr_generate(int kind, int M, int N, int K, int64_t W, int64_t row0,

@@ -1,7 +1,9 @@
 /*
  * hip_common.h -- internals shared by the HIP translation units
  * (engine.hip, csr_kernels.hip, hll_kernels.hip, multi_kernels.hip,
- * cg_kernels.hip, bicgstab_kernels.hip, diag_kernels.hip, panels.hip, mgpu.hip, and mat_ref.h on behalf of the first and the last).
+ * cg_kernels.hip, bicgstab_kernels.hip, diag_kernels.hip,
+ * transpose_kernels.hip, panels.hip, mgpu.hip, and mat_ref.h on behalf of the
+ * first and the last).
  * Not installed.
  */
 #ifndef SPMV_HIP_COMMON_H
@@ -560,6 +562,15 @@ int bicgstab_solve(const cg_matrix *A, int k, const double *B, int64_t ldb,
  * handle */
 int csr_diag(const spmv_csr_dev *A, double *out, int invert, hipStream_t s);
 int hll_diag(const spmv_hll_dev *H, double *out, int invert, hipStream_t s);
+
+/* T = A^T (transpose_kernels.hip; spmv_csr_transpose): T comes from
+ * csr_alloc_dev(N, M, NZ, value type of A) and gets its irp, ja and values;
+ * blocks; -EDOM when a column of A lies outside [0, N).  csr_equal_dev: two
+ * handles of one shape, entry count and value type compared element by
+ * element (spmv_csr_symmetry) */
+int csr_transpose_dev(const spmv_csr_dev *A, spmv_csr_dev *T, hipStream_t s);
+int csr_equal_dev(const spmv_csr_dev *X, const spmv_csr_dev *Y, int *pattern,
+                  int *values, hipStream_t s);
 
 /* kernel launchers (csr_kernels.hip / hll_kernels.hip) */
 int csr_launch_kernel(const spmv_csr_dev *A, int kernel, int waves, int group,
