@@ -399,8 +399,8 @@ int spmv_hll_value_bytes(const spmv_hll_dev *H); /* 8 or 4 */
  * / _kernel_bytes ((2 + value_bytes) S + 4 nb for the bases + 12 nb + 8 M +
  * 8 N), release / release_checked.  spmv_hll_build_panels*,
  * spmv_hll_launch_multi, spmv_hll_multi_bytes, spmv_hll_launch_axpby,
- * spmv_hll_axpby_bytes, spmv_hll_cg, spmv_hll_pcg, spmv_hll_bicgstab and
- * spmv_hll_diag: -ENOTSUP.  The handle owns
+ * spmv_hll_axpby_bytes, spmv_hll_cg, spmv_hll_pcg, spmv_hll_bicgstab,
+ * spmv_hll_cgls (in either position) and spmv_hll_diag: -ENOTSUP.  The handle owns
  * no 4-byte JA and no pad bitmap.  The one-shot seam, the reference ABI names
  * and spmv_mgpu.h create 4-byte handles only.
  */
@@ -815,6 +815,95 @@ int spmv_hll_bicgstab(const spmv_hll_dev *H, const spmv_launch_opts *opts,
                       double tol, int maxit, int check_every,
                       void *d_work, size_t work_bytes,
                       spmv_cg_info *info, void *stream);
+
+/*
+ * CGLS on the device for rectangular least squares (added after 0.7;
+ * spmv_version() is unchanged, detect it by the symbol): per column,
+ *   min ||A x - b||^2 + damp^2 ||x||^2,
+ * that is min ||A x - b|| for a tall A, the minimum-norm solution for a wide
+ * one (from d_X = 0), and the Tikhonov-regularised problem for damp > 0.
+ * Bjorck's form: A^T A is never formed.  A is M x N and AT is N x M, its
+ * transpose as a handle of its own (spmv_csr_transpose, and spmv_hll_from_csr
+ * of that for an HLL pair); both CSR or both column-major HLL, each of either
+ * value type.  That AT really is the transpose of A is NOT checked, just as
+ * spmv_*_cg does not check symmetry: only the shapes are.  One iteration is
+ * one launch_multi of A and one of AT.
+ *
+ * d_B has M rows and d_X has N rows, both of k = 1..8 interleaved columns as
+ * in spmv_*_launch_multi (ldb, ldx >= k, 0 = k).  d_X holds the initial guess
+ * on entry and the iterate on return; d_B is never written.  damp >= 0.
+ *
+ * Both handles are checked by the function that serves launch_multi, A first,
+ * with its answers (NULL -EINVAL, dead handle -EBADF / -ENODEV, compact handle
+ * -ENOTSUP, row-major HLL -EINVAL, after spmv_*_release_source() -ENODATA);
+ * the one `opts` is validated against both handles and used for both
+ * products.  Then -EINVAL: AT->M != A->N or AT->N != A->M, damp or tol
+ * negative or NaN, maxit < 0, check_every < 0, NULL info, a d_work that is not
+ * 8-byte aligned or holds fewer than spmv_cgls_work_bytes(M, N, k) bytes.
+ * M == 0 or N == 0: returns 0 with every record zeroed and nothing enqueued.
+ * The blocking, -EBUSY on a capturing stream before anything is allocated or
+ * enqueued, check_every (0 = 8) and a NULL d_work (the library allocates and
+ * frees it) are those of spmv_*_cg above, word for word.
+ * spmv_cgls_work_bytes(M, N, k) = a base that depends on no argument (the
+ * state block, three sets of partial sums) + 8 * k * (2 M + 2 N): R and Q of
+ * M rows, S and P of N rows.
+ *
+ * Result contract, to the bit.  Every operation is rounded once, no fused
+ * multiply-add, divisions are correctly rounded; dot_L(U, V) is the dot of
+ * spmv_cg_dot_shape over L rows, its order a function of that length alone;
+ * tol2 = tol * tol and d2 = damp * damp on the host.  With damp == 0 there is
+ * no d2 term at all (the lines marked `damp:` do not exist): another
+ * instantiation of the kernels, not a multiplication by zero.
+ *
+ *   R = B;  R = (-1) A X + 1 R   by A's launch_axpby              (M rows)
+ *   W = AT B  by AT's launch_multi;  atb = dot_N(W, W)
+ *   S = AT R  by AT's launch_multi;  damp: S = S - d2 * X         (N rows)
+ *   P = S;  ss = dot_N(S, S)
+ *   column j: status 2 (iterations 0) if ss or atb is not finite,
+ *             else converged (iterations 0) if ss <= tol2 * atb, else running
+ *   repeat at most maxit times:
+ *       Q = A P  by A's launch_multi (all k columns, the caller's opts)
+ *       delta = dot_M(Q, Q);   damp: delta = delta + d2 * dot_N(P, P)
+ *       running column with !(delta > 0 and finite): status 2, frozen
+ *       running column: alpha = ss / delta;  X = X + alpha * P;
+ *                       R = R - alpha * Q;  iterations += 1
+ *       S = AT R  by AT's launch_multi;   damp: S = S - d2 * X
+ *       sn = dot_N(S, S)
+ *       running column: sn <= tol2 * atb -> status 0, frozen (ss = sn)
+ *                       sn not finite    -> status 2, frozen
+ *       running column: beta = sn / ss;  P = S + beta * P;  ss = sn
+ *   columns still running: status 1
+ *   rr = dot_M(R, R), once, after the loop, for every column
+ *
+ * X, R, P, ss, the status and the count of a frozen column are never written
+ * again; S and Q are scratch, the products rewrite all k columns of them.  So
+ * X and the records do not depend on check_every, on who owns the work buffer,
+ * on waves_per_block or on the other columns, and column j of a k-column solve
+ * has the bits of the k = 1 solve of that column.  ss is tested against atb,
+ * not against r.r: a b orthogonal to the range of A (atb == 0) is converged
+ * at once with X untouched.
+ */
+typedef struct spmv_cgls_info {
+    int status;      /* 0 converged, 1 maxit reached, 2 breakdown */
+    int iterations;  /* updates of x applied to this column */
+    double ss;       /* last s.s of the recurrence, s = A^T r - damp^2 x */
+    double atb;      /* (A^T b).(A^T b): what ss is tested against */
+    double rr;       /* r.r of the recurrence's R when the call returns */
+} spmv_cgls_info;
+
+int64_t spmv_cgls_work_bytes(int M, int N, int k); /* -EINVAL: M < 0, N < 0, k outside 1..8 */
+int spmv_csr_cgls(const spmv_csr_dev *A, const spmv_csr_dev *AT,
+                  const spmv_launch_opts *opts, int k,
+                  const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                  double damp, double tol, int maxit, int check_every,
+                  void *d_work, size_t work_bytes,
+                  spmv_cgls_info *info, void *stream);
+int spmv_hll_cgls(const spmv_hll_dev *H, const spmv_hll_dev *HT,
+                  const spmv_launch_opts *opts, int k,
+                  const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                  double damp, double tol, int maxit, int check_every,
+                  void *d_work, size_t work_bytes,
+                  spmv_cgls_info *info, void *stream);
 
 /*
  * Pick the fastest kernel for this matrix by measurement (5 launches each):

@@ -404,6 +404,12 @@ class CgInfo(C.Structure):
                 ("rr", C.c_double), ("bb", C.c_double)]
 
 
+class CglsInfo(C.Structure):
+    """spmv_cgls_info (include/spmv_engine.h): one column of a cgls() solve"""
+    _fields_ = [("status", C.c_int), ("iterations", C.c_int),
+                ("ss", C.c_double), ("atb", C.c_double), ("rr", C.c_double)]
+
+
 _CSRp = C.POINTER(SparseCSR)
 _HLLp = C.POINTER(SparseHLL)
 
@@ -554,6 +560,7 @@ _sig("spmv_cg_work_bytes", C.c_int64, C.c_int, C.c_int)
 _sig("spmv_cg_dot_shape", None, _ip, _ip)
 _sig("spmv_pcg_work_bytes", C.c_int64, C.c_int, C.c_int)
 _sig("spmv_bicgstab_work_bytes", C.c_int64, C.c_int, C.c_int)
+_sig("spmv_cgls_work_bytes", C.c_int64, C.c_int, C.c_int, C.c_int)
 # spmv_csr_<name> and spmv_hll_<name>: the same argument types
 _TWINS = (
     ("release_checked", None, C.c_void_p, C.c_uint64),
@@ -604,6 +611,10 @@ _TWINS = (
      C.c_void_p, C.POINTER(LaunchOpts), C.c_int, C.c_void_p, C.c_int64,
      C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_int, C.c_int,
      C.c_void_p, C.c_size_t, C.POINTER(CgInfo), C.c_void_p),
+    ("cgls", C.c_int,
+     C.c_void_p, C.c_void_p, C.POINTER(LaunchOpts), C.c_int, C.c_void_p,
+     C.c_int64, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int,
+     C.c_int, C.c_void_p, C.c_size_t, C.POINTER(CglsInfo), C.c_void_p),
     ("diag", C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p),
     ("time", C.c_int,
      C.c_void_p, C.c_int, C.POINTER(LaunchOpts), C.c_void_p, C.c_void_p,
@@ -702,6 +713,19 @@ def bicgstab_work_bytes(M, k):
     needs: a base that depends on neither, and six vectors of 8 k M bytes"""
     return _check(_lib.spmv_bicgstab_work_bytes(int(M), int(k)),
                   "spmv_bicgstab_work_bytes")
+
+
+#: one column of a cgls() solve
+CglsResult = collections.namedtuple("CglsResult",
+                                    "status iterations ss atb rr")
+
+
+def cgls_work_bytes(M, N, k):
+    """bytes of device memory one cgls() solve of k problems with an M x N
+    matrix needs: a base that depends on none of them, and 8 k (2 M + 2 N)
+    for R, Q (M rows) and S, P (N rows)"""
+    return _check(_lib.spmv_cgls_work_bytes(int(M), int(N), int(k)),
+                  "spmv_cgls_work_bytes")
 
 
 #: CsrDevice.symmetry()
@@ -1483,6 +1507,40 @@ class _Device:
                    work.ptr if work is not None else None,
                    work.nbytes if work is not None else 0, info, stream)
         return [CgResult(i.status, i.iterations, i.rr, i.bb) for i in info]
+
+    def cgls(self, dAT, d_B, d_X, k=1, damp=0.0, tol=1e-8, maxit=1000,
+             check_every=0, ldb=0, ldx=0, work=None, waves_per_block=0,
+             group=0, stream=None):
+        """CGLS for min ||A X - B||^2 + damp^2 ||X||^2 on the device, A this
+        M x N handle (any shape) and dAT its N x M transpose as a handle of
+        the same class: transpose() for a CSR pair, transpose().to_hll(True)
+        for an HLL pair.  That dAT is the transpose is not checked, only its
+        shape.  d_B has M rows and d_X has N rows of k = 1..8 interleaved
+        columns (ldb, ldx >= k or 0); d_X holds the initial guess (zero gives
+        the minimum-norm solution of a wide A) and receives the iterate, d_B
+        is not written.  Stops a column when s.s <= tol^2 (A^T b).(A^T b)
+        with s = A^T r - damp^2 x, after maxit iterations, or on a breakdown
+        (delta not positive, a non-finite scalar).  The blocking, check_every
+        and `work` (at least cgls_work_bytes(M, N, k) bytes) as cg().
+        -> [CglsResult(status, iterations, ss, atb, rr)] * k"""
+        k, ldb, ldx = int(k), int(ldb), int(ldx)
+        if not 1 <= k <= 8:
+            raise ValueError("k=%r: 1..8 problems per solve" % (k,))
+        if (ldb and ldb < k) or (ldx and ldx < k):
+            raise ValueError("ldb=%d, ldx=%d: at least k=%d (or 0)"
+                             % (ldb, ldx, k))
+        if type(dAT) is not type(self):
+            raise TypeError("cgls: the transpose must be a %s like the "
+                            "matrix, not %r" % (type(self).__name__,
+                                                type(dAT).__name__))
+        o = _opts(waves_per_block, group if self._FMT == "csr" else 0)
+        info = (CglsInfo * k)()
+        self._call("cgls", dAT.h, C.byref(o), k, d_B, ldb, d_X, ldx,
+                   float(damp), float(tol), int(maxit), int(check_every),
+                   work.ptr if work is not None else None,
+                   work.nbytes if work is not None else 0, info, stream)
+        return [CglsResult(i.status, i.iterations, i.ss, i.atb, i.rr)
+                for i in info]
 
     def diag(self, d_out, invert=False, stream=None):
         """d_out[r] = the fp64 sum of the stored entries of row r in column

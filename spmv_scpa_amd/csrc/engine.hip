@@ -1914,6 +1914,36 @@ static int bicgstab(const D *d, const spmv_launch_opts *opts, int k,
                           info, (hipStream_t)stream);
 }
 
+/* CGLS (cgls_kernels.hip): both handles go through cg's checks, A first, with
+ * the one opts; that AT is the transpose of A is not checked, only its shape */
+template <typename D>
+static int cgls(const D *d, const D *dt, const spmv_launch_opts *opts, int k,
+                const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                double damp, double tol, int maxit, int check_every,
+                void *d_work, size_t work_bytes, spmv_cgls_info *info,
+                void *stream) {
+    int64_t ldb_t = ldb, ldx_t = ldx;
+    const int rc = multi_check(d, opts, k, d_B, &ldb, d_X, &ldx);
+    if (rc < 0)
+        return rc;
+    const int rct = multi_check(dt, opts, k, d_B, &ldb_t, d_X, &ldx_t);
+    if (rct < 0)
+        return rct;
+    if (dt->M != d->N || dt->N != d->M || !(damp >= 0.0) || !(tol >= 0.0) ||
+        maxit < 0 || check_every < 0 || !info)
+        return -EINVAL;
+    if (rc || rct) { /* no rows or no columns */
+        for (int j = 0; j < k; ++j)
+            info[j] = spmv_cgls_info{0, 0, 0.0, 0.0, 0.0};
+        return 0;
+    }
+    const cg_matrix A = {d, opts, d->M, cg_multi_of<D>, cg_axpby_of<D>};
+    const cg_matrix AT = {dt, opts, dt->M, cg_multi_of<D>, cg_axpby_of<D>};
+    return cgls_solve(&A, &AT, k, d_B, ldb, d_X, ldx, damp, tol, maxit,
+                      check_every ? check_every : 8, d_work, work_bytes, info,
+                      (hipStream_t)stream);
+}
+
 /* ---- the diagonal (diag_kernels.hip): launch_multi's handle checks ---- */
 static int diag_direct(const spmv_csr_dev *A, double *out, int invert,
                        hipStream_t s) {
@@ -2556,6 +2586,15 @@ static int copy_tune_log(const D *d, char *buf, size_t len) {
         return bicgstab(d, opts, k, d_B, ldb, d_X, ldx, d_minv, tol, maxit,    \
                         check_every, d_work, work_bytes, info, stream);        \
     }                                                                          \
+    int spmv_##fmt##_cgls(const D *d, const D *dt,                             \
+                          const spmv_launch_opts *opts, int k,                 \
+                          const double *d_B, int64_t ldb, double *d_X,         \
+                          int64_t ldx, double damp, double tol, int maxit,     \
+                          int check_every, void *d_work, size_t work_bytes,    \
+                          spmv_cgls_info *info, void *stream) {                \
+        return cgls(d, dt, opts, k, d_B, ldb, d_X, ldx, damp, tol, maxit,      \
+                    check_every, d_work, work_bytes, info, stream);            \
+    }                                                                          \
     int spmv_##fmt##_diag(const D *d, double *d_out, int invert,               \
                           void *stream) {                                      \
         return diag(d, d_out, invert, stream);                                 \
@@ -2632,6 +2671,9 @@ int64_t spmv_cg_work_bytes(int M, int k) { return cg_work_bytes(M, k, 0); }
 int64_t spmv_pcg_work_bytes(int M, int k) { return cg_work_bytes(M, k, 1); }
 int64_t spmv_bicgstab_work_bytes(int M, int k) {
     return bicgstab_work_bytes(M, k);
+}
+int64_t spmv_cgls_work_bytes(int M, int N, int k) {
+    return cgls_work_bytes(M, N, k);
 }
 void spmv_cg_dot_shape(int *workgroups, int *threads) {
     if (workgroups)

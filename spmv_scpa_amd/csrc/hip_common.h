@@ -1,7 +1,7 @@
 /*
  * hip_common.h -- internals shared by the HIP translation units
  * (engine.hip, csr_kernels.hip, hll_kernels.hip, multi_kernels.hip,
- * cg_kernels.hip, bicgstab_kernels.hip, diag_kernels.hip,
+ * cg_kernels.hip, bicgstab_kernels.hip, cgls_kernels.hip, diag_kernels.hip,
  * transpose_kernels.hip, panels.hip, mgpu.hip, and mat_ref.h on behalf of the
  * first and the last).
  * Not installed.
@@ -556,6 +556,17 @@ int bicgstab_solve(const cg_matrix *A, int k, const double *B, int64_t ldb,
                    double *X, int64_t ldx, const double *minv, double tol,
                    int maxit, int check_every, void *d_work, size_t work_bytes,
                    spmv_cg_info *info, hipStream_t s);
+
+/*
+ * CGLS for rectangular least squares (cgls_kernels.hip; spmv_*_cgls): A is
+ * M x N (A->M rows), AT its N x M transpose (AT->M = N rows); the dot, the
+ * state block and the host loop of cg, with vectors of both lengths.
+ */
+int64_t cgls_work_bytes(int M, int N, int k);
+int cgls_solve(const cg_matrix *A, const cg_matrix *AT, int k, const double *B,
+               int64_t ldb, double *X, int64_t ldx, double damp, double tol,
+               int maxit, int check_every, void *d_work, size_t work_bytes,
+               spmv_cgls_info *info, hipStream_t s);
 
 /* out[r] = the sum of row r's stored entries in column r, or 1 / that sum,
  * r < min(M, N) (diag_kernels.hip; spmv_*_diag); the caller has checked the
