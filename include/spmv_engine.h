@@ -400,8 +400,8 @@ int spmv_hll_value_bytes(const spmv_hll_dev *H); /* 8 or 4 */
  * 8 N), release / release_checked.  spmv_hll_build_panels*,
  * spmv_hll_launch_multi, spmv_hll_multi_bytes, spmv_hll_launch_axpby,
  * spmv_hll_axpby_bytes, spmv_hll_cg, spmv_hll_pcg, spmv_hll_bicgstab,
- * spmv_hll_cgls (in either position) and spmv_hll_diag: -ENOTSUP.  The handle owns
- * no 4-byte JA and no pad bitmap.  The one-shot seam, the reference ABI names
+ * spmv_hll_cgls (in either position), spmv_hll_minres and spmv_hll_diag:
+ * -ENOTSUP.  The handle owns no 4-byte JA and no pad bitmap.  The one-shot seam, the reference ABI names
  * and spmv_mgpu.h create 4-byte handles only.
  */
 int spmv_hll_to_index16(const spmv_hll_dev *H, spmv_hll_dev **out);
@@ -904,6 +904,105 @@ int spmv_hll_cgls(const spmv_hll_dev *H, const spmv_hll_dev *HT,
                   double damp, double tol, int maxit, int check_every,
                   void *d_work, size_t work_bytes,
                   spmv_cgls_info *info, void *stream);
+
+/*
+ * MINRES on the device for A X = B with a symmetric A that need not be
+ * definite: KKT and saddle-point matrices, shifted stencils (added after 0.7;
+ * spmv_version() is unchanged, detect it by the symbol).  A: square and
+ * symmetric -- symmetry is NOT checked, as in spmv_*_cg -- a CSR or
+ * column-major HLL handle of either value type.  One launch_multi per
+ * iteration and a three-term recurrence (Paige and Saunders); the residual
+ * norm of the recurrence falls monotonically.  k = 1..8 independent systems
+ * stored interleaved as in spmv_*_launch_multi.
+ *
+ * d_minv: M doubles, one per row, shared by the k columns, never written: a
+ * diagonal preconditioner, z(u)_i = minv_i * u_i.  It must be POSITIVE where
+ * given (a column whose u.z(u) is negative or not finite is a breakdown);
+ * spmv_*_diag(invert = 1) gives Jacobi where the diagonal is positive, a
+ * saddle-point caller passes 1 / |d| with 1 where d == 0.  NULL: none.
+ *
+ * d_X, d_B, the strides, the blocking, -EBUSY on a capturing stream before
+ * anything is allocated or enqueued, check_every (0 = 8), maxit, d_work (NULL:
+ * the library allocates and frees it; else 8-byte aligned and at least
+ * spmv_minres_work_bytes(M, k) bytes, else -EINVAL), M == 0 (returns 0 with
+ * zeroed records) and the argument checks (the handle, opts, k, strides and
+ * pointers by the function that serves launch_multi; M != N, a negative or NaN
+ * tol, maxit < 0, check_every < 0, NULL info: -EINVAL) are those of
+ * spmv_*_bicgstab above, word for word.  spmv_minres_work_bytes(M, k) = a base
+ * that depends on neither argument (the state block, three sets of partial
+ * sums) + 6 * 8 * k * M: two residual buffers, V, Q and two direction
+ * buffers.  The host rotates the two pairs by the parity of the iteration
+ * number, which all columns share: nothing is copied.
+ *
+ * Result contract, to the bit.  Every operation is rounded once, no fused
+ * multiply-add crosses a * and a +, divisions and square roots are correctly
+ * rounded; dot is the dot of spmv_cg_dot_shape; z(U)_i = rn(minv_i * u_i) in
+ * every column, U itself without d_minv; tol2 = tol * tol on the host.
+ *
+ *   R2 = B;  R2 = (-1) A X + 1 R2  by the handle's launch_axpby;  W1 = W2 = +0.0
+ *   bb = dot(B, B);  bn2 = dot(B, z(B));  b1 = dot(R2, z(R2))
+ *   column j: status 2 (iterations 0) if !(b1 >= 0 and finite) or !(bn2 >= 0 and finite),
+ *             else converged (iterations 0) if b1 <= tol2 * bn2, else running with
+ *             beta = sqrt(b1); phibar = beta; dbar = 0; epsln = 0; cs = -1; sn = 0
+ *   repeat at most maxit times, i = 1, 2, ...:
+ *       s = 1 / beta;  V = s * z(R2)                    (rn(s * rn(minv_i * r_i)))
+ *       Q = A V   by launch_multi (all k columns, the caller's opts)
+ *       i >= 2:  Q = Q - (beta / oldb) * R1             (i == 1: the term does not exist --
+ *                                                        another instantiation, not a zero)
+ *       alfa = dot(V, Q)
+ *       running column with alfa not finite: status 2, frozen
+ *       Rn = Q - (alfa / beta) * R2;   bnew = dot(Rn, z(Rn));   R1 = R2;  R2 = Rn
+ *       running column with !(bnew >= 0 and finite): status 2, frozen
+ *       oldb = beta;  beta = sqrt(bnew);  oldeps = epsln
+ *       delta = cs*dbar + sn*alfa;  gbar = sn*dbar - cs*alfa;  epsln = sn*beta;  dbar = -(cs*beta)
+ *       gamma = sqrt(gbar*gbar + beta*beta)
+ *       running column with !(gamma > 0 and finite): status 2, frozen
+ *       cs = gbar/gamma;  sn = beta/gamma;  phi = cs*phibar;  phibar = sn*phibar
+ *       Wn = ((V - oldeps*W1) - delta*W2) / gamma;  W1 = W2;  W2 = Wn
+ *       X = X + phi*Wn;  iterations += 1;  pp = phibar*phibar
+ *       running column: pp <= tol2 * bn2 -> status 0, frozen;  pp not finite -> status 2, frozen
+ *   columns still running: status 1
+ *   R = B - A X by launch_axpby;  rr = dot(R, R), once, for every column
+ *
+ * pp of a column that made no iteration is b1.  The W recurrence is the same
+ * three-term expression in every iteration, the first two included: the zero
+ * buffers are read and multiplied, so the sign of a zero is what the
+ * arithmetic gives.  A column frozen before the X update of an iteration does
+ * not get that update.  X, iterations, status and pp of a frozen column are
+ * never written again, however many iterations were enqueued after it stopped
+ * and whatever the other columns hold.  So the results do not depend on
+ * check_every, on who owns the work buffer, on waves_per_block or on the other
+ * columns, and column j of a k-column solve has the bits of the k = 1 solve
+ * of that column.  d_minv of all 1.0 gives the bits of d_minv == NULL.
+ * beta == 0 has no rule of its own: phibar becomes 0 and the column converges
+ * in that step.  The internal vectors are not observable.  The stopping test
+ * is in the norm the recurrence has, the M^-1 norm (the 2-norm without a
+ * preconditioner); rr and bb give the caller the true figure.
+ */
+typedef struct spmv_minres_info {
+    int status;      /* 0 converged, 1 maxit reached, 2 breakdown */
+    int iterations;  /* updates of x applied to this column */
+    double pp;       /* last phibar*phibar: the recurrence's residual estimate, squared, in the M^-1 norm */
+    double bn2;      /* dot(B, z(B)): what pp is tested against */
+    double rr;       /* true r.r, r = b - A x, computed once when the call returns */
+    double bb;       /* b.b */
+} spmv_minres_info;
+
+int64_t spmv_minres_work_bytes(int M, int k); /* -EINVAL: M < 0, k outside 1..8 */
+int spmv_csr_minres(const spmv_csr_dev *A, const spmv_launch_opts *opts, int k,
+                    const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                    const double *d_minv, double tol, int maxit,
+                    int check_every, void *d_work, size_t work_bytes,
+                    spmv_minres_info *info, void *stream);
+int spmv_hll_minres(const spmv_hll_dev *H, const spmv_launch_opts *opts, int k,
+                    const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                    const double *d_minv, double tol, int maxit,
+                    int check_every, void *d_work, size_t work_bytes,
+                    spmv_minres_info *info, void *stream);
+/* TEST HOOK: d_out[i] = the square root the MINRES kernels take of d_in[i],
+ * i < n, asynchronous on `stream` (-EINVAL: n < 0, a NULL pointer with n > 0);
+ * the contract asks for the correctly rounded one */
+int spmv_debug_sqrt(const double *d_in, double *d_out, int64_t n, void *stream);
 
 /*
  * Pick the fastest kernel for this matrix by measurement (5 launches each):

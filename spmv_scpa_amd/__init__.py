@@ -410,6 +410,14 @@ class CglsInfo(C.Structure):
                 ("ss", C.c_double), ("atb", C.c_double), ("rr", C.c_double)]
 
 
+class MinresInfo(C.Structure):
+    """spmv_minres_info (include/spmv_engine.h): one column of a minres()
+    solve"""
+    _fields_ = [("status", C.c_int), ("iterations", C.c_int),
+                ("pp", C.c_double), ("bn2", C.c_double), ("rr", C.c_double),
+                ("bb", C.c_double)]
+
+
 _CSRp = C.POINTER(SparseCSR)
 _HLLp = C.POINTER(SparseHLL)
 
@@ -561,6 +569,9 @@ _sig("spmv_cg_dot_shape", None, _ip, _ip)
 _sig("spmv_pcg_work_bytes", C.c_int64, C.c_int, C.c_int)
 _sig("spmv_bicgstab_work_bytes", C.c_int64, C.c_int, C.c_int)
 _sig("spmv_cgls_work_bytes", C.c_int64, C.c_int, C.c_int, C.c_int)
+_sig("spmv_minres_work_bytes", C.c_int64, C.c_int, C.c_int)
+_sig("spmv_debug_sqrt", C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
+     C.c_void_p)
 # spmv_csr_<name> and spmv_hll_<name>: the same argument types
 _TWINS = (
     ("release_checked", None, C.c_void_p, C.c_uint64),
@@ -615,6 +626,10 @@ _TWINS = (
      C.c_void_p, C.c_void_p, C.POINTER(LaunchOpts), C.c_int, C.c_void_p,
      C.c_int64, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int,
      C.c_int, C.c_void_p, C.c_size_t, C.POINTER(CglsInfo), C.c_void_p),
+    ("minres", C.c_int,
+     C.c_void_p, C.POINTER(LaunchOpts), C.c_int, C.c_void_p, C.c_int64,
+     C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_int, C.c_int,
+     C.c_void_p, C.c_size_t, C.POINTER(MinresInfo), C.c_void_p),
     ("diag", C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p),
     ("time", C.c_int,
      C.c_void_p, C.c_int, C.POINTER(LaunchOpts), C.c_void_p, C.c_void_p,
@@ -726,6 +741,18 @@ def cgls_work_bytes(M, N, k):
     for R, Q (M rows) and S, P (N rows)"""
     return _check(_lib.spmv_cgls_work_bytes(int(M), int(N), int(k)),
                   "spmv_cgls_work_bytes")
+
+
+#: one column of a minres() solve
+MinresResult = collections.namedtuple("MinresResult",
+                                      "status iterations pp bn2 rr bb")
+
+
+def minres_work_bytes(M, k):
+    """bytes of device memory one minres() solve of k systems with M rows
+    needs: a base that depends on neither, and six vectors of 8 k M bytes"""
+    return _check(_lib.spmv_minres_work_bytes(int(M), int(k)),
+                  "spmv_minres_work_bytes")
 
 
 #: CsrDevice.symmetry()
@@ -1490,10 +1517,33 @@ class _Device:
                         check_every, ldb, ldx, work, waves_per_block, group,
                         stream)
 
+    def minres(self, d_B, d_X, k=1, d_minv=None, tol=1e-8, maxit=1000,
+               check_every=0, ldb=0, ldx=0, work=None, waves_per_block=0,
+               group=0, stream=None):
+        """MINRES for A X = B on the device, A square and symmetric, definite
+        or not (KKT and saddle-point matrices, shifted stencils; symmetry is
+        not checked): one product per iteration and a residual estimate that
+        never grows.  k, the layout, d_X / d_B, the blocking, check_every and
+        `work` (at least minres_work_bytes(M, k) bytes) as cg().  d_minv: M
+        doubles of a POSITIVE diagonal preconditioner, never written
+        (diag(d_minv, invert=True) where the diagonal is positive; 1 / |d|
+        with 1 where d == 0 for a saddle point); None: none, with the bits a
+        vector of ones gives.  Stops a column when pp <= tol^2 bn2 -- pp the
+        recurrence's squared residual estimate, bn2 = b.z(b), both in the
+        norm of the preconditioner -- after maxit iterations, or on a
+        breakdown (u.z(u) negative, a non-finite scalar, gamma == 0).  rr is
+        the true r.r of b - A x, computed once at the end.
+        -> [MinresResult(status, iterations, pp, bn2, rr, bb)] * k"""
+        return self._cg("minres", d_B, d_X, (d_minv,), k, tol, maxit,
+                        check_every, ldb, ldx, work, waves_per_block, group,
+                        stream, MinresInfo, MinresResult)
+
     def _cg(self, name, d_B, d_X, minv, k, tol, maxit, check_every, ldb, ldx,
-            work, waves_per_block, group, stream):
-        """cg(), pcg() and bicgstab(): `minv` is () or (d_minv,), the
-        argument spmv_*_cg does not take"""
+            work, waves_per_block, group, stream, record=CgInfo,
+            result=CgResult):
+        """cg(), pcg(), bicgstab() and minres(): `minv` is () or (d_minv,),
+        the argument spmv_*_cg does not take; `record` / `result`: the C
+        record of the solver and the namedtuple with its fields"""
         k, ldb, ldx = int(k), int(ldb), int(ldx)
         if not 1 <= k <= 8:
             raise ValueError("k=%r: 1..8 systems per solve" % (k,))
@@ -1501,12 +1551,13 @@ class _Device:
             raise ValueError("ldb=%d, ldx=%d: at least k=%d (or 0)"
                              % (ldb, ldx, k))
         o = _opts(waves_per_block, group if self._FMT == "csr" else 0)
-        info = (CgInfo * k)()
+        info = (record * k)()
         self._call(name, C.byref(o), k, d_B, ldb, d_X, ldx, *minv, float(tol),
                    int(maxit), int(check_every),
                    work.ptr if work is not None else None,
                    work.nbytes if work is not None else 0, info, stream)
-        return [CgResult(i.status, i.iterations, i.rr, i.bb) for i in info]
+        return [result(*(getattr(i, f) for f in result._fields))
+                for i in info]
 
     def cgls(self, dAT, d_B, d_X, k=1, damp=0.0, tol=1e-8, maxit=1000,
              check_every=0, ldb=0, ldx=0, work=None, waves_per_block=0,

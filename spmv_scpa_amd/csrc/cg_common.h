@@ -1,8 +1,8 @@
 /*
  * cg_common.h -- what the device-resident solvers share (cg_kernels.hip:
  * spmv_*_cg / spmv_*_pcg; bicgstab_kernels.hip: spmv_*_bicgstab;
- * cgls_kernels.hip: spmv_*_cgls): the tile of
- * a vector kernel, the two halving trees of the dot order, the finite test
+ * cgls_kernels.hip: spmv_*_cgls; minres_kernels.hip: spmv_*_minres): the tile
+ * of a vector kernel, the two halving trees of the dot order, the finite test
  * and the launch macros.  One text, included by these files; the two kernels
  * every solver launches (k_cg_copy, k_cg_dot) stay in cg_kernels.hip and are
  * reached through cg_launch_copy / cg_launch_dot (hip_common.h), so they exist

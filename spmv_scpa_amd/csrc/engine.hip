@@ -1944,6 +1944,30 @@ static int cgls(const D *d, const D *dt, const spmv_launch_opts *opts, int k,
                       (hipStream_t)stream);
 }
 
+/* MINRES (minres_kernels.hip): bicgstab's checks and cg's view of the matrix;
+ * d_minv may be NULL (no preconditioner) */
+template <typename D>
+static int minres(const D *d, const spmv_launch_opts *opts, int k,
+                  const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                  const double *d_minv, double tol, int maxit, int check_every,
+                  void *d_work, size_t work_bytes, spmv_minres_info *info,
+                  void *stream) {
+    const int rc = multi_check(d, opts, k, d_B, &ldb, d_X, &ldx);
+    if (rc < 0)
+        return rc;
+    if (d->M != d->N || !(tol >= 0.0) || maxit < 0 || check_every < 0 || !info)
+        return -EINVAL;
+    if (rc) { /* no rows */
+        for (int j = 0; j < k; ++j)
+            info[j] = spmv_minres_info{0, 0, 0.0, 0.0, 0.0, 0.0};
+        return 0;
+    }
+    const cg_matrix A = {d, opts, d->M, cg_multi_of<D>, cg_axpby_of<D>};
+    return minres_solve(&A, k, d_B, ldb, d_X, ldx, d_minv, tol, maxit,
+                        check_every ? check_every : 8, d_work, work_bytes,
+                        info, (hipStream_t)stream);
+}
+
 /* ---- the diagonal (diag_kernels.hip): launch_multi's handle checks ---- */
 static int diag_direct(const spmv_csr_dev *A, double *out, int invert,
                        hipStream_t s) {
@@ -2595,6 +2619,15 @@ static int copy_tune_log(const D *d, char *buf, size_t len) {
         return cgls(d, dt, opts, k, d_B, ldb, d_X, ldx, damp, tol, maxit,      \
                     check_every, d_work, work_bytes, info, stream);            \
     }                                                                          \
+    int spmv_##fmt##_minres(const D *d, const spmv_launch_opts *opts, int k,   \
+                            const double *d_B, int64_t ldb, double *d_X,       \
+                            int64_t ldx, const double *d_minv, double tol,     \
+                            int maxit, int check_every, void *d_work,          \
+                            size_t work_bytes, spmv_minres_info *info,         \
+                            void *stream) {                                    \
+        return minres(d, opts, k, d_B, ldb, d_X, ldx, d_minv, tol, maxit,      \
+                      check_every, d_work, work_bytes, info, stream);          \
+    }                                                                          \
     int spmv_##fmt##_diag(const D *d, double *d_out, int invert,               \
                           void *stream) {                                      \
         return diag(d, d_out, invert, stream);                                 \
@@ -2674,6 +2707,13 @@ int64_t spmv_bicgstab_work_bytes(int M, int k) {
 }
 int64_t spmv_cgls_work_bytes(int M, int N, int k) {
     return cgls_work_bytes(M, N, k);
+}
+int64_t spmv_minres_work_bytes(int M, int k) {
+    return minres_work_bytes(M, k);
+}
+int spmv_debug_sqrt(const double *d_in, double *d_out, int64_t n,
+                    void *stream) {
+    return minres_debug_sqrt(d_in, d_out, n, (hipStream_t)stream);
 }
 void spmv_cg_dot_shape(int *workgroups, int *threads) {
     if (workgroups)

@@ -1,9 +1,9 @@
 /*
  * hip_common.h -- internals shared by the HIP translation units
  * (engine.hip, csr_kernels.hip, hll_kernels.hip, multi_kernels.hip,
- * cg_kernels.hip, bicgstab_kernels.hip, cgls_kernels.hip, diag_kernels.hip,
- * transpose_kernels.hip, panels.hip, mgpu.hip, and mat_ref.h on behalf of the
- * first and the last).
+ * cg_kernels.hip, bicgstab_kernels.hip, cgls_kernels.hip, minres_kernels.hip,
+ * diag_kernels.hip, transpose_kernels.hip, panels.hip, mgpu.hip, and
+ * mat_ref.h on behalf of the first and the last).
  * Not installed.
  */
 #ifndef SPMV_HIP_COMMON_H
@@ -567,6 +567,20 @@ int cgls_solve(const cg_matrix *A, const cg_matrix *AT, int k, const double *B,
                int64_t ldb, double *X, int64_t ldx, double damp, double tol,
                int maxit, int check_every, void *d_work, size_t work_bytes,
                spmv_cgls_info *info, hipStream_t s);
+
+/*
+ * MINRES for symmetric, possibly indefinite A (minres_kernels.hip;
+ * spmv_*_minres): the matrix, the dot and the host loop of cg, a state block
+ * of its own; minv == NULL is no preconditioner, else a positive diagonal.
+ * minres_debug_sqrt: out[i] = the solver's square root of in[i] (test hook).
+ */
+int64_t minres_work_bytes(int M, int k);
+int minres_solve(const cg_matrix *A, int k, const double *B, int64_t ldb,
+                 double *X, int64_t ldx, const double *minv, double tol,
+                 int maxit, int check_every, void *d_work, size_t work_bytes,
+                 spmv_minres_info *info, hipStream_t s);
+int minres_debug_sqrt(const double *d_in, double *d_out, int64_t n,
+                      hipStream_t s);
 
 /* out[r] = the sum of row r's stored entries in column r, or 1 / that sum,
  * r < min(M, N) (diag_kernels.hip; spmv_*_diag); the caller has checked the
