@@ -114,6 +114,11 @@ int spmv_stream_create(void **stream);  /* non-blocking stream */
 int spmv_stream_destroy(void *stream);
 int spmv_graph_begin_capture(void *stream); /* not the default (NULL) stream */
 int spmv_graph_end_capture(void *stream, void **graph_exec);
+/* the same, and the topology of what was captured (any out-pointer may be
+ * NULL): a single chain of n nodes has n - 1 edges, one root and a largest
+ * fan-out of 1.  Added after 0.7; detect it by the symbol. */
+int spmv_graph_end_capture_shape(void *stream, void **graph_exec, int *nodes,
+                                 int *edges, int *roots, int *max_fanout);
 int spmv_graph_launch(void *graph_exec, void *stream);
 int spmv_graph_destroy(void *graph_exec);
 /* x[i] = synth_x(seed, first + i) generated on the device */
@@ -293,6 +298,108 @@ int spmv_csr_transpose(const spmv_csr_dev *A, spmv_csr_dev **out);
 int spmv_transpose_plan(int N, int64_t NZ, int *passes, int *digit_bits,
                         int *tile, int64_t *workgroups, int64_t *scratch_bytes);
 int spmv_csr_symmetry(const spmv_csr_dev *A, int *out);
+/*
+ * Level-scheduled sparse triangular solve T x = b (added after 0.7; detect it
+ * by the symbol).  spmv_csr_trsv_analyse makes a PLAN from one triangle of a
+ * square CSR handle (f64 or f32 values; rows may be unsorted, hold duplicates
+ * and explicit zeros, and store both triangles: only the entries of the
+ * chosen triangle are used, so the lower plan of a full matrix is the
+ * Gauss-Seidel operator D + L).  The plan copies what it needs: A is unchanged
+ * and may be released afterwards.  uplo: 0 lower, 1 upper.  unit: 0 = divide
+ * by the stored diagonal, 1 = unit diagonal (the solve never reads the stored
+ * one; the plan's diag and zero_diag are what they are for unit = 0).
+ * max_levels: 0 = the library default, 1 << 20.
+ *
+ * THE PLAN IS DEFINED TO THE BYTE and does not depend on scheduling:
+ *   strict entries of row i: its stored entries with column < i (lower) or
+ *       > i (upper), in stored order; duplicates are kept and not summed;
+ *       explicit zeros are dependencies (the analysis never looks at a value)
+ *   diag[i]:  the fp64 sum, starting from 0.0, of the stored entries in column
+ *       i, in stored order (f32 values widened first); 0.0 where the row
+ *       stores none.  zero_diag counts the rows with diag == 0.0: it is
+ *       information, not an error
+ *   level[i]: 0 when row i has no strict entry, else 1 + the largest level of
+ *       its strict columns
+ *   order:    the stable sort of 0 .. M-1 by level (rows ascending inside a
+ *       level); level_ptr[l] = number of rows with a level below l
+ *   rowptr / ja / as: the strict entries of row order[p] at position p, in
+ *       stored order, in A's value type, the bits moved and never computed
+ * The levels come from Kahn's algorithm on the device, one launch and one
+ * 4-byte read-back per level (integer atomics on counters; no POSITION that
+ * reaches the plan comes from an atomic), the order from the radix sort of
+ * spmv_csr_transpose.  The analysis stops with -E2BIG as soon as it would
+ * open level max_levels -- a tridiagonal matrix has M levels and is not what
+ * a level-scheduled solve is for; no device loop is unbounded.
+ *
+ * Errors, in this order: NULL A or out, uplo / unit outside 0..1, max_levels
+ * < 0 -EINVAL; no device -ENODEV; a dead handle -EBADF; M != N -EINVAL; after
+ * spmv_csr_release_source -ENODATA; a column outside [0, N) -EDOM; more than
+ * max_levels levels -E2BIG; a failed allocation -ENOMEM.  On any error nothing
+ * is created and *out is NULL; all scratch is freed on every path.  M == 0
+ * gives a valid plan with 0 levels.  The call blocks.  Plans count in
+ * spmv_live_handles() and have a generation (spmv_handle_generation) like
+ * every handle; spmv_trsv_release ignores NULL and anything that is not a
+ * live plan.
+ *
+ * spmv_trsv_info: any out-pointer may be NULL.  entries = strict entries,
+ * widest_level = rows of the largest level, launches = kernel launches of one
+ * solve, bytes = device memory the plan owns.  spmv_trsv_download (tests):
+ * level[M], order[M], level_ptr[levels + 1], rowptr[M + 1], ja[entries],
+ * as[entries] (widened to fp64), diag[M]; any pointer may be NULL.
+ * spmv_trsv_shape: the library constants G = group (lanes and sum slots per
+ * row, a power of two), small_rows, threads (lanes of the chain workgroup).
+ *
+ * spmv_trsv_solve: X = T^-1 B for k = 1..8 interleaved right-hand sides in the
+ * layout of spmv_*_launch_multi (ldb, ldx >= k; 0 = k; only columns 0..k-1 of
+ * rows 0..M-1 are touched).  Asynchronous on `stream` and capturable: the
+ * sequence of launches is a function of the plan alone and the host reads
+ * nothing back.  d_X == d_B with ldx == ldb is allowed (in place); any other
+ * overlap is undefined.  opts: waves_per_block as in launch_multi (0..16);
+ * group, variant and reserved must be 0.  d_scale: M doubles or NULL.
+ * Argument errors are the -EINVAL cases of launch_multi; a dead plan -EBADF.
+ *
+ * THE RESULT IS DEFINED TO THE BIT.  Every operation is rounded once, no
+ * fused multiply-add.  For row i, column j, strict entries e_0 .. e_{n-1} in
+ * the plan's order:
+ *     p_g (g < G) starts at 0.0 and adds rn(a_e * X[c_e, j]) for e = g mod G,
+ *         in increasing e
+ *     p[g] += p[g + h] for h = G/2 .. 1;  s = p[0]
+ *     rhs = B[i, j], or rn(scale_i * B[i, j]) when d_scale is given
+ *     X[i, j] = rn(rhs - s) for unit, else rn(rn(rhs - s) / diag_i), a
+ *         correctly rounded division
+ * So X does not depend on waves_per_block, on k, on the other columns or on
+ * which kernel ran a level; a d_scale of ones gives the bits of NULL; a zero
+ * diagonal or a non-finite b is plain arithmetic (inf / NaN in that row and
+ * its dependents only), never a fault.  d_scale makes symmetric Gauss-Seidel
+ * z = (D+U)^-1 D (D+L)^-1 r two solves with no pass in between.
+ *
+ * Two kernels: a level of more than small_rows rows is one launch over its
+ * rows, G lanes per row; a maximal run of consecutive levels of at most
+ * small_rows rows each is one launch of ONE workgroup that walks them with a
+ * workgroup barrier in between.  There is NO waiting between workgroups of
+ * any kind -- no flags, no spins, no grid barrier, no dependency counters in
+ * the solve: the kernel boundary on the stream is the only cross-workgroup
+ * ordering.
+ *
+ * Not in scope: HLL handles, compact (16-bit) handles, the blocked path, a
+ * plan as the preconditioner of spmv_*_pcg / minres / bicgstab, IC(0) / ILU(0)
+ * factors, and any treatment of deep chains beyond the -E2BIG cap.
+ */
+typedef struct spmv_trsv_plan spmv_trsv_plan;
+int spmv_csr_trsv_analyse(const spmv_csr_dev *A, int uplo, int unit,
+                          int max_levels, spmv_trsv_plan **out);
+int spmv_trsv_info(const spmv_trsv_plan *P, int *M, int *levels,
+                   int64_t *entries, int *widest_level, int64_t *zero_diag,
+                   int *launches, int64_t *bytes);
+int spmv_trsv_download(const spmv_trsv_plan *P, int *level, int *order,
+                       int *level_ptr, int *rowptr, int *ja, double *as,
+                       double *diag);
+void spmv_trsv_shape(int *group, int *small_rows, int *threads);
+void spmv_trsv_release(spmv_trsv_plan *P);
+void spmv_trsv_release_checked(spmv_trsv_plan *P, uint64_t generation);
+int spmv_trsv_solve(const spmv_trsv_plan *P, const spmv_launch_opts *opts, int k,
+                    const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                    const double *d_scale, void *stream);
 /* Build a synthetic matrix (spmv_synth.h) directly in device memory. */
 int spmv_csr_generate(int kind, int M, int N, int K, int64_t W, int64_t row0,
                       uint64_t seed, spmv_csr_dev **out);

@@ -498,6 +498,8 @@ _sig("spmv_stream_create", C.c_int, C.POINTER(C.c_void_p))
 _sig("spmv_stream_destroy", C.c_int, C.c_void_p)
 _sig("spmv_graph_begin_capture", C.c_int, C.c_void_p)
 _sig("spmv_graph_end_capture", C.c_int, C.c_void_p, C.POINTER(C.c_void_p))
+_sig("spmv_graph_end_capture_shape", C.c_int, C.c_void_p,
+     C.POINTER(C.c_void_p), _ip, _ip, _ip, _ip)
 _sig("spmv_graph_launch", C.c_int, C.c_void_p, C.c_void_p)
 _sig("spmv_graph_destroy", C.c_int, C.c_void_p)
 _sig("spmv_seam_cache", None, C.c_int)
@@ -546,6 +548,18 @@ _sig("spmv_csr_transpose", C.c_int, C.c_void_p, C.POINTER(C.c_void_p))
 _sig("spmv_transpose_plan", C.c_int, C.c_int, C.c_int64, _ip, _ip, _ip,
      C.POINTER(C.c_int64), C.POINTER(C.c_int64))
 _sig("spmv_csr_symmetry", C.c_int, C.c_void_p, _ip)
+_i64p = C.POINTER(C.c_int64)
+_sig("spmv_csr_trsv_analyse", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+     C.POINTER(C.c_void_p))
+_sig("spmv_trsv_info", C.c_int, C.c_void_p, _ip, _ip, _i64p, _ip, _i64p, _ip,
+     _i64p)
+_sig("spmv_trsv_download", C.c_int, C.c_void_p, _ip, _ip, _ip, _ip, _ip, _dp,
+     _dp)
+_sig("spmv_trsv_shape", None, _ip, _ip, _ip)
+_sig("spmv_trsv_release", None, C.c_void_p)
+_sig("spmv_trsv_release_checked", None, C.c_void_p, C.c_uint64)
+_sig("spmv_trsv_solve", C.c_int, C.c_void_p, C.POINTER(LaunchOpts), C.c_int,
+     C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
 _sig("spmv_csr_generate", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
      C.c_int64, C.c_int64, C.c_uint64, C.POINTER(C.c_void_p))
 _sig("spmv_csr_launch_rows", C.c_int, C.c_void_p, C.c_int,
@@ -770,6 +784,16 @@ def transpose_plan(N, NZ):
            "spmv_transpose_plan")
     return dict(passes=p.value, digit_bits=d.value, tile=t.value,
                 workgroups=w.value, scratch_bytes=s.value)
+
+
+def trsv_shape():
+    """the constants of the triangular solve (host, no device):
+    dict(group, small_rows, threads) -- `group` lanes and sum slots per row (a
+    power of two, part of the result contract), a level of at most
+    `small_rows` rows joins a one-workgroup chain launch of `threads` lanes"""
+    g, r, t = C.c_int(), C.c_int(), C.c_int()
+    _lib.spmv_trsv_shape(C.byref(g), C.byref(r), C.byref(t))
+    return dict(group=g.value, small_rows=r.value, threads=t.value)
 
 
 def version():
@@ -1323,10 +1347,12 @@ class Stream:
     def sync(self):
         stream_sync(self.ptr)
 
-    def capture(self):
+    def capture(self, shape=False):
         """context manager: what is enqueued on this stream inside becomes a
-        Graph (`with st.capture() as g: ...; g.launch()`)"""
-        return _Capture(self)
+        Graph (`with st.capture() as g: ...; g.launch()`).  shape=True: g.shape
+        is dict(nodes, edges, roots, max_fanout) of what was captured -- a
+        single chain has nodes - 1 edges, one root and max_fanout 1"""
+        return _Capture(self, shape)
 
     def __del__(self):
         h, self.ptr = getattr(self, "ptr", None), None
@@ -1351,8 +1377,8 @@ class Graph:
 
 
 class _Capture:
-    def __init__(self, stream):
-        self.stream, self.graph = stream, Graph()
+    def __init__(self, stream, shape=False):
+        self.stream, self.graph, self.shape = stream, Graph(), shape
 
     def __enter__(self):
         _check(_lib.spmv_graph_begin_capture(self.stream.ptr),
@@ -1361,7 +1387,15 @@ class _Capture:
 
     def __exit__(self, et, ev, tb):
         h = C.c_void_p()
-        rc = _lib.spmv_graph_end_capture(self.stream.ptr, C.byref(h))
+        if self.shape:
+            n, e, r, f = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+            rc = _lib.spmv_graph_end_capture_shape(
+                self.stream.ptr, C.byref(h), C.byref(n), C.byref(e),
+                C.byref(r), C.byref(f))
+            self.graph.shape = dict(nodes=n.value, edges=e.value,
+                                    roots=r.value, max_fanout=f.value)
+        else:
+            rc = _lib.spmv_graph_end_capture(self.stream.ptr, C.byref(h))
         if et is None:
             _check(rc, "spmv_graph_end_capture")
             self.graph.h = h
@@ -1753,6 +1787,25 @@ class CsrDevice(_Device):
                "spmv_csr_symmetry")
         return out.value
 
+    def trsv_analyse(self, uplo="lower", unit=False, max_levels=0):
+        """a TrsvPlan for T x = b with T the `uplo` triangle of this (square)
+        handle: the level schedule and a copy of the strict entries, built on
+        the device and defined to the byte (spmv_engine.h).  unit=True: unit
+        diagonal.  More than max_levels levels (0: 1 << 20) is
+        OSError(E2BIG).  This handle stays valid and may be released"""
+        if uplo not in ("lower", "upper"):
+            raise ValueError("uplo=%r: \"lower\" or \"upper\"" % (uplo,))
+        max_levels = int(max_levels)
+        if max_levels < 0:
+            raise ValueError("max_levels=%d: 0 (the default) or more"
+                             % max_levels)
+        h = C.c_void_p()
+        _check(_lib.spmv_csr_trsv_analyse(self.h, int(uplo == "upper"),
+                                          int(bool(unit)), max_levels,
+                                          C.byref(h)),
+               "spmv_csr_trsv_analyse")
+        return TrsvPlan(h)
+
     @classmethod
     def generate(cls, kind, M, N, K, W, row0=0, seed=42):
         h = C.c_void_p()
@@ -1795,6 +1848,85 @@ class CsrDevice(_Device):
         _check(_lib.spmv_hll_from_csr(self.h, int(col_major), C.byref(h)),
                "spmv_hll_from_csr")
         return HllDevice(h)
+
+
+class TrsvPlan:
+    """The level schedule of a sparse triangular solve, resident in HBM
+    (spmv_engine.h, spmv_trsv_plan; CsrDevice.trsv_analyse makes one)."""
+
+    h = None
+    _RANK = 1
+
+    def __init__(self, handle):
+        self.h = handle
+        self.gen = _lib.spmv_handle_generation(self.h)
+        if not self.gen:
+            raise OSError(9, "spmv_handle_generation: %r is not a live plan "
+                             "of this library" % (self.h,))
+        _live.add(self)
+
+    def _released(self):
+        return not self.h
+
+    def _release_now(self):
+        self.release()
+
+    @property
+    def info(self):
+        """dict(M, levels, entries, widest_level, zero_diag, launches,
+        bytes)"""
+        M, lv, wd, ln = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        en, zd, by = C.c_int64(), C.c_int64(), C.c_int64()
+        _check(_lib.spmv_trsv_info(self.h, C.byref(M), C.byref(lv),
+                                   C.byref(en), C.byref(wd), C.byref(zd),
+                                   C.byref(ln), C.byref(by)),
+               "spmv_trsv_info")
+        return dict(M=M.value, levels=lv.value, entries=en.value,
+                    widest_level=wd.value, zero_diag=zd.value,
+                    launches=ln.value, bytes=by.value)
+
+    def download(self):
+        """dict(level, order, level_ptr, rowptr, ja: int32; as (the stored
+        values widened), diag: float64)"""
+        i = self.info
+        M, nz = i["M"], i["entries"]
+        out = dict(level=np.zeros(M, np.int32), order=np.zeros(M, np.int32),
+                   level_ptr=np.zeros(i["levels"] + 1, np.int32),
+                   rowptr=np.zeros(M + 1, np.int32),
+                   ja=np.zeros(nz, np.int32), diag=np.zeros(M, np.float64))
+        out["as"] = np.zeros(nz, np.float64)
+        _check(_lib.spmv_trsv_download(
+            self.h, *(out[n].ctypes.data_as(_ip) for n in
+                      ("level", "order", "level_ptr", "rowptr", "ja")),
+            out["as"].ctypes.data_as(_dp), out["diag"].ctypes.data_as(_dp)),
+            "spmv_trsv_download")
+        return out
+
+    def solve(self, d_B, d_X, k=1, scale=None, ldb=0, ldx=0,
+              waves_per_block=0, stream=None):
+        """X = T^-1 B for k = 1..8 interleaved right-hand sides (ldb, ldx >= k
+        or 0), asynchronous on `stream`; d_X may be d_B (in place, ldx == ldb).
+        scale: device pointer to M doubles, row i of B is multiplied by
+        scale[i] first.  The bits of X are fixed by the contract in
+        spmv_engine.h and depend on neither waves_per_block nor k"""
+        k, ldb, ldx = int(k), int(ldb), int(ldx)
+        if not 1 <= k <= 8:
+            raise ValueError("k=%r: 1..8 right-hand sides per solve" % (k,))
+        if (ldb and ldb < k) or (ldx and ldx < k):
+            raise ValueError("ldb=%d, ldx=%d: at least k=%d (or 0)"
+                             % (ldb, ldx, k))
+        o = _opts(waves_per_block)
+        _check(_lib.spmv_trsv_solve(self.h, C.byref(o), k, d_B, ldb, d_X, ldx,
+                                    scale, stream), "spmv_trsv_solve")
+
+    def release(self):
+        h, self.h = self.h, None
+        if h and _closed is False and _lib is not None:
+            _lib.spmv_trsv_release_checked(h, self.gen)
+
+    def __del__(self):
+        if _closed is False:  # None / True at or after interpreter shutdown
+            self.release()
 
 
 class HllDevice(_Device):

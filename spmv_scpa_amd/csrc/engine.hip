@@ -28,6 +28,7 @@
 #include "spmv_synth.h"
 #include "stream_table.h"
 #include "transpose_plan.h"
+#include "trsv_plan.h"
 #include "tune_blocked.h"
 #include "utils.h"
 
@@ -404,6 +405,48 @@ int spmv_graph_end_capture(void *stream, void **graph_exec) {
     (void)hipGraphDestroy(g);
     if (err != hipSuccess)
         return hip_errno(err);
+    *graph_exec = (void *)e;
+    return 0;
+}
+
+/* ... and the topology of what was captured: a single chain of n nodes has
+ * n - 1 edges, one root and a largest fan-out of 1 (0 for n <= 1) */
+int spmv_graph_end_capture_shape(void *stream, void **graph_exec, int *nodes,
+                                 int *edges, int *roots, int *max_fanout) {
+    if (!stream || !graph_exec)
+        return -EINVAL;
+    hipGraph_t g = NULL;
+    hipGraphExec_t e = NULL;
+    HIP_RET(hipStreamEndCapture((hipStream_t)stream, &g));
+    size_t nn = 0, ne = 0, nr = 0;
+    int fan = 0;
+    hipError_t err = hipGraphGetNodes(g, NULL, &nn);
+    if (err == hipSuccess)
+        err = hipGraphGetEdges(g, NULL, NULL, &ne);
+    if (err == hipSuccess)
+        err = hipGraphGetRootNodes(g, NULL, &nr);
+    if (err == hipSuccess && ne > 0) {
+        std::vector<hipGraphNode_t> from(ne), to(ne);
+        err = hipGraphGetEdges(g, from.data(), to.data(), &ne);
+        if (err == hipSuccess) {
+            std::unordered_map<hipGraphNode_t, int> out;
+            for (size_t i = 0; i < ne; ++i)
+                fan = std::max(fan, ++out[from[i]]);
+        }
+    }
+    if (err == hipSuccess)
+        err = hipGraphInstantiate(&e, g, NULL, NULL, 0);
+    (void)hipGraphDestroy(g);
+    if (err != hipSuccess)
+        return hip_errno(err);
+    if (nodes)
+        *nodes = (int)nn;
+    if (edges)
+        *edges = (int)ne;
+    if (roots)
+        *roots = (int)nr;
+    if (max_fanout)
+        *max_fanout = fan;
     *graph_exec = (void *)e;
     return 0;
 }
@@ -1040,6 +1083,160 @@ int spmv_csr_symmetry(const spmv_csr_dev *A, int *out) {
         return rc;
     *out = values ? 2 : pattern ? 1 : 0;
     return 0;
+}
+
+/* ------------------------------------------------------------------ */
+/* triangular solve (trsv_kernels.hip, trsv_plan.h)                     */
+/* ------------------------------------------------------------------ */
+
+void spmv_trsv_shape(int *group, int *small_rows, int *threads) {
+    if (group)
+        *group = TRSV_GROUP;
+    if (small_rows)
+        *small_rows = TRSV_SMALL_ROWS;
+    if (threads)
+        *threads = TRSV_THREADS;
+}
+
+void spmv_trsv_release(spmv_trsv_plan *P) {
+    if (!P || !live_take(P))
+        return;
+    trsv_free_dev(P);
+    free(P);
+}
+
+void spmv_trsv_release_checked(spmv_trsv_plan *P, uint64_t generation) {
+    if (!P || !live_take(P, generation))
+        return;
+    trsv_free_dev(P);
+    free(P);
+}
+
+int spmv_csr_trsv_analyse(const spmv_csr_dev *A, int uplo, int unit,
+                          int max_levels, spmv_trsv_plan **out) {
+    if (!A || !out || uplo < 0 || uplo > 1 || unit < 0 || unit > 1 ||
+        max_levels < 0)
+        return -EINVAL;
+    *out = NULL;
+    if (spmv_device_count() == 0)
+        return -ENODEV; /* no handle can be live: the more useful answer */
+    HANDLE_OK(A);
+    if (A->M != A->N)
+        return -EINVAL;
+    if (!A->ja && A->NZ > 0)
+        return -ENODATA; /* spmv_csr_release_source() */
+    spmv_trsv_plan *P = (spmv_trsv_plan *)calloc(1, sizeof *P);
+    if (!P)
+        return -ENOMEM;
+    const int rc = trsv_analyse_dev(
+        A, uplo, unit, max_levels ? max_levels : TRSV_DEFAULT_MAX_LEVELS, P, 0);
+    if (rc) {
+        trsv_free_dev(P);
+        free(P);
+        return rc;
+    }
+    live_add(P);
+    *out = P;
+    return 0;
+}
+
+/* NULL -> -EINVAL; not a live plan -> -EBADF, or -ENODEV without a device */
+#define PLAN_OK(P)                                                            \
+    do {                                                                      \
+        if (!(P))                                                             \
+            return -EINVAL;                                                   \
+        if (!live_has(P))                                                     \
+            return spmv_device_count() == 0 ? -ENODEV : -EBADF;               \
+    } while (0)
+
+int spmv_trsv_info(const spmv_trsv_plan *P, int *M, int *levels,
+                   int64_t *entries, int *widest_level, int64_t *zero_diag,
+                   int *launches, int64_t *bytes) {
+    PLAN_OK(P);
+    if (M)
+        *M = P->M;
+    if (levels)
+        *levels = P->levels;
+    if (entries)
+        *entries = P->entries;
+    if (widest_level)
+        *widest_level = P->widest_level;
+    if (zero_diag)
+        *zero_diag = P->zero_diag;
+    if (launches)
+        *launches = P->n_segs;
+    if (bytes)
+        *bytes = P->bytes;
+    return 0;
+}
+
+int spmv_trsv_download(const spmv_trsv_plan *P, int *level, int *order,
+                       int *level_ptr, int *rowptr, int *ja, double *as,
+                       double *diag) {
+    PLAN_OK(P);
+    const size_t M = (size_t)P->M, nz = (size_t)P->entries;
+    if (level_ptr)
+        HIP_RET(hipMemcpy(level_ptr, P->level_ptr,
+                          ((size_t)P->levels + 1) * sizeof(int),
+                          hipMemcpyDeviceToHost));
+    if (M == 0) {
+        if (rowptr)
+            rowptr[0] = 0;
+        return 0;
+    }
+    if (level)
+        HIP_RET(hipMemcpy(level, P->level, M * sizeof(int),
+                          hipMemcpyDeviceToHost));
+    if (order)
+        HIP_RET(hipMemcpy(order, P->order, M * sizeof(int),
+                          hipMemcpyDeviceToHost));
+    if (rowptr)
+        HIP_RET(hipMemcpy(rowptr, P->rowptr, (M + 1) * sizeof(int),
+                          hipMemcpyDeviceToHost));
+    if (diag)
+        HIP_RET(hipMemcpy(diag, P->diag, M * sizeof(double),
+                          hipMemcpyDeviceToHost));
+    if (ja && nz)
+        HIP_RET(hipMemcpy(ja, P->ja, nz * sizeof(int), hipMemcpyDeviceToHost));
+    if (as && nz) {
+        if (P->value_bytes == 4) { /* widened on the host: exact */
+            std::vector<float> narrow(nz);
+            HIP_RET(hipMemcpy(narrow.data(), P->as, nz * sizeof(float),
+                              hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < nz; ++i)
+                as[i] = (double)narrow[i];
+        } else {
+            HIP_RET(hipMemcpy(as, P->as, nz * sizeof(double),
+                              hipMemcpyDeviceToHost));
+        }
+    }
+    return 0;
+}
+
+int spmv_trsv_solve(const spmv_trsv_plan *P, const spmv_launch_opts *opts, int k,
+                    const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                    const double *d_scale, void *stream) {
+    PLAN_OK(P);
+    if (k < 1 || k > 8)
+        return -EINVAL;
+    if (ldb == 0)
+        ldb = k;
+    if (ldx == 0)
+        ldx = k;
+    if (ldb < k || ldx < k || !d_B || !d_X)
+        return -EINVAL;
+    if (opts) {
+        if (opts->waves_per_block < 0 || opts->waves_per_block > 16 ||
+            opts->group || opts->variant)
+            return -EINVAL;
+        for (int r : opts->reserved)
+            if (r)
+                return -EINVAL;
+    }
+    if (P->M == 0)
+        return 0;
+    return trsv_solve_dev(P, opts ? opts->waves_per_block : 0, k, d_B, ldb, d_X,
+                          ldx, d_scale, (hipStream_t)stream);
 }
 
 int spmv_csr_generate(int kind, int M, int N, int K, int64_t W, int64_t row0,

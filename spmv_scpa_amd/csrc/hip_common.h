@@ -2,7 +2,8 @@
  * hip_common.h -- internals shared by the HIP translation units
  * (engine.hip, csr_kernels.hip, hll_kernels.hip, multi_kernels.hip,
  * cg_kernels.hip, bicgstab_kernels.hip, cgls_kernels.hip, minres_kernels.hip,
- * diag_kernels.hip, transpose_kernels.hip, panels.hip, mgpu.hip, and
+ * diag_kernels.hip, transpose_kernels.hip, trsv_kernels.hip, panels.hip,
+ * mgpu.hip, and
  * mat_ref.h on behalf of the first and the last).
  * Not installed.
  */
@@ -596,6 +597,43 @@ int hll_diag(const spmv_hll_dev *H, double *out, int invert, hipStream_t s);
 int csr_transpose_dev(const spmv_csr_dev *A, spmv_csr_dev *T, hipStream_t s);
 int csr_equal_dev(const spmv_csr_dev *X, const spmv_csr_dev *Y, int *pattern,
                   int *values, hipStream_t s);
+/* exclusive scan of n ints in place; sums: transpose_scan_tiles(n) ints of
+ * scratch (transpose_kernels.hip; the triangular analysis scans with it too) */
+void tr_scan(int *data, int64_t n, int *sums, hipStream_t s);
+
+/*
+ * Level-scheduled triangular solve (trsv_kernels.hip; spmv_csr_trsv_analyse,
+ * spmv_trsv_solve).  The plan owns device copies of everything the solve
+ * reads and a host copy of level_ptr with the launch list made from it
+ * (trsv_plan.h): the sequence of launches is a function of the plan alone.
+ */
+struct trsv_segment;
+struct spmv_trsv_plan {
+    int M, uplo, unit, levels, value_bytes, device;
+    int widest_level;
+    int64_t entries;   /* strict entries */
+    int64_t zero_diag; /* rows whose diagonal sum is 0.0 */
+    int64_t bytes;     /* device memory the plan owns */
+    int *level;        /* [M] by row */
+    int *order;        /* [M] rows by (level, row) */
+    int *level_ptr;    /* [levels + 1] */
+    int *rowptr;       /* [M + 1] by position in `order` */
+    int *ja;           /* [entries] */
+    void *as;          /* [entries] of value_bytes each, A's bits */
+    double *diag;      /* [M] by row */
+    int *h_level_ptr;  /* host copy (malloc) */
+    trsv_segment *segs; /* host, the launches of one solve (malloc) */
+    int n_segs;
+};
+/* fills *P (zeroed by the caller) from A's chosen triangle; blocks; on an error
+ * the caller runs trsv_free_dev.  -E2BIG: more than max_levels levels */
+int trsv_analyse_dev(const spmv_csr_dev *A, int uplo, int unit, int max_levels,
+                     spmv_trsv_plan *P, hipStream_t s);
+void trsv_free_dev(spmv_trsv_plan *P); /* the arrays, not P itself */
+/* the arguments were checked by the caller; waves 0 = each kernel's default */
+int trsv_solve_dev(const spmv_trsv_plan *P, int waves, int k, const double *B,
+                   int64_t ldb, double *X, int64_t ldx, const double *scale,
+                   hipStream_t s);
 
 /* kernel launchers (csr_kernels.hip / hll_kernels.hip) */
 int csr_launch_kernel(const spmv_csr_dev *A, int kernel, int waves, int group,

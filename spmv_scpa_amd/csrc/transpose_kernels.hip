@@ -145,7 +145,7 @@ k_tr_scan_add(int *__restrict__ data, int64_t n, const int *__restrict__ sums) {
             data[base + u] += add;
 }
 
-static void tr_scan(int *data, int64_t n, int *sums, hipStream_t s) {
+void tr_scan(int *data, int64_t n, int *sums, hipStream_t s) {
     const int64_t tiles = transpose_scan_tiles(n);
     if (tiles == 0)
         return;
