@@ -381,9 +381,11 @@ int spmv_csr_symmetry(const spmv_csr_dev *A, int *out);
  * the solve: the kernel boundary on the stream is the only cross-workgroup
  * ordering.
  *
- * Not in scope: HLL handles, compact (16-bit) handles, the blocked path, a
- * plan as the preconditioner of spmv_*_pcg / minres / bicgstab, IC(0) / ILU(0)
- * factors, and any treatment of deep chains beyond the -E2BIG cap.
+ * Plans are the preconditioner of spmv_*_pcg_trsv, and spmv_csr_ic0 makes the
+ * factor to build them from (both below).  Not in scope: HLL handles, compact
+ * (16-bit) handles, the blocked path, a plan as the preconditioner of minres /
+ * bicgstab, ILU(0) factors, and any treatment of deep chains beyond the -E2BIG
+ * cap.
  */
 typedef struct spmv_trsv_plan spmv_trsv_plan;
 int spmv_csr_trsv_analyse(const spmv_csr_dev *A, int uplo, int unit,
@@ -400,6 +402,63 @@ void spmv_trsv_release_checked(spmv_trsv_plan *P, uint64_t generation);
 int spmv_trsv_solve(const spmv_trsv_plan *P, const spmv_launch_opts *opts, int k,
                     const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
                     const double *d_scale, void *stream);
+/*
+ * Zero-fill incomplete Cholesky A ~ L L^T on the device (added after 0.7;
+ * detect it by the symbol).  A: a square CSR handle with f64 values.  Only the
+ * entries with column <= row are read: the upper triangle may be present,
+ * absent or wrong.  Within that lower triangle every row must be strictly
+ * ascending by column (so no duplicates) and must store its diagonal; a device
+ * check answers -EINVAL otherwise, before anything is allocated for the
+ * result.  spmv_csr_transpose twice sorts the rows of a handle.  *out is a new,
+ * ordinary f64 CSR handle L, M x M, whose pattern is that lower triangle, rows
+ * ascending, the diagonal last in each row: launch, launch_multi, transpose,
+ * trsv_analyse, download and release work on it as on any handle.  A is
+ * unchanged.  The call blocks.  shift >= 0 factors A + shift * diag(A).
+ * max_levels: as spmv_csr_trsv_analyse (0 = 1 << 20).
+ *
+ * Errors, in this order: NULL A or out, a non-finite or negative shift,
+ * max_levels < 0 -EINVAL; no device -ENODEV; a dead handle -EBADF; M != N
+ * -EINVAL; f32 values -ENOTSUP; after spmv_csr_release_source -ENODATA; a
+ * column outside [0, N) -EDOM; the ordering / diagonal check -EINVAL; more
+ * than max_levels levels -E2BIG; a failed allocation -ENOMEM.  On any error
+ * nothing is created, *out is NULL, and all scratch is freed on every path.
+ * M == 0 gives a valid empty handle.  A pivot that is not positive is NOT an
+ * error: it is plain arithmetic (the square root of a negative number is NaN
+ * and reaches exactly the dependent rows) and is counted in bad_pivots, as
+ * zero_diag is in a plan.  info may be NULL.
+ *
+ * THE RESULT IS DEFINED TO THE BIT.  Every operation is rounded once, no fused
+ * multiply-add, an IEEE division, the correctly rounded square root of
+ * spmv_*_minres.  For row i with lower columns c_0 < ... < c_{n-1} < i, in
+ * increasing t:
+ *     j = c_t
+ *     s = 0.0;  for every column m < j stored in both row i and row j, in
+ *               increasing m:  s = rn(s + rn(L_im * L_jm))
+ *     L_ij = rn(rn(a_ij - s) / L_jj)
+ * then
+ *     s = 0.0;  for t = 0 .. n-1:  s = rn(s + rn(L_it * L_it))
+ *     d = rn(rn(a_ii + rn(shift * a_ii)) - s)
+ *     L_ii = sqrt(d);  bad_pivots counts the rows with !(d > 0), NaN included
+ * shift = 0 leaves a finite a_ii unchanged.  The sums are sequential by
+ * contract (one lane walks a row, merging it with the row of each strict
+ * column), so the bits depend neither on set_csr_waves_per_block, which sizes
+ * the workgroups here, nor on which kernel ran a level, nor on the run.
+ *
+ * The levels of L's rows are those of the strict lower pattern of A, from the
+ * analysis of spmv_csr_trsv_analyse, and the launches are its launch list: a
+ * level of more than small_rows rows is one launch, a maximal run of thinner
+ * levels one launch of ONE workgroup with a workgroup barrier between levels.
+ * No waiting between workgroups of any kind; every device loop is bounded by a
+ * row length.  info: levels and launches of the factorisation, entries = the
+ * stored entries of L.
+ */
+typedef struct spmv_ic0_info {
+    int levels, launches; /* of the factorisation */
+    int64_t entries;      /* stored entries of L */
+    int64_t bad_pivots;   /* rows whose pivot d was not > 0 (NaN included) */
+} spmv_ic0_info;
+int spmv_csr_ic0(const spmv_csr_dev *A, double shift, int max_levels,
+                 spmv_csr_dev **out, spmv_ic0_info *info /* may be NULL */);
 /* Build a synthetic matrix (spmv_synth.h) directly in device memory. */
 int spmv_csr_generate(int kind, int M, int N, int K, int64_t W, int64_t row0,
                       uint64_t seed, spmv_csr_dev **out);
@@ -845,6 +904,57 @@ int spmv_hll_pcg(const spmv_hll_dev *H, const spmv_launch_opts *opts, int k,
                  double tol, int maxit, int check_every,
                  void *d_work, size_t work_bytes,
                  spmv_cg_info *info, void *stream);
+
+/*
+ * Conjugate gradients preconditioned by triangular plans (added after 0.7;
+ * detect it by the symbol): spmv_*_pcg with Z = z(R) made by spmv_trsv_solve
+ * instead of a multiplication by minv, in two steps:
+ *     spmv_trsv_solve(first, k, R -> Z, no scale)
+ *     if second is not NULL: spmv_trsv_solve(second, k, Z -> Z in place,
+ *                                            d_scale)
+ * always for all k columns, with an opts that carries only the caller's
+ * waves_per_block.  Symmetric Gauss-Seidel is (the lower plan of A, the upper
+ * plan of A, diag(A)); IC(0) is (the lower plan of L = spmv_csr_ic0(A), the
+ * upper plan of spmv_csr_transpose(L), NULL).  The plans and d_scale are never
+ * written and may serve any number of solves.
+ *
+ * Everything else is spmv_*_pcg word for word: the handles, the interleaved
+ * k = 1..8 systems, the blocking, -EBUSY on a capturing stream, check_every,
+ * maxit, M == 0, the records and the frozen-column rule.  d_work:
+ * spmv_pcg_trsv_work_bytes(M, k) bytes, pcg's and one vector Z (ld = k).
+ * Checks added after pcg's, in this order: NULL first -EINVAL; d_scale without
+ * second -EINVAL; a dead plan -EBADF; a plan whose M is not A's -EINVAL.
+ *
+ * The recurrence is that of spmv_*_pcg with the stored Z where pcg has z(R):
+ * P = Z;  rz = dot(R, Z);  after the update rn = dot(R, R), Z = z(R),
+ * zn = dot(R, Z), beta = zn / rz, P = Z + beta * P -- the same classification
+ * ladder, the same dot order, every operation rounded once.  Z is scratch: a
+ * frozen column's Z may hold anything, and nothing of it reaches X, R, P or
+ * the state.  Two properties of the contract, not special cases: a plan of the
+ * identity (or a unit plan without strict entries) returns the bits of
+ * spmv_*_cg; a plan of a diagonal matrix of powers of two returns the bits of
+ * spmv_*_pcg with minv = 1 / d.  A NaN in a factor makes rz NaN: status 2 with
+ * 0 iterations.
+ *
+ * The price: every iteration adds the launches of the plans (spmv_trsv_info),
+ * 3.4-4.4 us each.  On a stencil in natural order that is far more than the
+ * iteration of spmv_*_pcg it replaces; it pays where the level count is small
+ * (a multicolour ordering) or the iteration count falls by more than the
+ * launches cost (profiles/ic0.md).
+ */
+int64_t spmv_pcg_trsv_work_bytes(int M, int k); /* as spmv_pcg_work_bytes */
+int spmv_csr_pcg_trsv(const spmv_csr_dev *A, const spmv_launch_opts *opts,
+                      int k, const double *d_B, int64_t ldb, double *d_X,
+                      int64_t ldx, const spmv_trsv_plan *first,
+                      const spmv_trsv_plan *second, const double *d_scale,
+                      double tol, int maxit, int check_every, void *d_work,
+                      size_t work_bytes, spmv_cg_info *info, void *stream);
+int spmv_hll_pcg_trsv(const spmv_hll_dev *H, const spmv_launch_opts *opts,
+                      int k, const double *d_B, int64_t ldb, double *d_X,
+                      int64_t ldx, const spmv_trsv_plan *first,
+                      const spmv_trsv_plan *second, const double *d_scale,
+                      double tol, int maxit, int check_every, void *d_work,
+                      size_t work_bytes, spmv_cg_info *info, void *stream);
 
 /*
  * BiCGStab on the device for A X = B with a nonsymmetric A (added after 0.7;

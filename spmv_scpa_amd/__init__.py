@@ -418,6 +418,12 @@ class MinresInfo(C.Structure):
                 ("bb", C.c_double)]
 
 
+class Ic0Info(C.Structure):
+    """spmv_ic0_info (include/spmv_engine.h): one CsrDevice.ic0()"""
+    _fields_ = [("levels", C.c_int), ("launches", C.c_int),
+                ("entries", C.c_int64), ("bad_pivots", C.c_int64)]
+
+
 _CSRp = C.POINTER(SparseCSR)
 _HLLp = C.POINTER(SparseHLL)
 
@@ -560,6 +566,8 @@ _sig("spmv_trsv_release", None, C.c_void_p)
 _sig("spmv_trsv_release_checked", None, C.c_void_p, C.c_uint64)
 _sig("spmv_trsv_solve", C.c_int, C.c_void_p, C.POINTER(LaunchOpts), C.c_int,
      C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
+_sig("spmv_csr_ic0", C.c_int, C.c_void_p, C.c_double, C.c_int,
+     C.POINTER(C.c_void_p), C.POINTER(Ic0Info))
 _sig("spmv_csr_generate", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
      C.c_int64, C.c_int64, C.c_uint64, C.POINTER(C.c_void_p))
 _sig("spmv_csr_launch_rows", C.c_int, C.c_void_p, C.c_int,
@@ -581,6 +589,7 @@ _sig("spmv_hll_kernel_bytes", C.c_int64, C.c_void_p, C.c_int)
 _sig("spmv_cg_work_bytes", C.c_int64, C.c_int, C.c_int)
 _sig("spmv_cg_dot_shape", None, _ip, _ip)
 _sig("spmv_pcg_work_bytes", C.c_int64, C.c_int, C.c_int)
+_sig("spmv_pcg_trsv_work_bytes", C.c_int64, C.c_int, C.c_int)
 _sig("spmv_bicgstab_work_bytes", C.c_int64, C.c_int, C.c_int)
 _sig("spmv_cgls_work_bytes", C.c_int64, C.c_int, C.c_int, C.c_int)
 _sig("spmv_minres_work_bytes", C.c_int64, C.c_int, C.c_int)
@@ -632,6 +641,10 @@ _TWINS = (
      C.c_void_p, C.POINTER(LaunchOpts), C.c_int, C.c_void_p, C.c_int64,
      C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_int, C.c_int,
      C.c_void_p, C.c_size_t, C.POINTER(CgInfo), C.c_void_p),
+    ("pcg_trsv", C.c_int,
+     C.c_void_p, C.POINTER(LaunchOpts), C.c_int, C.c_void_p, C.c_int64,
+     C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+     C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(CgInfo), C.c_void_p),
     ("bicgstab", C.c_int,
      C.c_void_p, C.POINTER(LaunchOpts), C.c_int, C.c_void_p, C.c_int64,
      C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_int, C.c_int,
@@ -735,6 +748,13 @@ def pcg_work_bytes(M, k):
     cg_work_bytes and one more set of partial sums"""
     return _check(_lib.spmv_pcg_work_bytes(int(M), int(k)),
                   "spmv_pcg_work_bytes")
+
+
+def pcg_trsv_work_bytes(M, k):
+    """bytes of device memory one pcg_trsv() solve of k systems with M rows
+    needs: pcg_work_bytes and one more vector (Z) of 8 k M bytes"""
+    return _check(_lib.spmv_pcg_trsv_work_bytes(int(M), int(k)),
+                  "spmv_pcg_trsv_work_bytes")
 
 
 def bicgstab_work_bytes(M, k):
@@ -1534,6 +1554,31 @@ class _Device:
                         check_every, ldb, ldx, work, waves_per_block, group,
                         stream)
 
+    def pcg_trsv(self, d_B, d_X, first, second=None, d_scale=None, k=1,
+                 tol=1e-8, maxit=1000, check_every=0, ldb=0, ldx=0, work=None,
+                 waves_per_block=0, group=0, stream=None):
+        """cg() preconditioned by triangular plans: z = M^-1 r is
+        first.solve(r -> z), then, with a second TrsvPlan,
+        second.solve(z -> z in place, scale=d_scale).  Symmetric Gauss-Seidel:
+        pcg_trsv(d_B, d_X, *A.sgs().args); IC(0): the lower plan of
+        L = A.ic0()[0] and the upper plan of L.transpose().  The plans and
+        d_scale (M doubles) are not written and may be shared by any number of
+        solves.  Everything else as pcg() (`work`: at least
+        pcg_trsv_work_bytes(M, k) bytes).  Each iteration adds the launches
+        of the plans (TrsvPlan.info["launches"]).
+        -> [CgResult(status, iterations, rr, bb)] * k"""
+        if not isinstance(first, TrsvPlan) or \
+                not (second is None or isinstance(second, TrsvPlan)):
+            raise ValueError("pcg_trsv: first is a TrsvPlan, second a "
+                             "TrsvPlan or None")
+        if d_scale is not None and second is None:
+            raise ValueError("pcg_trsv: d_scale scales the input of the "
+                             "second plan, and there is none")
+        return self._cg("pcg_trsv", d_B, d_X,
+                        (first.h, second.h if second is not None else None,
+                         d_scale), k, tol, maxit, check_every, ldb, ldx, work,
+                        waves_per_block, group, stream)
+
     def bicgstab(self, d_B, d_X, k=1, d_minv=None, tol=1e-8, maxit=1000,
                  check_every=0, ldb=0, ldx=0, work=None, waves_per_block=0,
                  group=0, stream=None):
@@ -1575,8 +1620,9 @@ class _Device:
     def _cg(self, name, d_B, d_X, minv, k, tol, maxit, check_every, ldb, ldx,
             work, waves_per_block, group, stream, record=CgInfo,
             result=CgResult):
-        """cg(), pcg(), bicgstab() and minres(): `minv` is () or (d_minv,),
-        the argument spmv_*_cg does not take; `record` / `result`: the C
+        """cg(), pcg(), pcg_trsv(), bicgstab() and minres(): `minv` is () or
+        (d_minv,) or (first, second, d_scale), the arguments spmv_*_cg does
+        not take; `record` / `result`: the C
         record of the solver and the namedtuple with its fields"""
         k, ldb, ldx = int(k), int(ldb), int(ldx)
         if not 1 <= k <= 8:
@@ -1806,6 +1852,35 @@ class CsrDevice(_Device):
                "spmv_csr_trsv_analyse")
         return TrsvPlan(h)
 
+    def ic0(self, shift=0.0, max_levels=0):
+        """(L, Ic0Info): the zero-fill incomplete Cholesky factor of this
+        (square, f64) handle, A + shift diag(A) ~ L L^T, as a new CsrDevice
+        with the pattern of the lower triangle, the diagonal last in each
+        row, built on the device and defined to the bit (spmv_engine.h).
+        Only entries with column <= row are read; they must be strictly
+        ascending in every row and hold the diagonal (OSError(EINVAL)
+        otherwise; transpose().transpose() sorts rows).  A pivot that is not
+        positive is counted in Ic0Info.bad_pivots and leaves NaN in L, it is
+        not an error.  The preconditioner of pcg_trsv() is
+        (L.trsv_analyse("lower"), L.transpose().trsv_analyse("upper")).
+        This handle stays valid"""
+        shift, max_levels = float(shift), int(max_levels)
+        if not (shift >= 0.0 and np.isfinite(shift)):
+            raise ValueError("shift=%r: a finite number, 0 or more"
+                             % (shift,))
+        if max_levels < 0:
+            raise ValueError("max_levels=%d: 0 (the default) or more"
+                             % max_levels)
+        h, info = C.c_void_p(), Ic0Info()
+        _check(_lib.spmv_csr_ic0(self.h, shift, max_levels, C.byref(h),
+                                 C.byref(info)), "spmv_csr_ic0")
+        return CsrDevice(h), info
+
+    def sgs(self, max_levels=0):
+        """an SgsPreconditioner of this (square) handle: its lower and upper
+        TrsvPlan and a DevBuffer with diag(A); release() frees the three"""
+        return SgsPreconditioner(self, max_levels)
+
     @classmethod
     def generate(cls, kind, M, N, K, W, row0=0, seed=42):
         h = C.c_void_p()
@@ -1927,6 +2002,38 @@ class TrsvPlan:
     def __del__(self):
         if _closed is False:  # None / True at or after interpreter shutdown
             self.release()
+
+
+class SgsPreconditioner:
+    """Symmetric Gauss-Seidel z = (D+U)^-1 D (D+L)^-1 r of a CsrDevice as
+    pcg_trsv() takes it: `lower` and `upper` (TrsvPlan), `diag` (DevBuffer, M
+    doubles); `args` = (lower, upper, diag.ptr).  CsrDevice.sgs() makes one;
+    the matrix may be released afterwards."""
+
+    lower = upper = diag = None
+
+    def __init__(self, A, max_levels=0):
+        try:
+            self.lower = A.trsv_analyse("lower", max_levels=max_levels)
+            self.upper = A.trsv_analyse("upper", max_levels=max_levels)
+            self.diag = DevBuffer(max(A.M, 1) * 8)
+            A.diag(self.diag.ptr)
+            stream_sync()
+        except BaseException:
+            self.release()
+            raise
+
+    @property
+    def args(self):
+        return self.lower, self.upper, self.diag.ptr
+
+    def release(self):
+        for plan in (self.lower, self.upper):
+            if plan is not None:
+                plan.release()
+        if self.diag is not None:
+            self.diag.free()
+        self.lower = self.upper = self.diag = None
 
 
 class HllDevice(_Device):

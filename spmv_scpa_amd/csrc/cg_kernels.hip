@@ -14,7 +14,10 @@
  * preconditioned solver has (k_pcg_first) and the host loop are in this file.
  * The kernels of an iteration -- update, dir, final_init, final_pq, final_rr /
  * final_rz -- are in cg_body.h, written once and included twice below: the
- * k_cg_* and the k_pcg_* kernel of a pair are one text.
+ * k_cg_* and the k_pcg_* kernel of a pair are one text.  The solver
+ * preconditioned by triangular plans (spmv_*_pcg_trsv) has no kernel of its
+ * own: pcgt_start / pcgt_iterate below enqueue the plain vector kernels, the
+ * plans' solves and the finalising kernels of the preconditioned pass.
  *
  * The dot order, the tile of a vector kernel (cg_lanes), the halving trees and
  * the launch macros are in cg_common.h, shared with bicgstab_kernels.hip.
@@ -160,6 +163,9 @@ struct cg_run {
     double *part0, *part1, *part2; /* part2: preconditioned only */
     double *R, *P, *Q;
     hipStream_t s;
+    const cg_plans *plans; /* spmv_*_pcg_trsv only, with Z and err */
+    double *Z;
+    int *err; /* the first refusal of a plan solve */
 };
 
 #define CG_PRE 0
@@ -168,6 +174,44 @@ struct cg_run {
 #define CG_PRE 1
 #include "cg_body.h"
 #undef CG_PRE
+
+/*
+ * spmv_*_pcg_trsv: the preconditioned recurrence with Z = z(R) STORED and made
+ * by the plans (cg_plans, hip_common.h).  No kernel of its own: the plain
+ * update and direction kernels (Z where k_cg_dir has R), k_cg_dot for R.Z in
+ * the dot order, and the finalising kernels of the preconditioned pass, which
+ * read only partial sums and the state.  Z is made for all k columns; a frozen
+ * column's Z reaches nothing, since every consumer is predicated or skips it.
+ */
+static void pcgt_apply(const cg_run &c) {
+    const cg_plans &pl = *c.plans;
+    int rc = trsv_solve_dev(pl.first, pl.waves, c.k, c.R, c.k, c.Z, c.k, NULL,
+                            c.s);
+    if (!rc && pl.second)
+        rc = trsv_solve_dev(pl.second, pl.waves, c.k, c.Z, c.k, c.Z, c.k,
+                            pl.scale, c.s);
+    if (rc && !*c.err)
+        *c.err = rc;
+    CG_LAUNCH(k_cg_dot, c.k, c.M, c.s, c.R, c.k, c.Z, c.k, c.part2);
+}
+
+/* Z = z(R), P = Z, the partials of rz; bb, rr, rz, the first classification */
+static void pcgt_start(const cg_run &c) {
+    pcgt_apply(c);
+    CG_LAUNCH(k_cg_copy, c.k, c.M, c.s, c.Z, c.k, c.P, c.k);
+    CG_FINAL(k_pcg_final_init, c.s, c.k, c.nwg, c.part0, c.part1, c.part2,
+             c.tol2, c.st);
+}
+
+/* one iteration behind the partials of P.Q in part0 */
+static void pcgt_iterate(const cg_run &c) {
+    CG_FINAL(k_pcg_final_pq, c.s, c.k, c.nwg, c.part0, c.st);
+    CG_LAUNCH(k_cg_update, c.k, c.M, c.s, c.st, c.X, c.ldx, c.P, c.R, c.Q,
+              c.part1);
+    pcgt_apply(c);
+    CG_FINAL(k_pcg_final_rz, c.s, c.k, c.nwg, c.part1, c.part2, c.tol2, c.st);
+    CG_LAUNCH(k_cg_dir, c.k, c.M, c.s, c.st, c.Z, c.P);
+}
 
 /* ------------------------------------------------------------------ */
 /* host                                                                 */
@@ -185,24 +229,27 @@ void cg_launch_dot(int k, int M, const double *U, int64_t ldu, const double *V,
 }
 
 /* state, the sets of partial sums (pq, rn; preconditioned: and zn, which is
- * live together with rn), R, P, Q */
+ * live together with rn), R, P, Q (pre == 2, plans: and Z) */
 int64_t cg_work_bytes(int M, int k, int pre) {
     if (M < 0 || k < 1 || k > CG_MAXK)
         return -EINVAL;
     return CG_STATE_BYTES + (pre ? 3 : 2) * CG_PART_BYTES +
-           3 * 8 * (int64_t)M * k;
+           (pre == 2 ? 4 : 3) * 8 * (int64_t)M * k;
 }
 
-/* The host loop of both solvers: minv == NULL is the plain one, else the
+/* The host loop of the three solvers: minv == NULL is the plain one, else the
  * preconditioned one (the CG_PRE 1 pass of cg_body.h, a third set of partial
- * sums).  The arguments were checked by the caller (engine.hip, cg): k in
- * 1..8, ldb, ldx >= k, M == N > 0, tol >= 0, maxit >= 0, check_every > 0. */
+ * sums); plans != NULL (and minv NULL) is the one preconditioned by triangular
+ * plans (pcgt_* above, and a stored Z).  The arguments were checked by the
+ * caller (engine.hip, cg / cg_trsv): k in 1..8, ldb, ldx >= k, M == N > 0,
+ * tol >= 0, maxit >= 0, check_every > 0, live plans of M rows. */
 int cg_solve(const cg_matrix *A, int k, const double *B, int64_t ldb, double *X,
-             int64_t ldx, const double *minv, double tol, int maxit,
-             int check_every, void *d_work, size_t work_bytes,
+             int64_t ldx, const double *minv, const cg_plans *plans, double tol,
+             int maxit, int check_every, void *d_work, size_t work_bytes,
              spmv_cg_info *info, hipStream_t s) {
     const int M = A->M;
-    const size_t need = (size_t)cg_work_bytes(M, k, minv != NULL);
+    const bool pre = minv || plans; /* a third set of partial sums */
+    const size_t need = (size_t)cg_work_bytes(M, k, plans ? 2 : minv != NULL);
     if (d_work && (work_bytes < need || ((uintptr_t)d_work & 7)))
         return -EINVAL;
     /* a capturing stream cannot be synchronised: refuse before anything is
@@ -216,7 +263,7 @@ int cg_solve(const cg_matrix *A, int k, const double *B, int64_t ldb, double *X,
     if (cap != hipStreamCaptureStatusNone)
         return -EBUSY;
 
-    int rc = 0;
+    int rc = 0, plan_rc = 0;
     void *own = NULL;
     cg_state h_st;
     int h_status[CG_MAXK];
@@ -230,14 +277,17 @@ int cg_solve(const cg_matrix *A, int k, const double *B, int64_t ldb, double *X,
         double *part0 = (double *)((char *)d_work + CG_STATE_BYTES);
         double *part1 = part0 + CG_PART_BYTES / 8;
         double *part2 = part1 + CG_PART_BYTES / 8; /* preconditioned only */
-        double *R = minv ? part2 + CG_PART_BYTES / 8 : part2;
+        double *R = pre ? part2 + CG_PART_BYTES / 8 : part2;
         double *P = R + (size_t)M * k;
         double *Q = P + (size_t)M * k;
         const cg_run c = {k, M, (int)cg_grid(M), tol * tol, st, minv, X, ldx,
-                          part0, part1, part2, R, P, Q, s};
+                          part0, part1, part2, R, P, Q, s, plans,
+                          Q + (size_t)M * k, &plan_rc};
         /* the one place the solvers part: which pass of cg_body.h enqueues */
-        void (*const start)(const cg_run &) = minv ? pcg_start : cg_start;
-        void (*const iterate)(const cg_run &) = minv ? pcg_iterate : cg_iterate;
+        void (*const start)(const cg_run &) =
+            plans ? pcgt_start : minv ? pcg_start : cg_start;
+        void (*const iterate)(const cg_run &) =
+            plans ? pcgt_iterate : minv ? pcg_iterate : cg_iterate;
 
         /* R = B - A X; bb, rr; P, the first classification */
         CG_LAUNCH(k_cg_copy, k, M, s, B, ldb, R, k);
@@ -248,6 +298,10 @@ int cg_solve(const cg_matrix *A, int k, const double *B, int64_t ldb, double *X,
         CG_LAUNCH(k_cg_dot, k, M, s, R, k, R, k, part1);
         start(c);
         HIP_TRY(hipGetLastError());
+        if (plan_rc) {
+            rc = plan_rc;
+            goto fail;
+        }
 
         for (int done = 0;;) {
             HIP_TRY(hipMemcpyAsync(h_status, st->status, k * sizeof(int),
@@ -268,6 +322,10 @@ int cg_solve(const cg_matrix *A, int k, const double *B, int64_t ldb, double *X,
                 iterate(c);
             }
             HIP_TRY(hipGetLastError());
+            if (plan_rc) {
+                rc = plan_rc;
+                goto fail;
+            }
             done += batch;
         }
         HIP_TRY(hipMemcpyAsync(&h_st, st, sizeof h_st, hipMemcpyDeviceToHost,

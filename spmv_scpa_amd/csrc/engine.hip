@@ -1058,6 +1058,42 @@ fail:
     return rc;
 }
 
+/* L of A ~ L L^T on A's lower triangle, a new M x M f64 handle
+ * (ic0_kernels.hip) */
+int spmv_csr_ic0(const spmv_csr_dev *A, double shift, int max_levels,
+                 spmv_csr_dev **out, spmv_ic0_info *info) {
+    if (out)
+        *out = NULL; /* on ANY error, the argument checks included */
+    if (!A || !out || !(shift >= 0.0) || !std::isfinite(shift) ||
+        max_levels < 0)
+        return -EINVAL;
+    if (spmv_device_count() == 0)
+        return -ENODEV; /* no handle can be live: the more useful answer */
+    HANDLE_OK(A);
+    if (A->M != A->N)
+        return -EINVAL;
+    if (A->value_bytes != 8)
+        return -ENOTSUP;
+    if (!A->ja && A->NZ > 0)
+        return -ENODATA; /* spmv_csr_release_source() */
+    spmv_csr_dev *d = NULL;
+    spmv_ic0_info got;
+    int rc = ic0_factor_dev(
+        A, shift, max_levels ? max_levels : TRSV_DEFAULT_MAX_LEVELS,
+        g_csr_waves, csr_alloc_dev, &d, &got, 0);
+    if (rc)
+        return rc;
+    rc = finish_csr_handle(d, NULL);
+    if (rc) {
+        spmv_csr_release(d);
+        return rc;
+    }
+    if (info)
+        *info = got;
+    *out = d;
+    return 0;
+}
+
 /* 0: not symmetric, 1: the pattern is, 2: the stored values are too */
 int spmv_csr_symmetry(const spmv_csr_dev *A, int *out) {
     if (!A || !out)
@@ -2082,7 +2118,39 @@ static int cg(const D *d, const spmv_launch_opts *opts, int k,
         return 0;
     }
     const cg_matrix A = {d, opts, d->M, cg_multi_of<D>, cg_axpby_of<D>};
-    return cg_solve(&A, k, d_B, ldb, d_X, ldx, d_minv, tol, maxit,
+    return cg_solve(&A, k, d_B, ldb, d_X, ldx, d_minv, NULL, tol, maxit,
+                    check_every ? check_every : 8, d_work, work_bytes, info,
+                    (hipStream_t)stream);
+}
+
+/* spmv_*_pcg_trsv: cg's checks, then the plans'; the plans run with an opts
+ * that carries only the caller's waves_per_block */
+template <typename D>
+static int cg_trsv(const D *d, const spmv_launch_opts *opts, int k,
+                   const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                   const spmv_trsv_plan *first, const spmv_trsv_plan *second,
+                   const double *d_scale, double tol, int maxit,
+                   int check_every, void *d_work, size_t work_bytes,
+                   spmv_cg_info *info, void *stream) {
+    const int rc = multi_check(d, opts, k, d_B, &ldb, d_X, &ldx);
+    if (rc < 0)
+        return rc;
+    if (d->M != d->N || !(tol >= 0.0) || maxit < 0 || check_every < 0 ||
+        !info || !first || (d_scale && !second))
+        return -EINVAL;
+    if (!live_has(first) || (second && !live_has(second)))
+        return -EBADF;
+    if (first->M != d->M || (second && second->M != d->M))
+        return -EINVAL;
+    if (rc) { /* no rows */
+        for (int j = 0; j < k; ++j)
+            info[j] = spmv_cg_info{0, 0, 0.0, 0.0};
+        return 0;
+    }
+    const cg_matrix A = {d, opts, d->M, cg_multi_of<D>, cg_axpby_of<D>};
+    const cg_plans pl = {first, second, d_scale,
+                         opts ? opts->waves_per_block : 0};
+    return cg_solve(&A, k, d_B, ldb, d_X, ldx, NULL, &pl, tol, maxit,
                     check_every ? check_every : 8, d_work, work_bytes, info,
                     (hipStream_t)stream);
 }
@@ -2798,6 +2866,16 @@ static int copy_tune_log(const D *d, char *buf, size_t len) {
         return cg(d, opts, k, d_B, ldb, d_X, ldx, true, d_minv, tol, maxit,    \
                   check_every, d_work, work_bytes, info, stream);              \
     }                                                                          \
+    int spmv_##fmt##_pcg_trsv(                                                 \
+        const D *d, const spmv_launch_opts *opts, int k, const double *d_B,    \
+        int64_t ldb, double *d_X, int64_t ldx, const spmv_trsv_plan *first,    \
+        const spmv_trsv_plan *second, const double *d_scale, double tol,       \
+        int maxit, int check_every, void *d_work, size_t work_bytes,           \
+        spmv_cg_info *info, void *stream) {                                    \
+        return cg_trsv(d, opts, k, d_B, ldb, d_X, ldx, first, second,          \
+                       d_scale, tol, maxit, check_every, d_work, work_bytes,   \
+                       info, stream);                                          \
+    }                                                                          \
     int spmv_##fmt##_bicgstab(const D *d, const spmv_launch_opts *opts,        \
                               int k, const double *d_B, int64_t ldb,           \
                               double *d_X, int64_t ldx, const double *d_minv,  \
@@ -2899,6 +2977,9 @@ HANDLE_API(hll, spmv_hll_dev, launch_blocks)
 
 int64_t spmv_cg_work_bytes(int M, int k) { return cg_work_bytes(M, k, 0); }
 int64_t spmv_pcg_work_bytes(int M, int k) { return cg_work_bytes(M, k, 1); }
+int64_t spmv_pcg_trsv_work_bytes(int M, int k) {
+    return cg_work_bytes(M, k, 2);
+}
 int64_t spmv_bicgstab_work_bytes(int M, int k) {
     return bicgstab_work_bytes(M, k);
 }

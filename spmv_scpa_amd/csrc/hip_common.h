@@ -2,8 +2,8 @@
  * hip_common.h -- internals shared by the HIP translation units
  * (engine.hip, csr_kernels.hip, hll_kernels.hip, multi_kernels.hip,
  * cg_kernels.hip, bicgstab_kernels.hip, cgls_kernels.hip, minres_kernels.hip,
- * diag_kernels.hip, transpose_kernels.hip, trsv_kernels.hip, panels.hip,
- * mgpu.hip, and
+ * diag_kernels.hip, transpose_kernels.hip, trsv_kernels.hip, ic0_kernels.hip,
+ * panels.hip, mgpu.hip, and
  * mat_ref.h on behalf of the first and the last).
  * Not installed.
  */
@@ -531,13 +531,23 @@ struct cg_matrix {
                  double alpha, double beta, const double *X, int64_t ldx,
                  double *Y, int64_t ldy, hipStream_t s);
 };
+/* the preconditioner of spmv_*_pcg_trsv: Z = z(R) is trsv_solve_dev(first,
+ * R -> Z, no scale), then, with a second plan, trsv_solve_dev(second, Z -> Z in
+ * place, scale), all k columns, `waves` lanes as the caller's opts say */
+struct spmv_trsv_plan;
+struct cg_plans {
+    const spmv_trsv_plan *first, *second; /* second may be NULL */
+    const double *scale;                  /* M doubles or NULL */
+    int waves;
+};
 /* minv == NULL: plain (spmv_*_cg); else preconditioned with z = minv .* r,
- * minv[M] (spmv_*_pcg, pre != 0): the same loop, one more set of partial sums
- * in the work buffer */
+ * minv[M] (spmv_*_pcg, pre == 1): the same loop, one more set of partial sums
+ * in the work buffer.  plans != NULL (minv NULL, pre == 2; spmv_*_pcg_trsv):
+ * the preconditioned loop with a STORED Z = z(R), one more vector behind Q */
 int64_t cg_work_bytes(int M, int k, int pre);
 int cg_solve(const cg_matrix *A, int k, const double *B, int64_t ldb, double *X,
-             int64_t ldx, const double *minv, double tol, int maxit,
-             int check_every, void *d_work, size_t work_bytes,
+             int64_t ldx, const double *minv, const cg_plans *plans, double tol,
+             int maxit, int check_every, void *d_work, size_t work_bytes,
              spmv_cg_info *info, hipStream_t s);
 /* the kernels every solver launches (k_cg_copy, k_cg_dot; k = 1..8): dst = src
  * over M rows of k interleaved columns, and the partial sums of U . V in the
@@ -634,6 +644,20 @@ void trsv_free_dev(spmv_trsv_plan *P); /* the arrays, not P itself */
 int trsv_solve_dev(const spmv_trsv_plan *P, int waves, int k, const double *B,
                    int64_t ldb, double *X, int64_t ldx, const double *scale,
                    hipStream_t s);
+
+/*
+ * Zero-fill incomplete Cholesky (ic0_kernels.hip; spmv_csr_ic0).  The caller
+ * has checked the handle (square, f64, with its source).  *out comes from
+ * `alloc` (engine.hip: csr_alloc_dev) once the pattern passed its check and the
+ * schedule is known, and holds irp, ja and the factor; the caller finishes it
+ * as spmv_csr_transpose does.  waves 0 = each kernel's default.  Blocks; on an
+ * error *out is untouched and everything is freed.
+ */
+typedef int (*ic0_alloc_fn)(int M, int N, int64_t NZ, int value_bytes,
+                            spmv_csr_dev **out);
+int ic0_factor_dev(const spmv_csr_dev *A, double shift, int max_levels,
+                   int waves, ic0_alloc_fn alloc, spmv_csr_dev **out,
+                   spmv_ic0_info *info, hipStream_t s);
 
 /* kernel launchers (csr_kernels.hip / hll_kernels.hip) */
 int csr_launch_kernel(const spmv_csr_dev *A, int kernel, int waves, int group,
