@@ -10,7 +10,9 @@
  * spmv_cg_dot_shape: the tile, the halving trees and the launch macros come
  * from cg_common.h, k_cg_dot and k_cg_copy from cg_kernels.hip through
  * cg_launch_dot / cg_launch_copy.  Here: the four vector kernels, the four
- * finalising kernels, the per-column state and the bounded host loop.
+ * finalising kernels, the per-column state and the launches of a solve in
+ * their order; the refusals, the own work buffer and the bounded host loop are
+ * solver_run (solver_host.h), the buffer is bicgstab_work (solver_work.h).
  *
  * ONE ITERATION, in launch order (Z = z(P) stands in its buffer on entry):
  *   launch_multi        V = A Z
@@ -54,16 +56,6 @@ struct bi_state {
     int iters[CG_MAXK];    /* full steps applied to x */
 };
 static_assert(sizeof(bi_state) <= CG_STATE_BYTES, "state block");
-
-/* running[n]: the column of pass n is running */
-template <int K>
-__device__ __forceinline__ void bi_running(const bi_state *st,
-                                           const cg_lanes<K> &l,
-                                           bool (&running)[K]) {
-#pragma unroll
-    for (int n = 0; n < K; ++n)
-        running[n] = st->status[l.j[n]] == CG_RUNNING;
-}
 
 /* z(u) of one element: rn(minv_i * u), or u itself */
 template <bool PRE>
@@ -116,7 +108,7 @@ k_bi_s(int M, const bi_state *__restrict__ st,
 #pragma clang fp contract(off)
     const cg_lanes<K> l;
     bool running[K];
-    bi_running<K>(st, l, running);
+    cg_running<K>(st, l, running);
     double alpha[K];
 #pragma unroll
     for (int n = 0; n < K; ++n)
@@ -198,7 +190,7 @@ k_bi_update(int M, const bi_state *__restrict__ st,
 #pragma clang fp contract(off)
     const cg_lanes<K> l;
     bool running[K];
-    bi_running<K>(st, l, running);
+    cg_running<K>(st, l, running);
     double alpha[K], omega[K], accr[K], acch[K];
 #pragma unroll
     for (int n = 0; n < K; ++n) {
@@ -260,7 +252,7 @@ k_bi_dir(int M, const bi_state *__restrict__ st,
 #pragma clang fp contract(off)
     const cg_lanes<K> l;
     bool running[K];
-    bi_running<K>(st, l, running);
+    cg_running<K>(st, l, running);
     double omega[K], beta[K];
 #pragma unroll
     for (int n = 0; n < K; ++n) {
@@ -401,27 +393,8 @@ k_bi_final_beta(int k, int nwg, const double *__restrict__ part_rn,
 /* host                                                                 */
 /* ------------------------------------------------------------------ */
 
-/* kernel<k, pre>(M, ...) over the slots of M rows on stream s */
-#define BI_LAUNCH_K(KK, kernel, pre, M, s, ...)                               \
-    do {                                                                      \
-        if (pre)                                                              \
-            hipLaunchKernelGGL((kernel<KK, true>), dim3(cg_grid(M)),          \
-                               dim3(CG_T), 0, s, M, __VA_ARGS__);             \
-        else                                                                  \
-            hipLaunchKernelGGL((kernel<KK, false>), dim3(cg_grid(M)),         \
-                               dim3(CG_T), 0, s, M, __VA_ARGS__);             \
-    } while (0)
-#define BI_LAUNCH(kernel, pre, k, M, s, ...)                                  \
-    CG_K_SWITCH(k, BI_LAUNCH_K, kernel, pre, M, s, __VA_ARGS__)
-
-#define BI_PARTS 2   /* sets of partial sums: (rv | ts | rn | bb), (tt | rhon | rr) */
-#define BI_VECTORS 6 /* R, Rh, P, V, T, Z */
-
 int64_t bicgstab_work_bytes(int M, int k) {
-    if (M < 0 || k < 1 || k > CG_MAXK)
-        return -EINVAL;
-    return CG_STATE_BYTES + BI_PARTS * CG_PART_BYTES +
-           BI_VECTORS * 8 * (int64_t)M * k;
+    return solver_work_bytes(bicgstab_work(M, k));
 }
 
 /* The arguments were checked by the caller (engine.hip, bicgstab): k in 1..8,
@@ -432,103 +405,63 @@ int bicgstab_solve(const cg_matrix *A, int k, const double *B, int64_t ldb,
                    spmv_cg_info *info, hipStream_t s) {
     const int M = A->M;
     const bool pre = minv != NULL;
-    const size_t need = (size_t)bicgstab_work_bytes(M, k);
-    if (d_work && (work_bytes < need || ((uintptr_t)d_work & 7)))
-        return -EINVAL;
-    /* a capturing stream cannot be synchronised: refuse before anything is
-     * allocated or enqueued, so the capture stays valid */
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const hipError_t ce = hipStreamIsCapturing(s, &cap);
-    if (ce != hipSuccess) {
-        (void)hipGetLastError();
-        return ce == hipErrorStreamCaptureImplicit ? -EBUSY : hip_errno(ce);
-    }
-    if (cap != hipStreamCaptureStatusNone)
-        return -EBUSY;
-
-    int rc = 0;
-    void *own = NULL;
-    bi_state h_st;
-    int h_status[CG_MAXK];
-    (void)hipGetLastError(); /* an earlier caller's unread error is not ours */
-    if (!d_work) {
-        HIP_TRY(hipMalloc(&own, need));
-        d_work = own;
-    }
-    {
-        bi_state *st = (bi_state *)d_work;
-        double *part0 = (double *)((char *)d_work + CG_STATE_BYTES);
-        double *part1 = part0 + CG_PART_BYTES / 8;
-        double *R = part1 + CG_PART_BYTES / 8;
-        double *Rh = R + (size_t)M * k;
-        double *P = Rh + (size_t)M * k;
-        double *V = P + (size_t)M * k;
-        double *T = V + (size_t)M * k;
-        double *Z = T + (size_t)M * k;
-        const int nwg = (int)cg_grid(M);
-        const double tol2 = tol * tol;
-
+    const solver_work w = bicgstab_work(M, k);
+    const int nwg = (int)cg_grid(M);
+    const double tol2 = tol * tol;
+    bi_state *st = NULL;
+    double *part0 = NULL, *part1 = NULL;
+    double *R = NULL, *Rh = NULL, *P = NULL, *V = NULL, *T = NULL, *Z = NULL;
+    bi_state h;
+    const int rc = solver_run(
+        w, maxit, check_every, d_work, work_bytes, &h, s,
         /* R = B - A X; Rh = P = R, Z = z(P); bb, rr, the first classification */
-        cg_launch_copy(k, M, B, ldb, R, k, s);
-        rc = A->axpby(A->handle, A->opts, k, -1.0, 1.0, X, ldx, R, k, s);
-        if (rc)
-            goto fail;
-        BI_LAUNCH(k_bi_first, pre, k, M, s, minv, R, Rh, P, Z);
-        cg_launch_dot(k, M, B, ldb, B, ldb, part0, s);
-        cg_launch_dot(k, M, R, k, R, k, part1, s);
-        CG_FINAL(k_bi_final_init, s, k, nwg, part0, part1, tol2, st);
-        HIP_TRY(hipGetLastError());
-
-        for (int done = 0;;) {
-            HIP_TRY(hipMemcpyAsync(h_status, st->status, k * sizeof(int),
-                                   hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            bool running = false;
-            for (int j = 0; j < k; ++j)
-                running = running || h_status[j] == CG_RUNNING;
-            if (!running || done >= maxit)
-                break;
-            const int batch = maxit - done < check_every ? maxit - done
-                                                         : check_every;
-            for (int it = 0; it < batch; ++it) {
-                rc = A->multi(A->handle, A->opts, k, Z, k, V, k, s);
-                if (rc)
-                    goto fail;
-                cg_launch_dot(k, M, Rh, k, V, k, part0, s);
-                CG_FINAL(k_bi_final_alpha, s, k, nwg, part0, st);
-                BI_LAUNCH(k_bi_s, pre, k, M, s, st, minv, R, V, Z);
-                rc = A->multi(A->handle, A->opts, k, Z, k, T, k, s);
-                if (rc)
-                    goto fail;
-                CG_LAUNCH(k_bi_tstt, k, M, s, T, R, part0, part1);
-                CG_FINAL(k_bi_final_omega, s, k, nwg, part0, part1, st);
-                BI_LAUNCH(k_bi_update, pre, k, M, s, st, minv, X, ldx, P, R, T,
-                          Rh, part0, part1);
-                CG_FINAL(k_bi_final_beta, s, k, nwg, part0, part1, tol2, st);
-                BI_LAUNCH(k_bi_dir, pre, k, M, s, st, minv, R, V, P, Z);
-            }
-            HIP_TRY(hipGetLastError());
-            done += batch;
-        }
-        HIP_TRY(hipMemcpyAsync(&h_st, st, sizeof h_st, hipMemcpyDeviceToHost,
-                               s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
+        [&](void *work) {
+            st = (bi_state *)work;
+            part0 = solver_part(work, w, 0);
+            part1 = solver_part(work, w, 1);
+            R = solver_vec(work, w, 0);
+            Rh = solver_vec(work, w, 1);
+            P = solver_vec(work, w, 2);
+            V = solver_vec(work, w, 3);
+            T = solver_vec(work, w, 4);
+            Z = solver_vec(work, w, 5);
+            cg_launch_copy(k, M, B, ldb, R, k, s);
+            const int rc =
+                A->axpby(A->handle, A->opts, k, -1.0, 1.0, X, ldx, R, k, s);
+            if (rc)
+                return rc;
+            CG_LAUNCH_FLAG(k_bi_first, pre, k, M, s, minv, R, Rh, P, Z);
+            cg_launch_dot(k, M, B, ldb, B, ldb, part0, s);
+            cg_launch_dot(k, M, R, k, R, k, part1, s);
+            CG_FINAL(k_bi_final_init, s, k, nwg, part0, part1, tol2, st);
+            return 0;
+        },
+        [&](int) {
+            int rc = A->multi(A->handle, A->opts, k, Z, k, V, k, s);
+            if (rc)
+                return rc;
+            cg_launch_dot(k, M, Rh, k, V, k, part0, s);
+            CG_FINAL(k_bi_final_alpha, s, k, nwg, part0, st);
+            CG_LAUNCH_FLAG(k_bi_s, pre, k, M, s, st, minv, R, V, Z);
+            rc = A->multi(A->handle, A->opts, k, Z, k, T, k, s);
+            if (rc)
+                return rc;
+            CG_LAUNCH(k_bi_tstt, k, M, s, T, R, part0, part1);
+            CG_FINAL(k_bi_final_omega, s, k, nwg, part0, part1, st);
+            CG_LAUNCH_FLAG(k_bi_update, pre, k, M, s, st, minv, X, ldx, P, R,
+                           T, Rh, part0, part1);
+            CG_FINAL(k_bi_final_beta, s, k, nwg, part0, part1, tol2, st);
+            CG_LAUNCH_FLAG(k_bi_dir, pre, k, M, s, st, minv, R, V, P, Z);
+            return 0;
+        },
+        [] { return 0; });
+    if (rc)
+        return rc;
     for (int j = 0; j < k; ++j) {
-        info[j].status =
-            h_st.status[j] == CG_RUNNING ? CG_MAXIT : h_st.status[j];
-        info[j].iterations = h_st.iters[j];
-        info[j].rr = h_st.rr[j];
-        info[j].bb = h_st.bb[j];
+        info[j].status = h.status[j];
+        info[j].iterations = h.iters[j];
+        info[j].rr = h.rr[j];
+        info[j].bb = h.bb[j];
     }
-    if (own)
-        rc = hip_errno(hipFree(own));
-    return rc;
-fail:
-    /* nothing of ours may still run when the work buffer goes */
-    (void)hipStreamSynchronize(s);
-    if (own)
-        (void)hipFree(own);
-    (void)hipGetLastError();
-    return rc;
+    return 0;
 }

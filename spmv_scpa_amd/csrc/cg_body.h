@@ -52,7 +52,7 @@ CG_KERNEL(k_cg_update, k_pcg_update)(
 #pragma clang fp contract(off)
     const cg_lanes<K> l;
     bool running[K];
-    running_passes<K>(st, l, running);
+    cg_running<K>(st, l, running);
     double alpha[K], acc[K];
 #if CG_PRE
     double accz[K];
@@ -127,7 +127,7 @@ CG_KERNEL(k_cg_dir, k_pcg_dir)(int M, const cg_state *__restrict__ st,
 #pragma clang fp contract(off)
     const cg_lanes<K> l;
     bool running[K];
-    running_passes<K>(st, l, running);
+    cg_running<K>(st, l, running);
     double beta[K];
 #pragma unroll
     for (int n = 0; n < K; ++n)

@@ -2,11 +2,14 @@
  * cg_common.h -- what the device-resident solvers share (cg_kernels.hip:
  * spmv_*_cg / spmv_*_pcg; bicgstab_kernels.hip: spmv_*_bicgstab;
  * cgls_kernels.hip: spmv_*_cgls; minres_kernels.hip: spmv_*_minres): the tile
- * of a vector kernel, the two halving trees of the dot order, the finite test
- * and the launch macros.  One text, included by these files; the two kernels
- * every solver launches (k_cg_copy, k_cg_dot) stay in cg_kernels.hip and are
- * reached through cg_launch_copy / cg_launch_dot (hip_common.h), so they exist
- * once in the library.
+ * of a vector kernel, the two halving trees of the dot order, the finite test,
+ * the frozen-column test (cg_running) and the launch macros.  One text,
+ * included by these files; the two kernels every solver launches (k_cg_copy,
+ * k_cg_dot) stay in cg_kernels.hip and are reached through cg_launch_copy /
+ * cg_launch_dot (hip_common.h), so they exist once in the library.  The host
+ * side the solvers share is included from here too: the work buffer
+ * (solver_work.h, through hip_common.h) and the refusals, the own buffer and
+ * the bounded loop of a solve (solver_host.h, solver_run).
  *
  * DOT ORDER, a function of M alone (CG_NWG, CG_T are constants of the
  * library, exported to the tests as spmv_cg_dot_shape):
@@ -20,9 +23,8 @@
 #ifndef SPMV_CG_COMMON_H
 #define SPMV_CG_COMMON_H
 
-#include "hip_common.h"
+#include "solver_host.h"
 
-#define CG_MAXK 8
 #define CG_FINAL_T 1024 /* threads of a finalising workgroup, >= CG_NWG */
 
 static_assert(CG_FINAL_T >= CG_NWG && (CG_NWG & (CG_NWG - 1)) == 0 &&
@@ -54,6 +56,17 @@ template <int K> struct cg_lanes {
         }
     }
 };
+
+/* running[n]: the column of pass n is running (State: a solver's state block,
+ * with its status[CG_MAXK]) */
+template <int K, typename State>
+__device__ __forceinline__ void cg_running(const State *st,
+                                           const cg_lanes<K> &l,
+                                           bool (&running)[K]) {
+#pragma unroll
+    for (int n = 0; n < K; ++n)
+        running[n] = st->status[l.j[n]] == CG_RUNNING;
+}
 
 /* The slot sums of a workgroup -> part[blockIdx.x * K + j]: the halving tree
  * of the dot order.  All CG_T threads call. */
@@ -133,6 +146,19 @@ static inline unsigned cg_grid(int M) {
                        __VA_ARGS__)
 #define CG_LAUNCH(kernel, k, M, s, ...)                                       \
     CG_K_SWITCH(k, CG_LAUNCH_K, kernel, M, s, __VA_ARGS__)
+/* kernel<k, flag>(M, ...) the same way: the vector kernels with a second, bool
+ * template argument (a preconditioner, a damping term, the first iteration) */
+#define CG_LAUNCH_FLAG_K(KK, kernel, flag, M, s, ...)                         \
+    do {                                                                      \
+        if (flag)                                                             \
+            hipLaunchKernelGGL((kernel<KK, true>), dim3(cg_grid(M)),          \
+                               dim3(CG_T), 0, s, M, __VA_ARGS__);             \
+        else                                                                  \
+            hipLaunchKernelGGL((kernel<KK, false>), dim3(cg_grid(M)),         \
+                               dim3(CG_T), 0, s, M, __VA_ARGS__);             \
+    } while (0)
+#define CG_LAUNCH_FLAG(kernel, flag, k, M, s, ...)                            \
+    CG_K_SWITCH(k, CG_LAUNCH_FLAG_K, kernel, flag, M, s, __VA_ARGS__)
 /* kernel(...) in one workgroup on stream s: every finalising kernel */
 #define CG_FINAL(kernel, s, ...)                                              \
     hipLaunchKernelGGL(kernel, dim3(1), dim3(CG_FINAL_T), 0, s, __VA_ARGS__)

@@ -6,12 +6,14 @@
  *
  * The product Q = A P and the initial residual are the handle's launch_multi /
  * launch_axpby (two function pointers, cg_matrix); everything else is here:
- * the fixed-order dot, the two fused vector updates, the per-column state and
- * the bounded host loop.  Templates over the number of vectors K, as in
- * multi_kernels.hip.
+ * the fixed-order dot, the two fused vector updates and the per-column state.
+ * Templates over the number of vectors K, as in multi_kernels.hip.  The host
+ * side -- the refusals, the own work buffer, the bounded loop -- is
+ * solver_run (solver_host.h), shared with the other solvers; cg_solve gives it
+ * the buffer (cg_work, solver_work.h) and its launches.
  *
- * The kernels both solvers launch (k_cg_copy, k_cg_dot), the one only the
- * preconditioned solver has (k_pcg_first) and the host loop are in this file.
+ * The kernels both solvers launch (k_cg_copy, k_cg_dot) and the one only the
+ * preconditioned solver has (k_pcg_first) are in this file.
  * The kernels of an iteration -- update, dir, final_init, final_pq, final_rr /
  * final_rz -- are in cg_body.h, written once and included twice below: the
  * k_cg_* and the k_pcg_* kernel of a pair are one text.  The solver
@@ -20,7 +22,7 @@
  * plans' solves and the finalising kernels of the preconditioned pass.
  *
  * The dot order, the tile of a vector kernel (cg_lanes), the halving trees and
- * the launch macros are in cg_common.h, shared with bicgstab_kernels.hip.
+ * the launch macros are in cg_common.h, shared with the other solvers.
  *
  * STATE.  alpha, beta, rr, bb, status and the iteration count of every column
  * live in one cg_state block at the head of the work buffer.  It is written
@@ -50,16 +52,6 @@ struct cg_state {
                               only; behind the fields the plain kernels use) */
 };
 static_assert(sizeof(cg_state) <= CG_STATE_BYTES, "state block");
-
-/* running[n]: the column of pass n is running */
-template <int K>
-__device__ __forceinline__ void running_passes(const cg_state *st,
-                                               const cg_lanes<K> &l,
-                                               bool (&running)[K]) {
-#pragma unroll
-    for (int n = 0; n < K; ++n)
-        running[n] = st->status[l.j[n]] == CG_RUNNING;
-}
 
 /* dst[i * ldd + j] = src[i * lds + j], j < K (R = B, P = R) */
 template <int K>
@@ -228,125 +220,69 @@ void cg_launch_dot(int k, int M, const double *U, int64_t ldu, const double *V,
     CG_LAUNCH(k_cg_dot, k, M, s, U, ldu, V, ldv, part);
 }
 
-/* state, the sets of partial sums (pq, rn; preconditioned: and zn, which is
- * live together with rn), R, P, Q (pre == 2, plans: and Z) */
 int64_t cg_work_bytes(int M, int k, int pre) {
-    if (M < 0 || k < 1 || k > CG_MAXK)
-        return -EINVAL;
-    return CG_STATE_BYTES + (pre ? 3 : 2) * CG_PART_BYTES +
-           (pre == 2 ? 4 : 3) * 8 * (int64_t)M * k;
+    return solver_work_bytes(cg_work(M, k, pre));
 }
 
-/* The host loop of the three solvers: minv == NULL is the plain one, else the
- * preconditioned one (the CG_PRE 1 pass of cg_body.h, a third set of partial
- * sums); plans != NULL (and minv NULL) is the one preconditioned by triangular
- * plans (pcgt_* above, and a stored Z).  The arguments were checked by the
- * caller (engine.hip, cg / cg_trsv): k in 1..8, ldb, ldx >= k, M == N > 0,
- * tol >= 0, maxit >= 0, check_every > 0, live plans of M rows. */
+/* The three solvers on the loop of solver_host.h: minv == NULL is the plain
+ * one, else the preconditioned one (the CG_PRE 1 pass of cg_body.h, a third
+ * set of partial sums); plans != NULL (and minv NULL) is the one
+ * preconditioned by triangular plans (pcgt_* above, and a stored Z).  The
+ * arguments were checked by the caller (engine.hip, cg / cg_trsv): k in 1..8,
+ * ldb, ldx >= k, M == N > 0, tol >= 0, maxit >= 0, check_every > 0, live plans
+ * of M rows. */
 int cg_solve(const cg_matrix *A, int k, const double *B, int64_t ldb, double *X,
              int64_t ldx, const double *minv, const cg_plans *plans, double tol,
              int maxit, int check_every, void *d_work, size_t work_bytes,
              spmv_cg_info *info, hipStream_t s) {
     const int M = A->M;
-    const bool pre = minv || plans; /* a third set of partial sums */
-    const size_t need = (size_t)cg_work_bytes(M, k, plans ? 2 : minv != NULL);
-    if (d_work && (work_bytes < need || ((uintptr_t)d_work & 7)))
-        return -EINVAL;
-    /* a capturing stream cannot be synchronised: refuse before anything is
-     * allocated or enqueued, so the capture stays valid */
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const hipError_t ce = hipStreamIsCapturing(s, &cap);
-    if (ce != hipSuccess) {
-        (void)hipGetLastError();
-        return ce == hipErrorStreamCaptureImplicit ? -EBUSY : hip_errno(ce);
-    }
-    if (cap != hipStreamCaptureStatusNone)
-        return -EBUSY;
-
-    int rc = 0, plan_rc = 0;
-    void *own = NULL;
-    cg_state h_st;
-    int h_status[CG_MAXK];
-    (void)hipGetLastError(); /* an earlier caller's unread error is not ours */
-    if (!d_work) {
-        HIP_TRY(hipMalloc(&own, need));
-        d_work = own;
-    }
-    {
-        cg_state *st = (cg_state *)d_work;
-        double *part0 = (double *)((char *)d_work + CG_STATE_BYTES);
-        double *part1 = part0 + CG_PART_BYTES / 8;
-        double *part2 = part1 + CG_PART_BYTES / 8; /* preconditioned only */
-        double *R = pre ? part2 + CG_PART_BYTES / 8 : part2;
-        double *P = R + (size_t)M * k;
-        double *Q = P + (size_t)M * k;
-        const cg_run c = {k, M, (int)cg_grid(M), tol * tol, st, minv, X, ldx,
-                          part0, part1, part2, R, P, Q, s, plans,
-                          Q + (size_t)M * k, &plan_rc};
-        /* the one place the solvers part: which pass of cg_body.h enqueues */
-        void (*const start)(const cg_run &) =
-            plans ? pcgt_start : minv ? pcg_start : cg_start;
-        void (*const iterate)(const cg_run &) =
-            plans ? pcgt_iterate : minv ? pcg_iterate : cg_iterate;
-
+    const solver_work w = cg_work(M, k, plans ? 2 : minv != NULL);
+    /* the one place the solvers part: which pass of cg_body.h enqueues */
+    void (*const start)(const cg_run &) =
+        plans ? pcgt_start : minv ? pcg_start : cg_start;
+    void (*const iterate)(const cg_run &) =
+        plans ? pcgt_iterate : minv ? pcg_iterate : cg_iterate;
+    int plan_rc = 0;
+    cg_run c = {};
+    cg_state h;
+    const int rc = solver_run(
+        w, maxit, check_every, d_work, work_bytes, &h, s,
         /* R = B - A X; bb, rr; P, the first classification */
-        CG_LAUNCH(k_cg_copy, k, M, s, B, ldb, R, k);
-        rc = A->axpby(A->handle, A->opts, k, -1.0, 1.0, X, ldx, R, k, s);
-        if (rc)
-            goto fail;
-        CG_LAUNCH(k_cg_dot, k, M, s, B, ldb, B, ldb, part0);
-        CG_LAUNCH(k_cg_dot, k, M, s, R, k, R, k, part1);
-        start(c);
-        HIP_TRY(hipGetLastError());
-        if (plan_rc) {
-            rc = plan_rc;
-            goto fail;
-        }
-
-        for (int done = 0;;) {
-            HIP_TRY(hipMemcpyAsync(h_status, st->status, k * sizeof(int),
-                                   hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            bool running = false;
-            for (int j = 0; j < k; ++j)
-                running = running || h_status[j] == CG_RUNNING;
-            if (!running || done >= maxit)
-                break;
-            const int batch = maxit - done < check_every ? maxit - done
-                                                         : check_every;
-            for (int it = 0; it < batch; ++it) {
-                rc = A->multi(A->handle, A->opts, k, P, k, Q, k, s);
-                if (rc)
-                    goto fail;
-                CG_LAUNCH(k_cg_dot, k, M, s, P, k, Q, k, part0);
-                iterate(c);
-            }
-            HIP_TRY(hipGetLastError());
-            if (plan_rc) {
-                rc = plan_rc;
-                goto fail;
-            }
-            done += batch;
-        }
-        HIP_TRY(hipMemcpyAsync(&h_st, st, sizeof h_st, hipMemcpyDeviceToHost,
-                               s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
+        [&](void *work) {
+            /* part2 and Z of a solver without them: where the next region
+             * starts, and never used */
+            c = cg_run{k, M, (int)cg_grid(M), tol * tol, (cg_state *)work,
+                       minv, X, ldx, solver_part(work, w, 0),
+                       solver_part(work, w, 1), solver_part(work, w, 2),
+                       solver_vec(work, w, 0), solver_vec(work, w, 1),
+                       solver_vec(work, w, 2), s, plans,
+                       solver_vec(work, w, 3), &plan_rc};
+            CG_LAUNCH(k_cg_copy, k, M, s, B, ldb, c.R, k);
+            const int rc =
+                A->axpby(A->handle, A->opts, k, -1.0, 1.0, X, ldx, c.R, k, s);
+            if (rc)
+                return rc;
+            CG_LAUNCH(k_cg_dot, k, M, s, B, ldb, B, ldb, c.part0);
+            CG_LAUNCH(k_cg_dot, k, M, s, c.R, k, c.R, k, c.part1);
+            start(c);
+            return plan_rc;
+        },
+        [&](int) {
+            const int rc = A->multi(A->handle, A->opts, k, c.P, k, c.Q, k, s);
+            if (rc)
+                return rc;
+            CG_LAUNCH(k_cg_dot, k, M, s, c.P, k, c.Q, k, c.part0);
+            iterate(c);
+            return plan_rc;
+        },
+        [] { return 0; });
+    if (rc)
+        return rc;
     for (int j = 0; j < k; ++j) {
-        info[j].status =
-            h_st.status[j] == CG_RUNNING ? CG_MAXIT : h_st.status[j];
-        info[j].iterations = h_st.iters[j];
-        info[j].rr = h_st.rr[j];
-        info[j].bb = h_st.bb[j];
+        info[j].status = h.status[j];
+        info[j].iterations = h.iters[j];
+        info[j].rr = h.rr[j];
+        info[j].bb = h.bb[j];
     }
-    if (own)
-        rc = hip_errno(hipFree(own));
-    return rc;
-fail:
-    /* nothing of ours may still run when the work buffer goes */
-    (void)hipStreamSynchronize(s);
-    if (own)
-        (void)hipFree(own);
-    (void)hipGetLastError();
-    return rc;
+    return 0;
 }

@@ -13,7 +13,9 @@
  * cg_kernels.hip), the initial residual A's launch_axpby.  The dot is the dot
  * of spmv_cg_dot_shape over the length of its operands: the tile, the halving
  * trees and the launch macros come from cg_common.h, k_cg_dot and k_cg_copy
- * from cg_kernels.hip through cg_launch_dot / cg_launch_copy.
+ * from cg_kernels.hip through cg_launch_dot / cg_launch_copy.  The refusals,
+ * the own work buffer and the bounded host loop are solver_run (solver_host.h);
+ * the buffer, with its vectors of both lengths, is cgls_work (solver_work.h).
  *
  * ONE ITERATION, in launch order:
  *   launch_multi(A)     Q = A P
@@ -54,16 +56,6 @@ struct ls_state {
     int iters[CG_MAXK];    /* updates of x */
 };
 static_assert(sizeof(ls_state) <= CG_STATE_BYTES, "state block");
-
-/* running[n]: the column of pass n is running */
-template <int K>
-__device__ __forceinline__ void ls_running(const ls_state *st,
-                                           const cg_lanes<K> &l,
-                                           bool (&running)[K]) {
-#pragma unroll
-    for (int n = 0; n < K; ++n)
-        running[n] = st->status[l.j[n]] == CG_RUNNING;
-}
 
 /* after S = AT R, N rows: DAMP: S <- S - d2 X;  P = S;  the partials of S . S
  * (DAMP: to part_pp too -- P . P of the first delta is the same sum); all
@@ -123,7 +115,7 @@ k_ls_update(int L, int M, int N, const ls_state *__restrict__ st,
     (void)L; /* the launch macro's length: max(M, N) */
     const cg_lanes<K> l;
     bool running[K];
-    ls_running<K>(st, l, running);
+    cg_running<K>(st, l, running);
     double alpha[K];
 #pragma unroll
     for (int n = 0; n < K; ++n)
@@ -210,7 +202,7 @@ k_ls_dir(int N, const ls_state *__restrict__ st, const double *__restrict__ S,
 #pragma clang fp contract(off)
     const cg_lanes<K> l;
     bool running[K];
-    ls_running<K>(st, l, running);
+    cg_running<K>(st, l, running);
     double beta[K], acc[K];
 #pragma unroll
     for (int n = 0; n < K; ++n) {
@@ -347,27 +339,8 @@ k_ls_final_rr(int k, int nwg, const double *__restrict__ part_rr,
 /* host                                                                 */
 /* ------------------------------------------------------------------ */
 
-/* kernel<k, damp>(L, ...) over the slots of L rows on stream s */
-#define LS_LAUNCH_K(KK, kernel, damp, L, s, ...)                              \
-    do {                                                                      \
-        if (damp)                                                             \
-            hipLaunchKernelGGL((kernel<KK, true>), dim3(cg_grid(L)),          \
-                               dim3(CG_T), 0, s, L, __VA_ARGS__);             \
-        else                                                                  \
-            hipLaunchKernelGGL((kernel<KK, false>), dim3(cg_grid(L)),         \
-                               dim3(CG_T), 0, s, L, __VA_ARGS__);             \
-    } while (0)
-#define LS_LAUNCH(kernel, damp, k, L, s, ...)                                 \
-    CG_K_SWITCH(k, LS_LAUNCH_K, kernel, damp, L, s, __VA_ARGS__)
-
-#define LS_PARTS 3 /* sets of partial sums: (qq | ss | sn | rr), atb, pp */
-
-/* the state and the sets of partial sums; R, Q of M rows, S, P of N rows */
 int64_t cgls_work_bytes(int M, int N, int k) {
-    if (M < 0 || N < 0 || k < 1 || k > CG_MAXK)
-        return -EINVAL;
-    return CG_STATE_BYTES + LS_PARTS * CG_PART_BYTES +
-           8 * (int64_t)k * (2 * (int64_t)M + 2 * (int64_t)N);
+    return solver_work_bytes(cgls_work(M, N, k));
 }
 
 /* The arguments were checked by the caller (engine.hip, cgls): k in 1..8,
@@ -380,120 +353,82 @@ int cgls_solve(const cg_matrix *A, const cg_matrix *AT, int k, const double *B,
     const int M = A->M, N = AT->M;
     const int L = M > N ? M : N;
     const bool damped = damp != 0.0;
-    const size_t need = (size_t)cgls_work_bytes(M, N, k);
-    if (d_work && (work_bytes < need || ((uintptr_t)d_work & 7)))
-        return -EINVAL;
-    /* a capturing stream cannot be synchronised: refuse before anything is
-     * allocated or enqueued, so the capture stays valid */
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const hipError_t ce = hipStreamIsCapturing(s, &cap);
-    if (ce != hipSuccess) {
-        (void)hipGetLastError();
-        return ce == hipErrorStreamCaptureImplicit ? -EBUSY : hip_errno(ce);
-    }
-    if (cap != hipStreamCaptureStatusNone)
-        return -EBUSY;
-
-    int rc = 0;
-    void *own = NULL;
-    ls_state h_st;
-    int h_status[CG_MAXK];
-    (void)hipGetLastError(); /* an earlier caller's unread error is not ours */
-    if (!d_work) {
-        HIP_TRY(hipMalloc(&own, need));
-        d_work = own;
-    }
-    {
-        ls_state *st = (ls_state *)d_work;
-        double *part0 = (double *)((char *)d_work + CG_STATE_BYTES);
-        double *part1 = part0 + CG_PART_BYTES / 8;
-        double *part2 = part1 + CG_PART_BYTES / 8;
-        double *R = part2 + CG_PART_BYTES / 8;
-        double *Q = R + (size_t)M * k;
-        double *S = Q + (size_t)M * k;
-        double *P = S + (size_t)N * k;
-        const int nwg_m = (int)cg_grid(M), nwg_n = (int)cg_grid(N);
-        const double tol2 = tol * tol;
-        const double d2 = damp * damp;
-
+    const solver_work w = cgls_work(M, N, k);
+    const int nwg_m = (int)cg_grid(M), nwg_n = (int)cg_grid(N);
+    const double tol2 = tol * tol;
+    const double d2 = damp * damp;
+    ls_state *st = NULL;
+    double *part0 = NULL, *part1 = NULL, *part2 = NULL;
+    double *R = NULL, *Q = NULL, *S = NULL, *P = NULL;
+    ls_state h;
+    const int rc = solver_run(
+        w, maxit, check_every, d_work, work_bytes, &h, s,
         /* R = B - A X;  W = AT B in S's storage, atb;  S = AT R (- d2 X),
          * P = S, ss;  the first classification */
-        cg_launch_copy(k, M, B, ldb, R, k, s);
-        rc = A->axpby(A->handle, A->opts, k, -1.0, 1.0, X, ldx, R, k, s);
-        if (rc)
-            goto fail;
-        rc = AT->multi(AT->handle, AT->opts, k, B, ldb, S, k, s);
-        if (rc)
-            goto fail;
-        cg_launch_dot(k, N, S, k, S, k, part1, s);
-        rc = AT->multi(AT->handle, AT->opts, k, R, k, S, k, s);
-        if (rc)
-            goto fail;
-        LS_LAUNCH(k_ls_first, damped, k, N, s, d2, X, ldx, S, P, part0, part2);
-        CG_FINAL(k_ls_final_init, s, k, nwg_n, part0, part1, tol2, st);
-        HIP_TRY(hipGetLastError());
-
-        for (int done = 0;;) {
-            HIP_TRY(hipMemcpyAsync(h_status, st->status, k * sizeof(int),
-                                   hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            bool running = false;
-            for (int j = 0; j < k; ++j)
-                running = running || h_status[j] == CG_RUNNING;
-            if (!running || done >= maxit)
-                break;
-            const int batch = maxit - done < check_every ? maxit - done
-                                                         : check_every;
-            for (int it = 0; it < batch; ++it) {
-                rc = A->multi(A->handle, A->opts, k, P, k, Q, k, s);
-                if (rc)
-                    goto fail;
-                cg_launch_dot(k, M, Q, k, Q, k, part0, s);
-                if (damped) {
-                    CG_FINAL(k_ls_final_alpha<true>, s, k, nwg_m, part0, nwg_n,
-                             part2, d2, st);
-                } else {
-                    CG_FINAL(k_ls_final_alpha<false>, s, k, nwg_m, part0,
-                             nwg_n, part2, d2, st);
-                }
-                CG_LAUNCH(k_ls_update, k, L, s, M, N, st, X, ldx, P, R, Q);
-                rc = AT->multi(AT->handle, AT->opts, k, R, k, S, k, s);
-                if (rc)
-                    goto fail;
-                if (damped) {
-                    CG_LAUNCH(k_ls_damp, k, N, s, d2, X, ldx, S, part0);
-                } else {
-                    cg_launch_dot(k, N, S, k, S, k, part0, s);
-                }
-                CG_FINAL(k_ls_final_beta, s, k, nwg_n, part0, tol2, st);
-                LS_LAUNCH(k_ls_dir, damped, k, N, s, st, S, P, part2);
+        [&](void *work) {
+            st = (ls_state *)work;
+            part0 = solver_part(work, w, 0);
+            part1 = solver_part(work, w, 1);
+            part2 = solver_part(work, w, 2);
+            R = solver_vec(work, w, 0);
+            Q = solver_vec(work, w, 1);
+            S = solver_vec(work, w, 2);
+            P = solver_vec(work, w, 3);
+            cg_launch_copy(k, M, B, ldb, R, k, s);
+            int rc = A->axpby(A->handle, A->opts, k, -1.0, 1.0, X, ldx, R, k, s);
+            if (rc)
+                return rc;
+            rc = AT->multi(AT->handle, AT->opts, k, B, ldb, S, k, s);
+            if (rc)
+                return rc;
+            cg_launch_dot(k, N, S, k, S, k, part1, s);
+            rc = AT->multi(AT->handle, AT->opts, k, R, k, S, k, s);
+            if (rc)
+                return rc;
+            CG_LAUNCH_FLAG(k_ls_first, damped, k, N, s, d2, X, ldx, S, P, part0,
+                           part2);
+            CG_FINAL(k_ls_final_init, s, k, nwg_n, part0, part1, tol2, st);
+            return 0;
+        },
+        [&](int) {
+            int rc = A->multi(A->handle, A->opts, k, P, k, Q, k, s);
+            if (rc)
+                return rc;
+            cg_launch_dot(k, M, Q, k, Q, k, part0, s);
+            if (damped) {
+                CG_FINAL(k_ls_final_alpha<true>, s, k, nwg_m, part0, nwg_n,
+                         part2, d2, st);
+            } else {
+                CG_FINAL(k_ls_final_alpha<false>, s, k, nwg_m, part0, nwg_n,
+                         part2, d2, st);
             }
-            HIP_TRY(hipGetLastError());
-            done += batch;
-        }
-        cg_launch_dot(k, M, R, k, R, k, part0, s);
-        CG_FINAL(k_ls_final_rr, s, k, nwg_m, part0, st);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&h_st, st, sizeof h_st, hipMemcpyDeviceToHost,
-                               s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
+            CG_LAUNCH(k_ls_update, k, L, s, M, N, st, X, ldx, P, R, Q);
+            rc = AT->multi(AT->handle, AT->opts, k, R, k, S, k, s);
+            if (rc)
+                return rc;
+            if (damped) {
+                CG_LAUNCH(k_ls_damp, k, N, s, d2, X, ldx, S, part0);
+            } else {
+                cg_launch_dot(k, N, S, k, S, k, part0, s);
+            }
+            CG_FINAL(k_ls_final_beta, s, k, nwg_n, part0, tol2, st);
+            CG_LAUNCH_FLAG(k_ls_dir, damped, k, N, s, st, S, P, part2);
+            return 0;
+        },
+        /* rr of the true residual, once */
+        [&] {
+            cg_launch_dot(k, M, R, k, R, k, part0, s);
+            CG_FINAL(k_ls_final_rr, s, k, nwg_m, part0, st);
+            return hip_errno(hipGetLastError());
+        });
+    if (rc)
+        return rc;
     for (int j = 0; j < k; ++j) {
-        info[j].status =
-            h_st.status[j] == CG_RUNNING ? CG_MAXIT : h_st.status[j];
-        info[j].iterations = h_st.iters[j];
-        info[j].ss = h_st.ss[j];
-        info[j].atb = h_st.atb[j];
-        info[j].rr = h_st.rr[j];
+        info[j].status = h.status[j];
+        info[j].iterations = h.iters[j];
+        info[j].ss = h.ss[j];
+        info[j].atb = h.atb[j];
+        info[j].rr = h.rr[j];
     }
-    if (own)
-        rc = hip_errno(hipFree(own));
-    return rc;
-fail:
-    /* nothing of ours may still run when the work buffer goes */
-    (void)hipStreamSynchronize(s);
-    if (own)
-        (void)hipFree(own);
-    (void)hipGetLastError();
-    return rc;
+    return 0;
 }

@@ -2099,6 +2099,50 @@ static int cg_axpby_of(const void *h, const spmv_launch_opts *opts, int k,
     return axpby_direct((const D *)h, opts, k, alpha, beta, X, ldx, Y, ldy, s);
 }
 
+template <typename D>
+static cg_matrix cg_matrix_of(const D *d, const spmv_launch_opts *opts) {
+    return cg_matrix{d, opts, d->M, cg_multi_of<D>, cg_axpby_of<D>};
+}
+
+/*
+ * The checks of every solver, in their order: launch_multi's of the handle and
+ * the vectors (ldb, ldx resolved), and, for a pair, of dt, the second handle of
+ * cgls; the refusals all solvers share (one handle: the matrix is square);
+ * then own(), what only this solver refuses (a negative code, or 0).  A matrix
+ * without rows (cgls: or columns) has nothing to solve: k zero-filled records.
+ * check_every 0 becomes the default.  Returns a negative code, 1 (answered:
+ * the caller returns 0) or 0 (solve).
+ */
+template <typename D, typename Info, typename Own>
+static int solver_check(const D *d, const spmv_launch_opts *opts, int k,
+                        const double *d_B, int64_t *ldb, double *d_X,
+                        int64_t *ldx, double tol, int maxit, int *check_every,
+                        Info *info, Own own, const D *dt = NULL,
+                        bool pair = false) {
+    int64_t ldb_t = *ldb, ldx_t = *ldx;
+    const int rc = multi_check(d, opts, k, d_B, ldb, d_X, ldx);
+    if (rc < 0)
+        return rc;
+    const int rct =
+        pair ? multi_check(dt, opts, k, d_B, &ldb_t, d_X, &ldx_t) : 0;
+    if (rct < 0)
+        return rct;
+    if ((!pair && d->M != d->N) || !(tol >= 0.0) || maxit < 0 ||
+        *check_every < 0 || !info)
+        return -EINVAL;
+    const int orc = own();
+    if (orc)
+        return orc;
+    if (rc || rct) {
+        for (int j = 0; j < k; ++j)
+            info[j] = Info{};
+        return 1;
+    }
+    if (!*check_every)
+        *check_every = 8;
+    return 0;
+}
+
 /* pre: spmv_*_pcg, which needs d_minv; spmv_*_cg passes NULL */
 template <typename D>
 static int cg(const D *d, const spmv_launch_opts *opts, int k,
@@ -2106,21 +2150,14 @@ static int cg(const D *d, const spmv_launch_opts *opts, int k,
               bool pre, const double *d_minv, double tol, int maxit,
               int check_every, void *d_work, size_t work_bytes,
               spmv_cg_info *info, void *stream) {
-    const int rc = multi_check(d, opts, k, d_B, &ldb, d_X, &ldx);
-    if (rc < 0)
-        return rc;
-    if (d->M != d->N || !(tol >= 0.0) || maxit < 0 || check_every < 0 ||
-        !info || (pre && !d_minv))
-        return -EINVAL;
-    if (rc) { /* no rows */
-        for (int j = 0; j < k; ++j)
-            info[j] = spmv_cg_info{0, 0, 0.0, 0.0};
-        return 0;
-    }
-    const cg_matrix A = {d, opts, d->M, cg_multi_of<D>, cg_axpby_of<D>};
+    const int rc = solver_check(
+        d, opts, k, d_B, &ldb, d_X, &ldx, tol, maxit, &check_every, info,
+        [&] { return pre && !d_minv ? -EINVAL : 0; });
+    if (rc)
+        return rc < 0 ? rc : 0;
+    const cg_matrix A = cg_matrix_of(d, opts);
     return cg_solve(&A, k, d_B, ldb, d_X, ldx, d_minv, NULL, tol, maxit,
-                    check_every ? check_every : 8, d_work, work_bytes, info,
-                    (hipStream_t)stream);
+                    check_every, d_work, work_bytes, info, (hipStream_t)stream);
 }
 
 /* spmv_*_pcg_trsv: cg's checks, then the plans'; the plans run with an opts
@@ -2132,27 +2169,23 @@ static int cg_trsv(const D *d, const spmv_launch_opts *opts, int k,
                    const double *d_scale, double tol, int maxit,
                    int check_every, void *d_work, size_t work_bytes,
                    spmv_cg_info *info, void *stream) {
-    const int rc = multi_check(d, opts, k, d_B, &ldb, d_X, &ldx);
-    if (rc < 0)
-        return rc;
-    if (d->M != d->N || !(tol >= 0.0) || maxit < 0 || check_every < 0 ||
-        !info || !first || (d_scale && !second))
-        return -EINVAL;
-    if (!live_has(first) || (second && !live_has(second)))
-        return -EBADF;
-    if (first->M != d->M || (second && second->M != d->M))
-        return -EINVAL;
-    if (rc) { /* no rows */
-        for (int j = 0; j < k; ++j)
-            info[j] = spmv_cg_info{0, 0, 0.0, 0.0};
-        return 0;
-    }
-    const cg_matrix A = {d, opts, d->M, cg_multi_of<D>, cg_axpby_of<D>};
+    const int rc = solver_check(
+        d, opts, k, d_B, &ldb, d_X, &ldx, tol, maxit, &check_every, info, [&] {
+            if (!first || (d_scale && !second))
+                return -EINVAL;
+            if (!live_has(first) || (second && !live_has(second)))
+                return -EBADF;
+            if (first->M != d->M || (second && second->M != d->M))
+                return -EINVAL;
+            return 0;
+        });
+    if (rc)
+        return rc < 0 ? rc : 0;
+    const cg_matrix A = cg_matrix_of(d, opts);
     const cg_plans pl = {first, second, d_scale,
                          opts ? opts->waves_per_block : 0};
     return cg_solve(&A, k, d_B, ldb, d_X, ldx, NULL, &pl, tol, maxit,
-                    check_every ? check_every : 8, d_work, work_bytes, info,
-                    (hipStream_t)stream);
+                    check_every, d_work, work_bytes, info, (hipStream_t)stream);
 }
 
 /* BiCGStab (bicgstab_kernels.hip): cg's checks and cg's view of the matrix;
@@ -2163,20 +2196,14 @@ static int bicgstab(const D *d, const spmv_launch_opts *opts, int k,
                     const double *d_minv, double tol, int maxit,
                     int check_every, void *d_work, size_t work_bytes,
                     spmv_cg_info *info, void *stream) {
-    const int rc = multi_check(d, opts, k, d_B, &ldb, d_X, &ldx);
-    if (rc < 0)
-        return rc;
-    if (d->M != d->N || !(tol >= 0.0) || maxit < 0 || check_every < 0 || !info)
-        return -EINVAL;
-    if (rc) { /* no rows */
-        for (int j = 0; j < k; ++j)
-            info[j] = spmv_cg_info{0, 0, 0.0, 0.0};
-        return 0;
-    }
-    const cg_matrix A = {d, opts, d->M, cg_multi_of<D>, cg_axpby_of<D>};
+    const int rc = solver_check(d, opts, k, d_B, &ldb, d_X, &ldx, tol, maxit,
+                                &check_every, info, [] { return 0; });
+    if (rc)
+        return rc < 0 ? rc : 0;
+    const cg_matrix A = cg_matrix_of(d, opts);
     return bicgstab_solve(&A, k, d_B, ldb, d_X, ldx, d_minv, tol, maxit,
-                          check_every ? check_every : 8, d_work, work_bytes,
-                          info, (hipStream_t)stream);
+                          check_every, d_work, work_bytes, info,
+                          (hipStream_t)stream);
 }
 
 /* CGLS (cgls_kernels.hip): both handles go through cg's checks, A first, with
@@ -2187,25 +2214,19 @@ static int cgls(const D *d, const D *dt, const spmv_launch_opts *opts, int k,
                 double damp, double tol, int maxit, int check_every,
                 void *d_work, size_t work_bytes, spmv_cgls_info *info,
                 void *stream) {
-    int64_t ldb_t = ldb, ldx_t = ldx;
-    const int rc = multi_check(d, opts, k, d_B, &ldb, d_X, &ldx);
-    if (rc < 0)
-        return rc;
-    const int rct = multi_check(dt, opts, k, d_B, &ldb_t, d_X, &ldx_t);
-    if (rct < 0)
-        return rct;
-    if (dt->M != d->N || dt->N != d->M || !(damp >= 0.0) || !(tol >= 0.0) ||
-        maxit < 0 || check_every < 0 || !info)
-        return -EINVAL;
-    if (rc || rct) { /* no rows or no columns */
-        for (int j = 0; j < k; ++j)
-            info[j] = spmv_cgls_info{0, 0, 0.0, 0.0, 0.0};
-        return 0;
-    }
-    const cg_matrix A = {d, opts, d->M, cg_multi_of<D>, cg_axpby_of<D>};
-    const cg_matrix AT = {dt, opts, dt->M, cg_multi_of<D>, cg_axpby_of<D>};
+    const int rc = solver_check(
+        d, opts, k, d_B, &ldb, d_X, &ldx, tol, maxit, &check_every, info,
+        [&] {
+            return dt->M != d->N || dt->N != d->M || !(damp >= 0.0) ? -EINVAL
+                                                                    : 0;
+        },
+        dt, true);
+    if (rc)
+        return rc < 0 ? rc : 0;
+    const cg_matrix A = cg_matrix_of(d, opts);
+    const cg_matrix AT = cg_matrix_of(dt, opts);
     return cgls_solve(&A, &AT, k, d_B, ldb, d_X, ldx, damp, tol, maxit,
-                      check_every ? check_every : 8, d_work, work_bytes, info,
+                      check_every, d_work, work_bytes, info,
                       (hipStream_t)stream);
 }
 
@@ -2217,20 +2238,14 @@ static int minres(const D *d, const spmv_launch_opts *opts, int k,
                   const double *d_minv, double tol, int maxit, int check_every,
                   void *d_work, size_t work_bytes, spmv_minres_info *info,
                   void *stream) {
-    const int rc = multi_check(d, opts, k, d_B, &ldb, d_X, &ldx);
-    if (rc < 0)
-        return rc;
-    if (d->M != d->N || !(tol >= 0.0) || maxit < 0 || check_every < 0 || !info)
-        return -EINVAL;
-    if (rc) { /* no rows */
-        for (int j = 0; j < k; ++j)
-            info[j] = spmv_minres_info{0, 0, 0.0, 0.0, 0.0, 0.0};
-        return 0;
-    }
-    const cg_matrix A = {d, opts, d->M, cg_multi_of<D>, cg_axpby_of<D>};
+    const int rc = solver_check(d, opts, k, d_B, &ldb, d_X, &ldx, tol, maxit,
+                                &check_every, info, [] { return 0; });
+    if (rc)
+        return rc < 0 ? rc : 0;
+    const cg_matrix A = cg_matrix_of(d, opts);
     return minres_solve(&A, k, d_B, ldb, d_X, ldx, d_minv, tol, maxit,
-                        check_every ? check_every : 8, d_work, work_bytes,
-                        info, (hipStream_t)stream);
+                        check_every, d_work, work_bytes, info,
+                        (hipStream_t)stream);
 }
 
 /* ---- the diagonal (diag_kernels.hip): launch_multi's handle checks ---- */

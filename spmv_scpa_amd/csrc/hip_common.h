@@ -15,6 +15,7 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "solver_work.h"
 #include "spmv_engine.h"
 
 #define WAVE 64 /* gfx950 wavefront */
@@ -508,11 +509,10 @@ int hll_launch_axpby(const spmv_hll_dev *H, int waves, int k, double alpha,
  * product -- CG_NWG workgroups of CG_T threads, element i in slot
  * i mod (CG_NWG * CG_T) -- is part of the result contract
  * (spmv_cg_dot_shape): the order of a dot depends on M and on nothing else.
+ * CG_NWG, the sizes of the state blocks and of a set of partial sums, and the
+ * work buffer of every solver are in solver_work.h (free of HIP).
  */
-#define CG_NWG 1024
 #define CG_T 256
-#define CG_STATE_BYTES 512                /* per-column state, cg_kernels.hip */
-#define CG_PART_BYTES (CG_NWG * 8 * 8)    /* CG_NWG workgroup sums of 8 columns */
 /* spmv_cg_info.status, and the one value only the device sees */
 #define CG_CONVERGED 0
 #define CG_MAXIT 1

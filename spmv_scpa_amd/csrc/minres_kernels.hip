@@ -12,7 +12,9 @@
  * cg_kernels.hip through cg_launch_dot / cg_launch_copy.  Here: the Lanczos
  * recurrence and the Givens rotations of Paige and Saunders as four vector
  * kernels and four finalising kernels, the per-column state, the device
- * square root and the bounded host loop.
+ * square root and the launches of a solve in their order; the refusals, the
+ * own work buffer and the bounded host loop are solver_run (solver_host.h), the
+ * buffer is minres_work (solver_work.h).
  *
  * ONE ITERATION i = 1, 2, ..., in launch order:
  *   k_mr_v             V = s z(R2), s = 1 / beta                    (2 + d)
@@ -48,10 +50,8 @@
  */
 #include "cg_common.h"
 
-#define MR_STATE_BYTES 2048
-
-/* per-column state, device memory (MR_STATE_BYTES at the head of the work
- * buffer) */
+/* per-column state, device memory (MR_STATE_BYTES, solver_work.h, at the head
+ * of the work buffer) */
 struct mr_state {
     double bb[CG_MAXK];     /* b.b */
     double bn2[CG_MAXK];    /* b.z(b) */
@@ -473,27 +473,8 @@ k_mr_debug_sqrt(int64_t n, const double *__restrict__ in,
 /* host                                                                 */
 /* ------------------------------------------------------------------ */
 
-/* kernel<k, flag>(M, ...) over the slots of M rows on stream s */
-#define MR_LAUNCH_K(KK, kernel, flag, M, s, ...)                              \
-    do {                                                                      \
-        if (flag)                                                             \
-            hipLaunchKernelGGL((kernel<KK, true>), dim3(cg_grid(M)),          \
-                               dim3(CG_T), 0, s, M, __VA_ARGS__);             \
-        else                                                                  \
-            hipLaunchKernelGGL((kernel<KK, false>), dim3(cg_grid(M)),         \
-                               dim3(CG_T), 0, s, M, __VA_ARGS__);             \
-    } while (0)
-#define MR_LAUNCH(kernel, flag, k, M, s, ...)                                 \
-    CG_K_SWITCH(k, MR_LAUNCH_K, kernel, flag, M, s, __VA_ARGS__)
-
-#define MR_PARTS 3   /* sets of partial sums: (bb | alfa | rr), (bn2 | bnew), b1 */
-#define MR_VECTORS 6 /* two residuals, V, Q, two directions */
-
 int64_t minres_work_bytes(int M, int k) {
-    if (M < 0 || k < 1 || k > CG_MAXK)
-        return -EINVAL;
-    return MR_STATE_BYTES + MR_PARTS * CG_PART_BYTES +
-           MR_VECTORS * 8 * (int64_t)M * k;
+    return solver_work_bytes(minres_work(M, k));
 }
 
 int minres_debug_sqrt(const double *d_in, double *d_out, int64_t n,
@@ -517,123 +498,88 @@ int minres_solve(const cg_matrix *A, int k, const double *B, int64_t ldb,
                  spmv_minres_info *info, hipStream_t s) {
     const int M = A->M;
     const bool pre = minv != NULL;
-    const size_t need = (size_t)minres_work_bytes(M, k);
-    if (d_work && (work_bytes < need || ((uintptr_t)d_work & 7)))
-        return -EINVAL;
-    /* a capturing stream cannot be synchronised: refuse before anything is
-     * allocated or enqueued, so the capture stays valid */
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const hipError_t ce = hipStreamIsCapturing(s, &cap);
-    if (ce != hipSuccess) {
-        (void)hipGetLastError();
-        return ce == hipErrorStreamCaptureImplicit ? -EBUSY : hip_errno(ce);
-    }
-    if (cap != hipStreamCaptureStatusNone)
-        return -EBUSY;
-
-    int rc = 0;
-    void *own = NULL;
-    mr_state h_st;
-    int h_status[CG_MAXK];
-    (void)hipGetLastError(); /* an earlier caller's unread error is not ours */
-    if (!d_work) {
-        HIP_TRY(hipMalloc(&own, need));
-        d_work = own;
-    }
-    {
-        mr_state *st = (mr_state *)d_work;
-        double *part0 = (double *)((char *)d_work + MR_STATE_BYTES);
-        double *part1 = part0 + CG_PART_BYTES / 8;
-        double *part2 = part1 + CG_PART_BYTES / 8;
-        const size_t vec = (size_t)M * k;
-        /* iteration i: R2 = Rb[(i - 1) & 1], R1 and then Rn = Rb[i & 1]; the
-         * same with W2, W1 and Wn in Wb */
-        double *Rb[2], *Wb[2];
-        Rb[0] = part2 + CG_PART_BYTES / 8;
-        Rb[1] = Rb[0] + vec;
-        double *V = Rb[1] + vec;
-        double *Q = V + vec;
-        Wb[0] = Q + vec;
-        Wb[1] = Wb[0] + vec;
-        const int nwg = (int)cg_grid(M);
-        const double tol2 = tol * tol;
-
+    const solver_work w = minres_work(M, k);
+    const int nwg = (int)cg_grid(M);
+    const double tol2 = tol * tol;
+    mr_state *st = NULL;
+    double *part0 = NULL, *part1 = NULL, *part2 = NULL;
+    /* iteration i: R2 = Rb[(i - 1) & 1], R1 and then Rn = Rb[i & 1]; the same
+     * with W2, W1 and Wn in Wb */
+    double *Rb[2] = {NULL, NULL}, *Wb[2] = {NULL, NULL};
+    double *V = NULL, *Q = NULL;
+    mr_state h;
+    const int rc = solver_run(
+        w, maxit, check_every, d_work, work_bytes, &h, s,
         /* R2 = B - A X; W1 = W2 = +0.0; bb, bn2, b1, the first classification
          * (without minv bn2 is bb, sum for sum) */
-        cg_launch_copy(k, M, B, ldb, Rb[0], k, s);
-        rc = A->axpby(A->handle, A->opts, k, -1.0, 1.0, X, ldx, Rb[0], k, s);
-        if (rc)
-            goto fail;
-        HIP_TRY(hipMemsetAsync(Wb[0], 0, 2 * vec * 8, s));
-        cg_launch_dot(k, M, B, ldb, B, ldb, part0, s);
-        if (pre) {
-            CG_LAUNCH(k_mr_dotz, k, M, s, minv, B, ldb, part1);
-            CG_LAUNCH(k_mr_dotz, k, M, s, minv, Rb[0], (int64_t)k, part2);
-        } else {
-            cg_launch_dot(k, M, Rb[0], k, Rb[0], k, part2, s);
-        }
-        CG_FINAL(k_mr_final_init, s, k, nwg, part0, pre ? part1 : part0, part2,
-                 tol2, st);
-        HIP_TRY(hipGetLastError());
-
-        for (int done = 0;;) {
-            HIP_TRY(hipMemcpyAsync(h_status, st->status, k * sizeof(int),
-                                   hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            bool running = false;
-            for (int j = 0; j < k; ++j)
-                running = running || h_status[j] == CG_RUNNING;
-            if (!running || done >= maxit)
-                break;
-            const int batch = maxit - done < check_every ? maxit - done
-                                                         : check_every;
-            for (int it = 0; it < batch; ++it) {
-                const int i = done + it + 1;
-                const double *R2 = Rb[(i - 1) & 1];
-                double *R1 = Rb[i & 1];
-                MR_LAUNCH(k_mr_v, pre, k, M, s, st, minv, R2, V);
-                rc = A->multi(A->handle, A->opts, k, V, k, Q, k, s);
-                if (rc)
-                    goto fail;
-                MR_LAUNCH(k_mr_orth, i == 1, k, M, s, st, V, R1, Q, part0);
-                CG_FINAL(k_mr_final_alfa, s, k, nwg, part0, st);
-                MR_LAUNCH(k_mr_res, pre, k, M, s, st, minv, Q, R2, R1, part1);
-                CG_FINAL(k_mr_final_givens, s, k, nwg, part1, tol2, st);
-                CG_LAUNCH(k_mr_step, k, M, s, st, V, Wb[i & 1],
-                          Wb[(i - 1) & 1], X, ldx);
+        [&](void *work) {
+            st = (mr_state *)work;
+            part0 = solver_part(work, w, 0);
+            part1 = solver_part(work, w, 1);
+            part2 = solver_part(work, w, 2);
+            Rb[0] = solver_vec(work, w, 0);
+            Rb[1] = solver_vec(work, w, 1);
+            V = solver_vec(work, w, 2);
+            Q = solver_vec(work, w, 3);
+            Wb[0] = solver_vec(work, w, 4);
+            Wb[1] = solver_vec(work, w, 5);
+            cg_launch_copy(k, M, B, ldb, Rb[0], k, s);
+            const int rc = A->axpby(A->handle, A->opts, k, -1.0, 1.0, X, ldx,
+                                    Rb[0], k, s);
+            if (rc)
+                return rc;
+            /* both directions: neighbours, the last two vectors */
+            const hipError_t e = hipMemsetAsync(
+                Wb[0], 0,
+                (size_t)(solver_work_vec(w, 6) - solver_work_vec(w, 4)), s);
+            if (e != hipSuccess)
+                return hip_errno(e);
+            cg_launch_dot(k, M, B, ldb, B, ldb, part0, s);
+            if (pre) {
+                CG_LAUNCH(k_mr_dotz, k, M, s, minv, B, ldb, part1);
+                CG_LAUNCH(k_mr_dotz, k, M, s, minv, Rb[0], (int64_t)k, part2);
+            } else {
+                cg_launch_dot(k, M, Rb[0], k, Rb[0], k, part2, s);
             }
-            HIP_TRY(hipGetLastError());
-            done += batch;
-        }
+            CG_FINAL(k_mr_final_init, s, k, nwg, part0, pre ? part1 : part0,
+                     part2, tol2, st);
+            return 0;
+        },
+        [&](int i) {
+            const double *R2 = Rb[(i - 1) & 1];
+            double *R1 = Rb[i & 1];
+            CG_LAUNCH_FLAG(k_mr_v, pre, k, M, s, st, minv, R2, V);
+            const int rc = A->multi(A->handle, A->opts, k, V, k, Q, k, s);
+            if (rc)
+                return rc;
+            CG_LAUNCH_FLAG(k_mr_orth, i == 1, k, M, s, st, V, R1, Q, part0);
+            CG_FINAL(k_mr_final_alfa, s, k, nwg, part0, st);
+            CG_LAUNCH_FLAG(k_mr_res, pre, k, M, s, st, minv, Q, R2, R1, part1);
+            CG_FINAL(k_mr_final_givens, s, k, nwg, part1, tol2, st);
+            CG_LAUNCH(k_mr_step, k, M, s, st, V, Wb[i & 1], Wb[(i - 1) & 1], X,
+                      ldx);
+            return 0;
+        },
         /* the true residual, once: R = B - A X in a buffer no one needs now */
-        cg_launch_copy(k, M, B, ldb, Q, k, s);
-        rc = A->axpby(A->handle, A->opts, k, -1.0, 1.0, X, ldx, Q, k, s);
-        if (rc)
-            goto fail;
-        cg_launch_dot(k, M, Q, k, Q, k, part0, s);
-        CG_FINAL(k_mr_final_rr, s, k, nwg, part0, st);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&h_st, st, sizeof h_st, hipMemcpyDeviceToHost,
-                               s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
+        [&] {
+            cg_launch_copy(k, M, B, ldb, Q, k, s);
+            const int rc =
+                A->axpby(A->handle, A->opts, k, -1.0, 1.0, X, ldx, Q, k, s);
+            if (rc)
+                return rc;
+            cg_launch_dot(k, M, Q, k, Q, k, part0, s);
+            CG_FINAL(k_mr_final_rr, s, k, nwg, part0, st);
+            return hip_errno(hipGetLastError());
+        });
+    if (rc)
+        return rc;
     for (int j = 0; j < k; ++j) {
-        info[j].status =
-            h_st.status[j] == CG_RUNNING ? CG_MAXIT : h_st.status[j];
-        info[j].iterations = h_st.iters[j];
-        info[j].pp = h_st.pp[j];
-        info[j].bn2 = h_st.bn2[j];
-        info[j].rr = h_st.rr[j];
-        info[j].bb = h_st.bb[j];
+        info[j].status = h.status[j];
+        info[j].iterations = h.iters[j];
+        info[j].pp = h.pp[j];
+        info[j].bn2 = h.bn2[j];
+        info[j].rr = h.rr[j];
+        info[j].bb = h.bb[j];
     }
-    if (own)
-        rc = hip_errno(hipFree(own));
-    return rc;
-fail:
-    /* nothing of ours may still run when the work buffer goes */
-    (void)hipStreamSynchronize(s);
-    if (own)
-        (void)hipFree(own);
-    (void)hipGetLastError();
-    return rc;
+    return 0;
 }
