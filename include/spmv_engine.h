@@ -459,6 +459,122 @@ typedef struct spmv_ic0_info {
 } spmv_ic0_info;
 int spmv_csr_ic0(const spmv_csr_dev *A, double shift, int max_levels,
                  spmv_csr_dev **out, spmv_ic0_info *info /* may be NULL */);
+/*
+ * A multicolour ordering on the device (added after 0.7; detect it by the
+ * symbols): a plan has one level per colour at most once the rows of a colour
+ * are numbered together, so the launches of a triangular solve fall from the
+ * depth of the natural order to a handful.  Three calls: spmv_csr_colour finds
+ * the ordering, spmv_csr_permute applies it to a handle, spmv_permute_vectors
+ * carries B and X between the two numberings.
+ *
+ * spmv_csr_colour: a distance-1 colouring of a square CSR handle (f64 or f32
+ * values; only the pattern is read; rows may be unsorted and hold duplicates
+ * and explicit zeros).  d_colour, d_new_of_old: M ints on the device each,
+ * either may be NULL; info may be NULL.  max_rounds: 0 = the default, 4096.
+ *
+ * THE RESULT IS A FUNCTION OF THE PATTERN AND `seed` ALONE, defined to the
+ * byte:
+ *   graph     i ~ j iff i != j and (i, j) or (j, i) is stored.  An explicit
+ *       zero is an edge, the diagonal is none, a duplicate is one edge.  A
+ *       pattern that is not symmetric is not an error: adjacency is read from
+ *       A and from A^T
+ *   priority  h(i) = fmix32((uint32_t)i ^ seed), the finaliser of murmur3:
+ *       h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35;
+ *       h ^= h >> 16, in 32 bits.  A bijection: priorities are distinct, there
+ *       is no tie rule.  (The row index as the priority would make the rounds
+ *       the levels of the natural order.)
+ *   colour[i] the smallest integer >= 0 that is not the colour of a neighbour
+ *       j with h(j) > h(i): first-fit in decreasing priority
+ *   round[i]  1 when no neighbour has a higher priority, else 1 + the largest
+ *       round of those that have; info->rounds = the largest round
+ *   new_of_old  the inverse of the stable sort of 0 .. M-1 by colour (rows
+ *       ascending inside a colour).  In B = P A P^T a row of colour c has its
+ *       strict lower entries in colours < c only, so both triangular plans of
+ *       B have at most info->colours levels
+ *   info      colours, rounds, widest / narrowest = the rows of the largest /
+ *       smallest colour
+ * The device runs Jones-Plassmann, one launch and one 4-byte read-back per
+ * round, as Kahn's algorithm in spmv_csr_trsv_analyse: round r colours exactly
+ * the rows with round[i] == r.  A round reads the colours earlier launches
+ * wrote from one array and writes another, so a lane never reads a word that a
+ * lane of its own launch writes, and info->rounds and the launch sequence are
+ * reproducible.  One lane per row; the smallest free colour is found with one
+ * walk of the row per window of 64 colours (a 64-bit mask), at most
+ * ceil((deg + 1) / 64) of them.  Every device loop is bounded by a row length
+ * or that count; no waiting between workgroups of any kind.  The order is the
+ * radix sort of spmv_csr_transpose; no position comes from an atomic.
+ *
+ * Errors, in this order: NULL A or max_rounds < 0 -EINVAL; no device -ENODEV;
+ * a dead handle -EBADF; M != N -EINVAL; after spmv_csr_release_source
+ * -ENODATA; a column outside [0, N) -EDOM; more than max_rounds rounds -E2BIG
+ * (a clique of n rows needs n rounds and n colours: a colouring is not for
+ * that); a failed allocation -ENOMEM.  On any error the two arrays are not
+ * written, *info is not written, all scratch is freed and
+ * spmv_live_handles() is unchanged.  M == 0 gives 0 colours and 0 rounds.  The
+ * call blocks.  Peak device memory, freed before the call returns: the pattern
+ * of A^T (4 (M + 1) + 8 NZ bytes; built by the transposition of
+ * spmv_csr_transpose, with its scratch of spmv_transpose_plan(M, NZ) while it
+ * runs), two colour arrays and three more of M ints.
+ *
+ * spmv_csr_permute: *out = B = P A Q^T, a NEW, ordinary M x N handle of A's
+ * value type that owns its arrays; A may be rectangular and is unchanged.
+ * d_row_new_of_old: M ints on the device, p[r] = the new number of row r;
+ * d_col_new_of_old: N ints, q[c] likewise; NULL = the identity.  The symmetric
+ * permutation passes one array twice.
+ *
+ * THE RESULT IS DEFINED TO THE BYTE: row p[r] of B holds the entries of row r
+ * of A with column c written as q[c], STABLY SORTED BY NEW COLUMN -- what two
+ * stable sorts of A's entries in stored order give, first by q[c], then by
+ * p[r].  Duplicates keep their source order and are not summed; explicit zeros
+ * stay; values are moved with their bits (NaN payloads, -0.0, subnormals).  A
+ * source without duplicates gives strictly ascending rows, which is what
+ * spmv_csr_ic0 demands.  With both arrays NULL, B is (A^T)^T.  It is computed
+ * as two transpositions with a relabelling before each; no position comes from
+ * an atomic.  Every kernel id, launch_multi, spmv_hll_from_csr,
+ * spmv_csr_to_f32, transpose, trsv_analyse, ic0, the solvers, download and
+ * release work on B as on any handle.
+ *
+ * Errors: those of spmv_csr_transpose up to -ENODATA, in its order; then,
+ * before anything is allocated for the result, a device check of each array,
+ * rows first (the inverse is scattered and compared back): an entry outside
+ * its range -EDOM, a repeated entry -EINVAL; then a column of A outside [0, N)
+ * -EDOM; a failed allocation -ENOMEM.  On any error nothing is created and
+ * *out is NULL.  M, N or NZ may be 0.  The call blocks.  Peak device memory
+ * besides A and B, freed before the call returns: the intermediate N x M
+ * matrix (4 (N + 1) + (4 + value bytes) NZ), 4 NZ for the relabelled columns
+ * and the scratch of spmv_transpose_plan.
+ *
+ * spmv_permute_vectors: k = 1..8 interleaved vectors in the layout of
+ * spmv_*_launch_multi (ldin, ldout >= k; 0 = k; only columns 0..k-1 of rows
+ * 0..M-1 are touched).  inverse == 0: out[p[r], j] = in[r, j] (into the new
+ * numbering); otherwise out[r, j] = in[p[r], j] (back).  The bits are moved.
+ * Asynchronous on `stream` and capturable.  -EINVAL: k outside 1..8, M < 0, a
+ * leading dimension below k, a NULL pointer, d_in == d_out; -ENODEV without a
+ * GPU.  The array is TRUSTED (spmv_csr_permute is where a permutation is
+ * checked); any other overlap of in and out is undefined.  The lanes cover
+ * the k doubles of consecutive rows contiguously, so the side that is not
+ * gathered moves whole cache lines.
+ *
+ * Not in scope: HLL and compact (16-bit) handles as input, distance-2
+ * colouring, balancing the sizes of the colours, RCM or any bandwidth
+ * ordering, plans inside minres / bicgstab, ILU(0), and fusing a plan's solve
+ * with its neighbours in the iteration.
+ */
+typedef struct spmv_colour_info {
+    int colours, rounds;   /* rounds = kernel rounds = longest priority chain */
+    int widest, narrowest; /* rows of the largest / smallest colour */
+} spmv_colour_info;
+int spmv_csr_colour(const spmv_csr_dev *A, uint32_t seed, int max_rounds,
+                    int *d_colour /* M ints or NULL */,
+                    int *d_new_of_old /* M ints or NULL */,
+                    spmv_colour_info *info /* or NULL */);
+int spmv_csr_permute(const spmv_csr_dev *A,
+                     const int *d_row_new_of_old /* M or NULL */,
+                     const int *d_col_new_of_old /* N or NULL */,
+                     spmv_csr_dev **out);
+int spmv_permute_vectors(const int *d_new_of_old, int M, int k, int inverse,
+                         const double *d_in, int64_t ldin, double *d_out,
+                         int64_t ldout, void *stream);
 /* Build a synthetic matrix (spmv_synth.h) directly in device memory. */
 int spmv_csr_generate(int kind, int M, int N, int K, int64_t W, int64_t row0,
                       uint64_t seed, spmv_csr_dev **out);
@@ -939,7 +1055,8 @@ int spmv_hll_pcg(const spmv_hll_dev *H, const spmv_launch_opts *opts, int k,
  * The price: every iteration adds the launches of the plans (spmv_trsv_info),
  * 3.4-4.4 us each.  On a stencil in natural order that is far more than the
  * iteration of spmv_*_pcg it replaces; it pays where the level count is small
- * (a multicolour ordering) or the iteration count falls by more than the
+ * (a multicolour ordering: spmv_csr_colour and spmv_csr_permute above make
+ * one) or the iteration count falls by more than the
  * launches cost (profiles/ic0.md).
  */
 int64_t spmv_pcg_trsv_work_bytes(int M, int k); /* as spmv_pcg_work_bytes */

@@ -424,6 +424,12 @@ class Ic0Info(C.Structure):
                 ("entries", C.c_int64), ("bad_pivots", C.c_int64)]
 
 
+class ColourInfo(C.Structure):
+    """spmv_colour_info (include/spmv_engine.h): one CsrDevice.colour()"""
+    _fields_ = [("colours", C.c_int), ("rounds", C.c_int),
+                ("widest", C.c_int), ("narrowest", C.c_int)]
+
+
 _CSRp = C.POINTER(SparseCSR)
 _HLLp = C.POINTER(SparseHLL)
 
@@ -568,6 +574,12 @@ _sig("spmv_trsv_solve", C.c_int, C.c_void_p, C.POINTER(LaunchOpts), C.c_int,
      C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
 _sig("spmv_csr_ic0", C.c_int, C.c_void_p, C.c_double, C.c_int,
      C.POINTER(C.c_void_p), C.POINTER(Ic0Info))
+_sig("spmv_csr_colour", C.c_int, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p,
+     C.c_void_p, C.POINTER(ColourInfo))
+_sig("spmv_csr_permute", C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.POINTER(C.c_void_p))
+_sig("spmv_permute_vectors", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+     C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p)
 _sig("spmv_csr_generate", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
      C.c_int64, C.c_int64, C.c_uint64, C.POINTER(C.c_void_p))
 _sig("spmv_csr_launch_rows", C.c_int, C.c_void_p, C.c_int,
@@ -1876,6 +1888,35 @@ class CsrDevice(_Device):
                                  C.byref(info)), "spmv_csr_ic0")
         return CsrDevice(h), info
 
+    def colour(self, seed=0, max_rounds=0):
+        """a Colouring of this (square) handle: the deterministic first-fit
+        colouring by the priority fmix32(row ^ seed) and the ordering that
+        numbers the rows colour by colour, found on the device and defined to
+        the byte (spmv_engine.h).  Only the pattern is read, through A and
+        A^T.  More than max_rounds rounds (0: 4096) is OSError(E2BIG).
+        permute(col, col) then has plans of at most col.colours levels"""
+        seed, max_rounds = int(seed), int(max_rounds)
+        if not 0 <= seed < 1 << 32:
+            raise ValueError("seed=%d: a 32-bit unsigned number" % seed)
+        if max_rounds < 0:
+            raise ValueError("max_rounds=%d: 0 (the default) or more"
+                             % max_rounds)
+        return Colouring(self, seed, max_rounds)
+
+    def permute(self, rows=None, cols=None):
+        """a new CsrDevice B = P A Q^T: row r becomes row rows[r], column c
+        becomes cols[c], every row stably sorted by new column, values moved
+        with their bits (spmv_engine.h).  rows / cols: a DevBuffer of int32
+        (M / N of them), a raw device pointer, a Colouring (its .perm) or
+        None for the identity.  An array that is no permutation is
+        OSError(EDOM) (an entry out of range) or OSError(EINVAL) (a repeated
+        entry).  This handle stays valid"""
+        h = C.c_void_p()
+        _check(_lib.spmv_csr_permute(self.h, _perm_ptr(rows, "rows"),
+                                     _perm_ptr(cols, "cols"), C.byref(h)),
+               "spmv_csr_permute")
+        return CsrDevice(h)
+
     def sgs(self, max_levels=0):
         """an SgsPreconditioner of this (square) handle: its lower and upper
         TrsvPlan and a DevBuffer with diag(A); release() frees the three"""
@@ -2002,6 +2043,92 @@ class TrsvPlan:
     def __del__(self):
         if _closed is False:  # None / True at or after interpreter shutdown
             self.release()
+
+
+class Colouring:
+    """The result of CsrDevice.colour(): `colour` and `perm` (DevBuffer, M
+    int32 each: the colour of every row, and new_of_old -- the new number of
+    every row once the rows are ordered colour by colour), `colours`,
+    `rounds`, `widest`, `narrowest` (spmv_engine.h, spmv_colour_info) and `M`.
+    permute() and permute_vectors() take it where they take a permutation."""
+
+    colour = perm = None
+    _RANK = 1
+
+    def __init__(self, A, seed, max_rounds):
+        self.M = A.M
+        info = ColourInfo()
+        try:
+            self.colour = DevBuffer(max(A.M, 1) * 4)
+            self.perm = DevBuffer(max(A.M, 1) * 4)
+            _check(_lib.spmv_csr_colour(A.h, seed, max_rounds,
+                                        self.colour.ptr, self.perm.ptr,
+                                        C.byref(info)), "spmv_csr_colour")
+        except BaseException:
+            self.release()
+            raise
+        self.colours, self.rounds = info.colours, info.rounds
+        self.widest, self.narrowest = info.widest, info.narrowest
+        _live.add(self)
+
+    def _released(self):
+        return self.perm is None
+
+    def _release_now(self):
+        self.release()
+
+    def release(self):
+        for buf in (self.colour, self.perm):
+            if buf is not None:
+                buf.free()
+        self.colour = self.perm = None
+
+
+def _perm_ptr(p, what):
+    """the device pointer of a permutation argument: a Colouring (its .perm),
+    a DevBuffer, a raw pointer, or None"""
+    if isinstance(p, Colouring):
+        p = p.perm
+        if p is None:
+            raise ValueError("%s: a released Colouring" % what)
+    if isinstance(p, DevBuffer):
+        if not p.ptr:
+            raise ValueError("%s: a freed DevBuffer" % what)
+        return p.ptr
+    if p is None or isinstance(p, int):
+        return p
+    raise ValueError("%s=%r: a DevBuffer, a device pointer, a Colouring or "
+                     "None" % (what, p))
+
+
+def permute_vectors(perm, d_in, d_out, M, k=1, inverse=False, ldin=0, ldout=0,
+                    stream=None):
+    """k = 1..8 interleaved vectors between two numberings of the rows
+    (spmv_permute_vectors): out[perm[r], j] = in[r, j], or with inverse=True
+    out[r, j] = in[perm[r], j]; the bits are moved.  perm: M int32 on the
+    device (a DevBuffer, a pointer or a Colouring); it is trusted.  d_in,
+    d_out: device pointers or DevBuffers, not the same one.  Asynchronous on
+    `stream`"""
+    M, k, ldin, ldout = int(M), int(k), int(ldin), int(ldout)
+    if not 1 <= k <= 8:
+        raise ValueError("k=%r: 1..8 vectors per call" % (k,))
+    if M < 0:
+        raise ValueError("M=%d: 0 or more rows" % M)
+    if (ldin and ldin < k) or (ldout and ldout < k):
+        raise ValueError("ldin=%d, ldout=%d: at least k=%d (or 0)"
+                         % (ldin, ldout, k))
+    p = _perm_ptr(perm, "perm")
+    if isinstance(d_in, DevBuffer):
+        d_in = d_in.ptr
+    if isinstance(d_out, DevBuffer):
+        d_out = d_out.ptr
+    if not p or not d_in or not d_out:
+        raise ValueError("perm, d_in and d_out: device pointers, not None")
+    if d_in == d_out:
+        raise ValueError("d_in is d_out: the permutation is not in place")
+    _check(_lib.spmv_permute_vectors(p, M, k, int(bool(inverse)), d_in, ldin,
+                                     d_out, ldout, stream),
+           "spmv_permute_vectors")
 
 
 class SgsPreconditioner:

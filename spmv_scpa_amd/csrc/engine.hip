@@ -1122,6 +1122,73 @@ int spmv_csr_symmetry(const spmv_csr_dev *A, int *out) {
 }
 
 /* ------------------------------------------------------------------ */
+/* colouring and permutation (colour_kernels.hip)                       */
+/* ------------------------------------------------------------------ */
+
+#define COLOUR_DEFAULT_MAX_ROUNDS 4096
+
+int spmv_csr_colour(const spmv_csr_dev *A, uint32_t seed, int max_rounds,
+                    int *d_colour, int *d_new_of_old, spmv_colour_info *info) {
+    if (!A || max_rounds < 0)
+        return -EINVAL;
+    if (spmv_device_count() == 0)
+        return -ENODEV; /* no handle can be live: the more useful answer */
+    HANDLE_OK(A);
+    if (A->M != A->N)
+        return -EINVAL;
+    if (!A->ja && A->NZ > 0)
+        return -ENODATA; /* spmv_csr_release_source() */
+    return csr_colour_dev(A, seed,
+                          max_rounds ? max_rounds : COLOUR_DEFAULT_MAX_ROUNDS,
+                          d_colour, d_new_of_old, info, 0);
+}
+
+/* a new M x N handle B = P A Q^T: two relabelled transpositions */
+int spmv_csr_permute(const spmv_csr_dev *A, const int *d_row_new_of_old,
+                     const int *d_col_new_of_old, spmv_csr_dev **out) {
+    if (!A || !out)
+        return -EINVAL;
+    *out = NULL;
+    if (spmv_device_count() == 0)
+        return -ENODEV; /* no handle can be live: the more useful answer */
+    HANDLE_OK(A);
+    if (!A->ja && A->NZ > 0)
+        return -ENODATA; /* spmv_csr_release_source() */
+    spmv_csr_dev *d = NULL;
+    int rc = csr_permute_dev(A, d_row_new_of_old, d_col_new_of_old,
+                             csr_alloc_dev, &d, 0);
+    if (rc)
+        return rc;
+    rc = finish_csr_handle(d, NULL);
+    if (rc) {
+        spmv_csr_release(d);
+        return rc;
+    }
+    *out = d;
+    return 0;
+}
+
+int spmv_permute_vectors(const int *d_new_of_old, int M, int k, int inverse,
+                         const double *d_in, int64_t ldin, double *d_out,
+                         int64_t ldout, void *stream) {
+    if (k < 1 || k > 8 || M < 0)
+        return -EINVAL;
+    if (ldin == 0)
+        ldin = k;
+    if (ldout == 0)
+        ldout = k;
+    if (ldin < k || ldout < k || !d_in || !d_out || d_in == d_out ||
+        !d_new_of_old)
+        return -EINVAL;
+    if (spmv_device_count() == 0)
+        return -ENODEV;
+    if (M == 0)
+        return 0;
+    return permute_vectors_dev(d_new_of_old, M, k, inverse != 0, d_in, ldin,
+                               d_out, ldout, (hipStream_t)stream);
+}
+
+/* ------------------------------------------------------------------ */
 /* triangular solve (trsv_kernels.hip, trsv_plan.h)                     */
 /* ------------------------------------------------------------------ */
 

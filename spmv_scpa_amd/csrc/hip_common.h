@@ -659,6 +659,23 @@ int ic0_factor_dev(const spmv_csr_dev *A, double shift, int max_levels,
                    int waves, ic0_alloc_fn alloc, spmv_csr_dev **out,
                    spmv_ic0_info *info, hipStream_t s);
 
+/*
+ * Colouring and permutation (colour_kernels.hip; spmv_csr_colour,
+ * spmv_csr_permute, spmv_permute_vectors).  The caller has checked the handle
+ * (with its source; square for the colouring) and the arguments.  Both block,
+ * free their scratch on every path and leave the caller's arrays / *out
+ * untouched on an error.  csr_permute_dev takes *out from `alloc` once p and q
+ * passed their checks; the caller finishes it as spmv_csr_transpose does.
+ */
+int csr_colour_dev(const spmv_csr_dev *A, uint32_t seed, int max_rounds,
+                   int *d_colour, int *d_new_of_old, spmv_colour_info *info,
+                   hipStream_t s);
+int csr_permute_dev(const spmv_csr_dev *A, const int *p, const int *q,
+                    ic0_alloc_fn alloc, spmv_csr_dev **out, hipStream_t s);
+int permute_vectors_dev(const int *p, int M, int k, int inverse,
+                        const double *in, int64_t ldin, double *out,
+                        int64_t ldout, hipStream_t s);
+
 /* kernel launchers (csr_kernels.hip / hll_kernels.hip) */
 int csr_launch_kernel(const spmv_csr_dev *A, int kernel, int waves, int group,
                       int variant, const double *x, double *y, int r0, int r1,
