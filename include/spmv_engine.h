@@ -381,11 +381,12 @@ int spmv_csr_symmetry(const spmv_csr_dev *A, int *out);
  * the solve: the kernel boundary on the stream is the only cross-workgroup
  * ordering.
  *
- * Plans are the preconditioner of spmv_*_pcg_trsv, and spmv_csr_ic0 makes the
- * factor to build them from (both below).  Not in scope: HLL handles, compact
- * (16-bit) handles, the blocked path, a plan as the preconditioner of minres /
- * bicgstab, ILU(0) factors, and any treatment of deep chains beyond the -E2BIG
- * cap.
+ * Plans are the preconditioner of spmv_*_pcg_trsv and spmv_*_bicgstab_trsv,
+ * and spmv_csr_ic0 / spmv_csr_ilu0 make the factors to build them from (all
+ * below).  Not in scope: HLL handles, compact (16-bit) handles, the blocked
+ * path, a plan as the preconditioner of minres, f32 or HLL input to the
+ * factorisations, ILU with fill or a threshold, and any treatment of deep
+ * chains beyond the -E2BIG cap.
  */
 typedef struct spmv_trsv_plan spmv_trsv_plan;
 int spmv_csr_trsv_analyse(const spmv_csr_dev *A, int uplo, int unit,
@@ -459,6 +460,69 @@ typedef struct spmv_ic0_info {
 } spmv_ic0_info;
 int spmv_csr_ic0(const spmv_csr_dev *A, double shift, int max_levels,
                  spmv_csr_dev **out, spmv_ic0_info *info /* may be NULL */);
+/*
+ * Zero-fill incomplete LU A ~ L U on the device, for a matrix that is not
+ * symmetric (added after 0.7; detect it by the symbol).  A: a square CSR handle
+ * with f64 values.  Every row, over the WHOLE row and not only its lower part,
+ * must be strictly ascending by column (so no duplicates) and must store its
+ * diagonal; a device check answers -EINVAL otherwise, before anything is
+ * allocated for the result.  spmv_csr_transpose twice sorts the rows of a
+ * handle.  *out is a new, ordinary f64 CSR handle, M x M, with exactly A's
+ * pattern: the entries with column < row are L (its unit diagonal is implied
+ * and not stored), the entries with column >= row are U.  launch,
+ * launch_multi, transpose, trsv_analyse, download and release work on it as on
+ * any handle, and ONE handle gives both plans of the preconditioner:
+ *     lower = spmv_csr_trsv_analyse(LU, 0, unit = 1)    L z' = r
+ *     upper = spmv_csr_trsv_analyse(LU, 1, unit = 0)    U z  = z'
+ * A is unchanged.  The call blocks.  shift >= 0 factors A + shift * diag(A).
+ * max_levels: as spmv_csr_trsv_analyse (0 = 1 << 20).
+ *
+ * Errors, in this order: NULL A or out, a non-finite or negative shift,
+ * max_levels < 0 -EINVAL; no device -ENODEV; a dead handle -EBADF; M != N
+ * -EINVAL; f32 values -ENOTSUP; after spmv_csr_release_source -ENODATA; a
+ * column outside [0, N) -EDOM; the ordering / diagonal check -EINVAL; more
+ * than max_levels levels -E2BIG; a failed allocation -ENOMEM.  On any error
+ * nothing is created, *out is NULL, and all scratch is freed on every path.
+ * M == 0 gives a valid empty handle.  A pivot that is zero or not finite is
+ * NOT an error: it is plain arithmetic (the inf / NaN of the division reaches
+ * exactly the dependent rows) and is counted in bad_pivots.  info may be NULL.
+ *
+ * THE RESULT IS DEFINED TO THE BIT.  Every operation is rounded once, no fused
+ * multiply-add, an IEEE division.  Row i has the columns c_0 < ... < c_{n-1},
+ * its diagonal at position d, and working values w_t = a_{i,c_t}:
+ *     w_d = rn(a_ii + rn(shift * a_ii))
+ *     for t = 0 .. d-1, in increasing t:       j = c_t
+ *         l = rn(w_t / u_jj);   w_t = l
+ *         for every column m > j stored in both row i and row j:
+ *             w_m = rn(w_m - rn(l * u_jm))
+ * Row i of the result is w; bad_pivots counts the rows whose final w_d is 0 or
+ * not finite.  shift = 0 leaves a finite a_ii unchanged.  For one t every w_m
+ * is touched at most once, and t increases: each entry receives its updates in
+ * increasing j, so the bits are a function of A and shift alone.  They depend
+ * neither on how many lanes work on a row, nor on set_csr_waves_per_block,
+ * which sizes the workgroups here, nor on which kernel ran a level, nor on the
+ * run.  (Unlike spmv_csr_ic0, whose sums force one lane per row, the updates
+ * of one t are independent: a group of lanes shares a row, each lane owning
+ * every G-th position of it.)
+ *
+ * The levels of the rows are those of the strict lower pattern of A, from the
+ * analysis of spmv_csr_trsv_analyse, and the launches are its launch list, as
+ * for spmv_csr_ic0: a level of more than small_rows rows is one launch, a
+ * maximal run of thinner levels one launch of ONE workgroup with a workgroup
+ * barrier between levels.  No waiting between workgroups of any kind; every
+ * device loop is bounded by a row length.  info: levels and launches of the
+ * factorisation, entries = the stored entries of the result (= those of A).
+ * A multicolour ordering (spmv_csr_colour, spmv_csr_permute below; the
+ * colouring reads A and A^T, so the pattern need not be symmetric) brings the
+ * levels of the factorisation and of both plans down to the colours.
+ */
+typedef struct spmv_ilu0_info {
+    int levels, launches; /* of the factorisation */
+    int64_t entries;      /* stored entries of LU (= those of A) */
+    int64_t bad_pivots;   /* rows whose final u_ii is 0 or not finite */
+} spmv_ilu0_info;
+int spmv_csr_ilu0(const spmv_csr_dev *A, double shift, int max_levels,
+                  spmv_csr_dev **out, spmv_ilu0_info *info /* may be NULL */);
 /*
  * A multicolour ordering on the device (added after 0.7; detect it by the
  * symbols): a plan has one level per colour at most once the rows of a colour
@@ -557,8 +621,8 @@ int spmv_csr_ic0(const spmv_csr_dev *A, double shift, int max_levels,
  *
  * Not in scope: HLL and compact (16-bit) handles as input, distance-2
  * colouring, balancing the sizes of the colours, RCM or any bandwidth
- * ordering, plans inside minres / bicgstab, ILU(0), and fusing a plan's solve
- * with its neighbours in the iteration.
+ * ordering, plans inside minres, ILU with fill, and fusing a plan's solve with
+ * its neighbours in the iteration.
  */
 typedef struct spmv_colour_info {
     int colours, rounds;   /* rounds = kernel rounds = longest priority chain */
@@ -1149,6 +1213,67 @@ int spmv_hll_bicgstab(const spmv_hll_dev *H, const spmv_launch_opts *opts,
                       double tol, int maxit, int check_every,
                       void *d_work, size_t work_bytes,
                       spmv_cg_info *info, void *stream);
+
+/*
+ * BiCGStab preconditioned by triangular plans (added after 0.7; detect it by
+ * the symbol): spmv_*_bicgstab word for word, with two differences.  The right
+ * preconditioner z(U) is made by spmv_trsv_solve instead of a multiplication
+ * by minv, in two steps:
+ *     spmv_trsv_solve(first, k, U -> Z, no scale)
+ *     if second is not NULL: spmv_trsv_solve(second, k, Z -> Z in place,
+ *                                            d_scale)
+ * always for all k columns, with an opts that carries only the caller's
+ * waves_per_block.  ILU(0) is (the unit lower plan of LU = spmv_csr_ilu0(A),
+ * the upper plan of the same LU, NULL); symmetric Gauss-Seidel is (the lower
+ * plan of A, the upper plan of A, diag(A)).  The plans and d_scale are never
+ * written and may serve any number of solves.
+ *
+ * And z IS STORED: spmv_*_bicgstab forms z(P) and z(S) again from minv where
+ * it updates X, a plan cannot be asked twice for the price of a
+ * multiplication.  Zp = z(P) and Zs = z(S) are two vectors, both live at the
+ * update, so d_work holds spmv_bicgstab_trsv_work_bytes(M, k) bytes: the base
+ * of spmv_bicgstab_work_bytes + 7 * 8 * k * M (R, Rh, P, V, T, Zp, Zs).  One
+ * iteration, in launch order:
+ *     V = A Zp;  rv;  alpha;  S = R - alpha V (in R);  Zs = z(S)
+ *     T = A Zs;  ts, tt;  omega;  X = (X + alpha Zp) + omega Zs, R = S - omega T
+ *     rn, rhon;  beta;  P = R + beta (P - omega V);  Zp = z(P)
+ * the first Zp = z(P) behind P = R of the set-up.  The recurrence, the
+ * classification ladder, the dot order and the roundings are those of
+ * spmv_*_bicgstab above with the stored vectors where it has z(.).  A frozen
+ * column's Z may hold anything, and nothing of it reaches X, R, P or the
+ * state.
+ *
+ * Everything else is spmv_*_bicgstab: the handles, the interleaved k = 1..8
+ * systems, the blocking, -EBUSY on a capturing stream, check_every, maxit,
+ * M == 0, the records and the frozen-column rule.  Checks added after
+ * bicgstab's, in this order (those of spmv_*_pcg_trsv): NULL first -EINVAL;
+ * d_scale without second -EINVAL; a dead plan -EBADF; a plan whose M is not
+ * A's -EINVAL.  A plan solve that is refused ends the solve with its code.
+ *
+ * Two properties of the contract, not special cases: a unit plan without
+ * strict entries (or a plan of the identity) returns the bits of
+ * spmv_*_bicgstab with d_minv == NULL; a plan of a diagonal matrix of powers
+ * of two returns the bits of spmv_*_bicgstab with d_minv = 1 / d.  A NaN in a
+ * factor makes rv NaN: the running columns end with status 2, never a fault.
+ *
+ * The price is that of spmv_*_pcg_trsv, twice: every iteration adds the
+ * launches of the plans two times (profiles/ilu0.md).
+ */
+int64_t spmv_bicgstab_trsv_work_bytes(int M, int k); /* as spmv_bicgstab_work_bytes */
+int spmv_csr_bicgstab_trsv(const spmv_csr_dev *A, const spmv_launch_opts *opts,
+                           int k, const double *d_B, int64_t ldb, double *d_X,
+                           int64_t ldx, const spmv_trsv_plan *first,
+                           const spmv_trsv_plan *second, const double *d_scale,
+                           double tol, int maxit, int check_every,
+                           void *d_work, size_t work_bytes,
+                           spmv_cg_info *info, void *stream);
+int spmv_hll_bicgstab_trsv(const spmv_hll_dev *H, const spmv_launch_opts *opts,
+                           int k, const double *d_B, int64_t ldb, double *d_X,
+                           int64_t ldx, const spmv_trsv_plan *first,
+                           const spmv_trsv_plan *second, const double *d_scale,
+                           double tol, int maxit, int check_every,
+                           void *d_work, size_t work_bytes,
+                           spmv_cg_info *info, void *stream);
 
 /*
  * CGLS on the device for rectangular least squares (added after 0.7;

@@ -424,6 +424,12 @@ class Ic0Info(C.Structure):
                 ("entries", C.c_int64), ("bad_pivots", C.c_int64)]
 
 
+class Ilu0Info(C.Structure):
+    """spmv_ilu0_info (include/spmv_engine.h): one CsrDevice.ilu0()"""
+    _fields_ = [("levels", C.c_int), ("launches", C.c_int),
+                ("entries", C.c_int64), ("bad_pivots", C.c_int64)]
+
+
 class ColourInfo(C.Structure):
     """spmv_colour_info (include/spmv_engine.h): one CsrDevice.colour()"""
     _fields_ = [("colours", C.c_int), ("rounds", C.c_int),
@@ -574,6 +580,8 @@ _sig("spmv_trsv_solve", C.c_int, C.c_void_p, C.POINTER(LaunchOpts), C.c_int,
      C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
 _sig("spmv_csr_ic0", C.c_int, C.c_void_p, C.c_double, C.c_int,
      C.POINTER(C.c_void_p), C.POINTER(Ic0Info))
+_sig("spmv_csr_ilu0", C.c_int, C.c_void_p, C.c_double, C.c_int,
+     C.POINTER(C.c_void_p), C.POINTER(Ilu0Info))
 _sig("spmv_csr_colour", C.c_int, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p,
      C.c_void_p, C.POINTER(ColourInfo))
 _sig("spmv_csr_permute", C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -603,6 +611,7 @@ _sig("spmv_cg_dot_shape", None, _ip, _ip)
 _sig("spmv_pcg_work_bytes", C.c_int64, C.c_int, C.c_int)
 _sig("spmv_pcg_trsv_work_bytes", C.c_int64, C.c_int, C.c_int)
 _sig("spmv_bicgstab_work_bytes", C.c_int64, C.c_int, C.c_int)
+_sig("spmv_bicgstab_trsv_work_bytes", C.c_int64, C.c_int, C.c_int)
 _sig("spmv_cgls_work_bytes", C.c_int64, C.c_int, C.c_int, C.c_int)
 _sig("spmv_minres_work_bytes", C.c_int64, C.c_int, C.c_int)
 _sig("spmv_debug_sqrt", C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
@@ -661,6 +670,10 @@ _TWINS = (
      C.c_void_p, C.POINTER(LaunchOpts), C.c_int, C.c_void_p, C.c_int64,
      C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_int, C.c_int,
      C.c_void_p, C.c_size_t, C.POINTER(CgInfo), C.c_void_p),
+    ("bicgstab_trsv", C.c_int,
+     C.c_void_p, C.POINTER(LaunchOpts), C.c_int, C.c_void_p, C.c_int64,
+     C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+     C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(CgInfo), C.c_void_p),
     ("cgls", C.c_int,
      C.c_void_p, C.c_void_p, C.POINTER(LaunchOpts), C.c_int, C.c_void_p,
      C.c_int64, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int,
@@ -774,6 +787,14 @@ def bicgstab_work_bytes(M, k):
     needs: a base that depends on neither, and six vectors of 8 k M bytes"""
     return _check(_lib.spmv_bicgstab_work_bytes(int(M), int(k)),
                   "spmv_bicgstab_work_bytes")
+
+
+def bicgstab_trsv_work_bytes(M, k):
+    """bytes of device memory one bicgstab_trsv() solve of k systems with M
+    rows needs: the base of bicgstab_work_bytes and seven vectors of 8 k M
+    bytes (z(P) and z(S) are stored, each in a vector of its own)"""
+    return _check(_lib.spmv_bicgstab_trsv_work_bytes(int(M), int(k)),
+                  "spmv_bicgstab_trsv_work_bytes")
 
 
 #: one column of a cgls() solve
@@ -1608,6 +1629,32 @@ class _Device:
                         check_every, ldb, ldx, work, waves_per_block, group,
                         stream)
 
+    def bicgstab_trsv(self, d_B, d_X, first, second=None, d_scale=None, k=1,
+                      tol=1e-8, maxit=1000, check_every=0, ldb=0, ldx=0,
+                      work=None, waves_per_block=0, group=0, stream=None):
+        """bicgstab() with a right preconditioner made by triangular plans:
+        z = M^-1 u is first.solve(u -> z), then, with a second TrsvPlan,
+        second.solve(z -> z in place, scale=d_scale).  ILU(0): with
+        LU = A.ilu0()[0], first = LU.trsv_analyse("lower", unit=True) and
+        second = LU.trsv_analyse("upper"); symmetric Gauss-Seidel:
+        bicgstab_trsv(d_B, d_X, *A.sgs().args).  The plans and d_scale (M
+        doubles) are not written and may be shared by any number of solves.
+        Everything else as bicgstab() (`work`: at least
+        bicgstab_trsv_work_bytes(M, k) bytes).  Each iteration adds the
+        launches of the plans twice (TrsvPlan.info["launches"]).
+        -> [CgResult(status, iterations, rr, bb)] * k"""
+        if not isinstance(first, TrsvPlan) or \
+                not (second is None or isinstance(second, TrsvPlan)):
+            raise ValueError("bicgstab_trsv: first is a TrsvPlan, second a "
+                             "TrsvPlan or None")
+        if d_scale is not None and second is None:
+            raise ValueError("bicgstab_trsv: d_scale scales the input of the "
+                             "second plan, and there is none")
+        return self._cg("bicgstab_trsv", d_B, d_X,
+                        (first.h, second.h if second is not None else None,
+                         d_scale), k, tol, maxit, check_every, ldb, ldx, work,
+                        waves_per_block, group, stream)
+
     def minres(self, d_B, d_X, k=1, d_minv=None, tol=1e-8, maxit=1000,
                check_every=0, ldb=0, ldx=0, work=None, waves_per_block=0,
                group=0, stream=None):
@@ -1886,6 +1933,30 @@ class CsrDevice(_Device):
         h, info = C.c_void_p(), Ic0Info()
         _check(_lib.spmv_csr_ic0(self.h, shift, max_levels, C.byref(h),
                                  C.byref(info)), "spmv_csr_ic0")
+        return CsrDevice(h), info
+
+    def ilu0(self, shift=0.0, max_levels=0):
+        """(LU, Ilu0Info): the zero-fill incomplete LU factors of this
+        (square, f64) handle, A + shift diag(A) ~ L U, as ONE new CsrDevice
+        with exactly this handle's pattern: L strictly below the diagonal
+        (its unit diagonal implied), U on and above it, built on the device
+        and defined to the bit (spmv_engine.h).  Every row must be strictly
+        ascending and hold its diagonal (OSError(EINVAL) otherwise;
+        transpose().transpose() sorts rows).  A pivot that is zero or not
+        finite is counted in Ilu0Info.bad_pivots and leaves inf / NaN in the
+        dependent rows, it is not an error.  The preconditioner of
+        bicgstab_trsv() is (LU.trsv_analyse("lower", unit=True),
+        LU.trsv_analyse("upper")).  This handle stays valid"""
+        shift, max_levels = float(shift), int(max_levels)
+        if not (shift >= 0.0 and np.isfinite(shift)):
+            raise ValueError("shift=%r: a finite number, 0 or more"
+                             % (shift,))
+        if max_levels < 0:
+            raise ValueError("max_levels=%d: 0 (the default) or more"
+                             % max_levels)
+        h, info = C.c_void_p(), Ilu0Info()
+        _check(_lib.spmv_csr_ilu0(self.h, shift, max_levels, C.byref(h),
+                                  C.byref(info)), "spmv_csr_ilu0")
         return CsrDevice(h), info
 
     def colour(self, seed=0, max_rounds=0):

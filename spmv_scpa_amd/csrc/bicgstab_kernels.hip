@@ -1,8 +1,8 @@
 /*
  * bicgstab_kernels.hip -- BiCGStab for A X = B on the device (spmv_*_bicgstab,
- * spmv_engine.h), A square and otherwise arbitrary, with an optional right
- * diagonal preconditioner: k = 1..8 independent systems stored interleaved
- * (X[i * ldx + j]), A a CSR or column-major HLL handle, gfx950 (wave64).
+ * spmv_*_bicgstab_trsv; spmv_engine.h), A square and otherwise arbitrary, with
+ * an optional right preconditioner, a diagonal or triangular plans: k = 1..8
+ * independent systems stored interleaved (X[i * ldx + j]), A a CSR or column-major HLL handle, gfx950 (wave64).
  *
  * The two products of an iteration and the initial residual are the handle's
  * launch_multi / launch_axpby (cg_matrix, as in cg_kernels.hip); only A x is
@@ -32,9 +32,16 @@
  * being read: 8 M bytes for two streams of 8 k M.  S lives in R's storage, Z
  * and Zs share one buffer: the vector launch_multi reads.
  *
- * PRE.  Every vector kernel is a template over <K, PRE>: PRE false has no minv
- * argument to read and z(u) = u; PRE true forms rn(minv_i * u).  rn(1.0 * u)
+ * PRE.  Every vector kernel is a template over <K, PRE>: BI_NONE has no minv
+ * argument to read and z(u) = u; BI_DIAG forms rn(minv_i * u).  rn(1.0 * u)
  * is u, so minv of all 1.0 gives the bits of minv == NULL by arithmetic.
+ * BI_STORED is spmv_*_bicgstab_trsv: z(.) is made by triangular plans
+ * (bi_apply: trsv_solve_dev once or twice) BEHIND the kernel that made its
+ * argument -- behind k_bi_first and k_bi_dir for Zp = z(P), behind k_bi_s for
+ * Zs = z(S) -- so those three write no Z at all, and k_bi_update reads Zp and Zs
+ * where the other modes multiply: a plan cannot be recomputed, so the two are
+ * vectors of their own, both live at the update (bicgstab_trsv_work: 7
+ * vectors).  The statements of the other two modes are what they were.
  *
  * STATE and FROZEN COLUMNS: as in cg_kernels.hip.  bi_state is written by ONE
  * workgroup (the finalising kernels, thread 0), the vector kernels read it and
@@ -57,11 +64,16 @@ struct bi_state {
 };
 static_assert(sizeof(bi_state) <= CG_STATE_BYTES, "state block");
 
+/* PRE of the vector kernels */
+#define BI_NONE 0   /* z(u) = u */
+#define BI_DIAG 1   /* z(u) = rn(minv_i * u), formed where it is used */
+#define BI_STORED 2 /* z(u) made by triangular plans between the kernels */
+
 /* z(u) of one element: rn(minv_i * u), or u itself */
-template <bool PRE>
+template <int PRE>
 __device__ __forceinline__ double bi_z(double d, double u) {
 #pragma clang fp contract(off)
-    if constexpr (PRE)
+    if constexpr (PRE == BI_DIAG)
         return d * u;
     else
         return u;
@@ -69,7 +81,7 @@ __device__ __forceinline__ double bi_z(double d, double u) {
 
 /* Rh = R, P = R, Z = z(R), interleaved with ld = K; all columns (nothing is
  * frozen before the first classification) */
-template <int K, bool PRE>
+template <int K, int PRE>
 __global__ void __launch_bounds__(CG_T)
 k_bi_first(int M, const double *__restrict__ minv,
            const double *__restrict__ R, double *__restrict__ Rh,
@@ -83,7 +95,7 @@ k_bi_first(int M, const double *__restrict__ minv,
             const int64_t i = base + l.t[n] < M ? base + l.t[n] : M - 1;
             r[n] = R[i * K + l.j[n]];
             d[n] = 0.0;
-            if constexpr (PRE)
+            if constexpr (PRE == BI_DIAG)
                 d[n] = minv[i];
         }
 #pragma unroll
@@ -93,14 +105,15 @@ k_bi_first(int M, const double *__restrict__ minv,
             if (i < M) {
                 Rh[i * K + l.j[n]] = r[n];
                 P[i * K + l.j[n]] = r[n];
-                Z[i * K + l.j[n]] = z;
+                if constexpr (PRE != BI_STORED)
+                    Z[i * K + l.j[n]] = z;
             }
         }
     }
 }
 
 /* the running columns: S = R - alpha V in R's place, Z = z(S) */
-template <int K, bool PRE>
+template <int K, int PRE>
 __global__ void __launch_bounds__(CG_T)
 k_bi_s(int M, const bi_state *__restrict__ st,
        const double *__restrict__ minv, double *__restrict__ R,
@@ -121,7 +134,7 @@ k_bi_s(int M, const bi_state *__restrict__ st,
             r[n] = R[i * K + l.j[n]];
             v[n] = V[i * K + l.j[n]];
             d[n] = 0.0;
-            if constexpr (PRE)
+            if constexpr (PRE == BI_DIAG)
                 d[n] = minv[i];
         }
 #pragma unroll
@@ -132,7 +145,8 @@ k_bi_s(int M, const bi_state *__restrict__ st,
             const double z = bi_z<PRE>(d[n], sn);
             if (i < M && running[n]) {
                 R[i * K + l.j[n]] = sn;
-                Z[i * K + l.j[n]] = z;
+                if constexpr (PRE != BI_STORED)
+                    Z[i * K + l.j[n]] = z;
             }
         }
     }
@@ -180,13 +194,14 @@ k_bi_tstt(int M, const double *__restrict__ T, const double *__restrict__ S,
 /* fused update of the running columns: X = (X + alpha z(P)) + omega z(S),
  * R = S - omega T (S stands in R), and the partials of R . R and Rh . R in the
  * dot order -- one pass over five vectors and minv */
-template <int K, bool PRE>
+template <int K, int PRE>
 __global__ void __launch_bounds__(CG_T)
 k_bi_update(int M, const bi_state *__restrict__ st,
             const double *__restrict__ minv, double *__restrict__ X,
             int64_t ldx, const double *__restrict__ P, double *__restrict__ R,
             const double *__restrict__ T, const double *__restrict__ Rh,
-            double *__restrict__ part_rn, double *__restrict__ part_rhon) {
+            double *__restrict__ part_rn, double *__restrict__ part_rhon,
+            const double *__restrict__ Zp, const double *__restrict__ Zs) {
 #pragma clang fp contract(off)
     const cg_lanes<K> l;
     bool running[K];
@@ -205,19 +220,28 @@ k_bi_update(int M, const bi_state *__restrict__ st,
         for (int n = 0; n < K; ++n) {
             const int64_t i = base + l.t[n] < M ? base + l.t[n] : M - 1;
             x[n] = X[i * ldx + l.j[n]];
-            p[n] = P[i * K + l.j[n]];
+            /* stored: p holds z(P) and d holds z(S) as they stand in memory;
+             * P and minv are not read */
+            if constexpr (PRE == BI_STORED)
+                p[n] = Zp[i * K + l.j[n]];
+            else
+                p[n] = P[i * K + l.j[n]];
             sv[n] = R[i * K + l.j[n]];
             t[n] = T[i * K + l.j[n]];
             rh[n] = Rh[i * K + l.j[n]];
             d[n] = 0.0;
-            if constexpr (PRE)
+            if constexpr (PRE == BI_DIAG)
                 d[n] = minv[i];
+            if constexpr (PRE == BI_STORED)
+                d[n] = Zs[i * K + l.j[n]];
         }
 #pragma unroll
         for (int n = 0; n < K; ++n) {
             const int64_t i = base + l.t[n];
-            const double zp = bi_z<PRE>(d[n], p[n]);
-            const double zs = bi_z<PRE>(d[n], sv[n]);
+            const double zp =
+                PRE == BI_STORED ? p[n] : bi_z<PRE>(d[n], p[n]);
+            const double zs =
+                PRE == BI_STORED ? d[n] : bi_z<PRE>(d[n], sv[n]);
             const double ap = alpha[n] * zp;
             const double x1 = x[n] + ap;
             const double os = omega[n] * zs;
@@ -243,7 +267,7 @@ k_bi_update(int M, const bi_state *__restrict__ st,
 
 /* direction update of the running columns: P = R + beta (P - omega V), and
  * Z = z(P) for the next product */
-template <int K, bool PRE>
+template <int K, int PRE>
 __global__ void __launch_bounds__(CG_T)
 k_bi_dir(int M, const bi_state *__restrict__ st,
          const double *__restrict__ minv, const double *__restrict__ R,
@@ -268,7 +292,7 @@ k_bi_dir(int M, const bi_state *__restrict__ st,
             r[n] = R[i * K + l.j[n]];
             v[n] = V[i * K + l.j[n]];
             d[n] = 0.0;
-            if constexpr (PRE)
+            if constexpr (PRE == BI_DIAG)
                 d[n] = minv[i];
         }
 #pragma unroll
@@ -281,7 +305,8 @@ k_bi_dir(int M, const bi_state *__restrict__ st,
             const double z = bi_z<PRE>(d[n], pn);
             if (i < M && running[n]) {
                 P[i * K + l.j[n]] = pn;
-                Z[i * K + l.j[n]] = z;
+                if constexpr (PRE != BI_STORED)
+                    Z[i * K + l.j[n]] = z;
             }
         }
     }
@@ -393,24 +418,58 @@ k_bi_final_beta(int k, int nwg, const double *__restrict__ part_rn,
 /* host                                                                 */
 /* ------------------------------------------------------------------ */
 
-int64_t bicgstab_work_bytes(int M, int k) {
-    return solver_work_bytes(bicgstab_work(M, k));
+int64_t bicgstab_work_bytes(int M, int k, int trsv) {
+    return solver_work_bytes(trsv ? bicgstab_trsv_work(M, k)
+                                  : bicgstab_work(M, k));
 }
 
-/* The arguments were checked by the caller (engine.hip, bicgstab): k in 1..8,
- * ldb, ldx >= k, M == N > 0, tol >= 0, maxit >= 0, check_every > 0. */
+/* kernel<k, pre>(M, ...): the vector kernels by their PRE */
+#define BI_LAUNCH_K(KK, kernel, pre, M, s, ...)                               \
+    do {                                                                      \
+        if ((pre) == BI_STORED)                                               \
+            hipLaunchKernelGGL((kernel<KK, BI_STORED>), dim3(cg_grid(M)),     \
+                               dim3(CG_T), 0, s, M, __VA_ARGS__);             \
+        else if ((pre) == BI_DIAG)                                            \
+            hipLaunchKernelGGL((kernel<KK, BI_DIAG>), dim3(cg_grid(M)),       \
+                               dim3(CG_T), 0, s, M, __VA_ARGS__);             \
+        else                                                                  \
+            hipLaunchKernelGGL((kernel<KK, BI_NONE>), dim3(cg_grid(M)),       \
+                               dim3(CG_T), 0, s, M, __VA_ARGS__);             \
+    } while (0)
+#define BI_LAUNCH(kernel, pre, k, M, s, ...)                                  \
+    CG_K_SWITCH(k, BI_LAUNCH_K, kernel, pre, M, s, __VA_ARGS__)
+
+/* Z = z(U) of spmv_*_bicgstab_trsv, all k columns (a frozen column's Z
+ * reaches nothing: every consumer is predicated); a refused plan solve is the
+ * code that ends the batch */
+static int bi_apply(const cg_plans &pl, int k, const double *U, double *Z,
+                    hipStream_t s) {
+    int rc = trsv_solve_dev(pl.first, pl.waves, k, U, k, Z, k, NULL, s);
+    if (!rc && pl.second)
+        rc = trsv_solve_dev(pl.second, pl.waves, k, Z, k, Z, k, pl.scale, s);
+    return rc;
+}
+
+/* The arguments were checked by the caller (engine.hip, bicgstab /
+ * bicgstab_trsv): k in 1..8, ldb, ldx >= k, M == N > 0, tol >= 0, maxit >= 0,
+ * check_every > 0, live plans of M rows.  plans != NULL (and minv NULL): the
+ * stored mode, Z = z(P) in Zp and z(S) in a vector Zs of its own; else Zs is
+ * Zp, the one buffer launch_multi reads. */
 int bicgstab_solve(const cg_matrix *A, int k, const double *B, int64_t ldb,
-                   double *X, int64_t ldx, const double *minv, double tol,
-                   int maxit, int check_every, void *d_work, size_t work_bytes,
+                   double *X, int64_t ldx, const double *minv,
+                   const cg_plans *plans, double tol, int maxit,
+                   int check_every, void *d_work, size_t work_bytes,
                    spmv_cg_info *info, hipStream_t s) {
     const int M = A->M;
-    const bool pre = minv != NULL;
-    const solver_work w = bicgstab_work(M, k);
+    const int pre = plans ? BI_STORED : minv ? BI_DIAG : BI_NONE;
+    const solver_work w =
+        plans ? bicgstab_trsv_work(M, k) : bicgstab_work(M, k);
     const int nwg = (int)cg_grid(M);
     const double tol2 = tol * tol;
     bi_state *st = NULL;
     double *part0 = NULL, *part1 = NULL;
-    double *R = NULL, *Rh = NULL, *P = NULL, *V = NULL, *T = NULL, *Z = NULL;
+    double *R = NULL, *Rh = NULL, *P = NULL, *V = NULL, *T = NULL, *Zp = NULL,
+           *Zs = NULL;
     bi_state h;
     const int rc = solver_run(
         w, maxit, check_every, d_work, work_bytes, &h, s,
@@ -424,35 +483,52 @@ int bicgstab_solve(const cg_matrix *A, int k, const double *B, int64_t ldb,
             P = solver_vec(work, w, 2);
             V = solver_vec(work, w, 3);
             T = solver_vec(work, w, 4);
-            Z = solver_vec(work, w, 5);
+            Zp = solver_vec(work, w, 5);
+            Zs = plans ? solver_vec(work, w, 6) : Zp;
             cg_launch_copy(k, M, B, ldb, R, k, s);
-            const int rc =
+            int rc =
                 A->axpby(A->handle, A->opts, k, -1.0, 1.0, X, ldx, R, k, s);
             if (rc)
                 return rc;
-            CG_LAUNCH_FLAG(k_bi_first, pre, k, M, s, minv, R, Rh, P, Z);
+            BI_LAUNCH(k_bi_first, pre, k, M, s, minv, R, Rh, P, Zp);
+            if (plans) {
+                rc = bi_apply(*plans, k, P, Zp, s);
+                if (rc)
+                    return rc;
+            }
             cg_launch_dot(k, M, B, ldb, B, ldb, part0, s);
             cg_launch_dot(k, M, R, k, R, k, part1, s);
             CG_FINAL(k_bi_final_init, s, k, nwg, part0, part1, tol2, st);
             return 0;
         },
         [&](int) {
-            int rc = A->multi(A->handle, A->opts, k, Z, k, V, k, s);
+            int rc = A->multi(A->handle, A->opts, k, Zp, k, V, k, s);
             if (rc)
                 return rc;
             cg_launch_dot(k, M, Rh, k, V, k, part0, s);
             CG_FINAL(k_bi_final_alpha, s, k, nwg, part0, st);
-            CG_LAUNCH_FLAG(k_bi_s, pre, k, M, s, st, minv, R, V, Z);
-            rc = A->multi(A->handle, A->opts, k, Z, k, T, k, s);
+            BI_LAUNCH(k_bi_s, pre, k, M, s, st, minv, R, V, Zs);
+            if (plans) {
+                rc = bi_apply(*plans, k, R, Zs, s);
+                if (rc)
+                    return rc;
+            }
+            rc = A->multi(A->handle, A->opts, k, Zs, k, T, k, s);
             if (rc)
                 return rc;
             CG_LAUNCH(k_bi_tstt, k, M, s, T, R, part0, part1);
             CG_FINAL(k_bi_final_omega, s, k, nwg, part0, part1, st);
-            CG_LAUNCH_FLAG(k_bi_update, pre, k, M, s, st, minv, X, ldx, P, R,
-                           T, Rh, part0, part1);
+            /* the stored vectors are arguments of the stored mode alone: the
+             * other two never read them (there Zs IS Zp, which two restrict
+             * pointers must not be) */
+            BI_LAUNCH(k_bi_update, pre, k, M, s, st, minv, X, ldx, P, R, T, Rh,
+                      part0, part1, plans ? Zp : (const double *)NULL,
+                      plans ? Zs : (const double *)NULL);
             CG_FINAL(k_bi_final_beta, s, k, nwg, part0, part1, tol2, st);
-            CG_LAUNCH_FLAG(k_bi_dir, pre, k, M, s, st, minv, R, V, P, Z);
-            return 0;
+            BI_LAUNCH(k_bi_dir, pre, k, M, s, st, minv, R, V, P, Zp);
+            if (plans)
+                rc = bi_apply(*plans, k, P, Zp, s);
+            return rc;
         },
         [] { return 0; });
     if (rc)

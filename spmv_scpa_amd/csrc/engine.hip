@@ -1094,6 +1094,42 @@ int spmv_csr_ic0(const spmv_csr_dev *A, double shift, int max_levels,
     return 0;
 }
 
+/* L and U of A ~ L U on A's pattern, a new M x M f64 handle
+ * (ilu0_kernels.hip): the checks of spmv_csr_ic0, in its order */
+int spmv_csr_ilu0(const spmv_csr_dev *A, double shift, int max_levels,
+                  spmv_csr_dev **out, spmv_ilu0_info *info) {
+    if (out)
+        *out = NULL; /* on ANY error, the argument checks included */
+    if (!A || !out || !(shift >= 0.0) || !std::isfinite(shift) ||
+        max_levels < 0)
+        return -EINVAL;
+    if (spmv_device_count() == 0)
+        return -ENODEV; /* no handle can be live: the more useful answer */
+    HANDLE_OK(A);
+    if (A->M != A->N)
+        return -EINVAL;
+    if (A->value_bytes != 8)
+        return -ENOTSUP;
+    if (!A->ja && A->NZ > 0)
+        return -ENODATA; /* spmv_csr_release_source() */
+    spmv_csr_dev *d = NULL;
+    spmv_ilu0_info got;
+    int rc = ilu0_factor_dev(
+        A, shift, max_levels ? max_levels : TRSV_DEFAULT_MAX_LEVELS,
+        g_csr_waves, csr_alloc_dev, &d, &got, 0);
+    if (rc)
+        return rc;
+    rc = finish_csr_handle(d, NULL);
+    if (rc) {
+        spmv_csr_release(d);
+        return rc;
+    }
+    if (info)
+        *info = got;
+    *out = d;
+    return 0;
+}
+
 /* 0: not symmetric, 1: the pattern is, 2: the stored values are too */
 int spmv_csr_symmetry(const spmv_csr_dev *A, int *out) {
     if (!A || !out)
@@ -2227,6 +2263,18 @@ static int cg(const D *d, const spmv_launch_opts *opts, int k,
                     check_every, d_work, work_bytes, info, (hipStream_t)stream);
 }
 
+/* the checks spmv_*_pcg_trsv and spmv_*_bicgstab_trsv add for their plans */
+static int plans_check(int M, const spmv_trsv_plan *first,
+                       const spmv_trsv_plan *second, const double *d_scale) {
+    if (!first || (d_scale && !second))
+        return -EINVAL;
+    if (!live_has(first) || (second && !live_has(second)))
+        return -EBADF;
+    if (first->M != M || (second && second->M != M))
+        return -EINVAL;
+    return 0;
+}
+
 /* spmv_*_pcg_trsv: cg's checks, then the plans'; the plans run with an opts
  * that carries only the caller's waves_per_block */
 template <typename D>
@@ -2237,15 +2285,8 @@ static int cg_trsv(const D *d, const spmv_launch_opts *opts, int k,
                    int check_every, void *d_work, size_t work_bytes,
                    spmv_cg_info *info, void *stream) {
     const int rc = solver_check(
-        d, opts, k, d_B, &ldb, d_X, &ldx, tol, maxit, &check_every, info, [&] {
-            if (!first || (d_scale && !second))
-                return -EINVAL;
-            if (!live_has(first) || (second && !live_has(second)))
-                return -EBADF;
-            if (first->M != d->M || (second && second->M != d->M))
-                return -EINVAL;
-            return 0;
-        });
+        d, opts, k, d_B, &ldb, d_X, &ldx, tol, maxit, &check_every, info,
+        [&] { return plans_check(d->M, first, second, d_scale); });
     if (rc)
         return rc < 0 ? rc : 0;
     const cg_matrix A = cg_matrix_of(d, opts);
@@ -2268,7 +2309,28 @@ static int bicgstab(const D *d, const spmv_launch_opts *opts, int k,
     if (rc)
         return rc < 0 ? rc : 0;
     const cg_matrix A = cg_matrix_of(d, opts);
-    return bicgstab_solve(&A, k, d_B, ldb, d_X, ldx, d_minv, tol, maxit,
+    return bicgstab_solve(&A, k, d_B, ldb, d_X, ldx, d_minv, NULL, tol, maxit,
+                          check_every, d_work, work_bytes, info,
+                          (hipStream_t)stream);
+}
+
+/* spmv_*_bicgstab_trsv: bicgstab's checks, then the plans' as cg_trsv's */
+template <typename D>
+static int bicgstab_trsv(const D *d, const spmv_launch_opts *opts, int k,
+                         const double *d_B, int64_t ldb, double *d_X,
+                         int64_t ldx, const spmv_trsv_plan *first,
+                         const spmv_trsv_plan *second, const double *d_scale,
+                         double tol, int maxit, int check_every, void *d_work,
+                         size_t work_bytes, spmv_cg_info *info, void *stream) {
+    const int rc = solver_check(
+        d, opts, k, d_B, &ldb, d_X, &ldx, tol, maxit, &check_every, info,
+        [&] { return plans_check(d->M, first, second, d_scale); });
+    if (rc)
+        return rc < 0 ? rc : 0;
+    const cg_matrix A = cg_matrix_of(d, opts);
+    const cg_plans pl = {first, second, d_scale,
+                         opts ? opts->waves_per_block : 0};
+    return bicgstab_solve(&A, k, d_B, ldb, d_X, ldx, NULL, &pl, tol, maxit,
                           check_every, d_work, work_bytes, info,
                           (hipStream_t)stream);
 }
@@ -2967,6 +3029,16 @@ static int copy_tune_log(const D *d, char *buf, size_t len) {
         return bicgstab(d, opts, k, d_B, ldb, d_X, ldx, d_minv, tol, maxit,    \
                         check_every, d_work, work_bytes, info, stream);        \
     }                                                                          \
+    int spmv_##fmt##_bicgstab_trsv(                                            \
+        const D *d, const spmv_launch_opts *opts, int k, const double *d_B,    \
+        int64_t ldb, double *d_X, int64_t ldx, const spmv_trsv_plan *first,    \
+        const spmv_trsv_plan *second, const double *d_scale, double tol,       \
+        int maxit, int check_every, void *d_work, size_t work_bytes,           \
+        spmv_cg_info *info, void *stream) {                                    \
+        return bicgstab_trsv(d, opts, k, d_B, ldb, d_X, ldx, first, second,    \
+                             d_scale, tol, maxit, check_every, d_work,         \
+                             work_bytes, info, stream);                        \
+    }                                                                          \
     int spmv_##fmt##_cgls(const D *d, const D *dt,                             \
                           const spmv_launch_opts *opts, int k,                 \
                           const double *d_B, int64_t ldb, double *d_X,         \
@@ -3063,7 +3135,10 @@ int64_t spmv_pcg_trsv_work_bytes(int M, int k) {
     return cg_work_bytes(M, k, 2);
 }
 int64_t spmv_bicgstab_work_bytes(int M, int k) {
-    return bicgstab_work_bytes(M, k);
+    return bicgstab_work_bytes(M, k, 0);
+}
+int64_t spmv_bicgstab_trsv_work_bytes(int M, int k) {
+    return bicgstab_work_bytes(M, k, 1);
 }
 int64_t spmv_cgls_work_bytes(int M, int N, int k) {
     return cgls_work_bytes(M, N, k);

@@ -3,7 +3,7 @@
  * (engine.hip, csr_kernels.hip, hll_kernels.hip, multi_kernels.hip,
  * cg_kernels.hip, bicgstab_kernels.hip, cgls_kernels.hip, minres_kernels.hip,
  * diag_kernels.hip, transpose_kernels.hip, trsv_kernels.hip, ic0_kernels.hip,
- * panels.hip, mgpu.hip, and
+ * ilu0_kernels.hip, panels.hip, mgpu.hip, and
  * mat_ref.h on behalf of the first and the last).
  * Not installed.
  */
@@ -560,12 +560,15 @@ void cg_launch_dot(int k, int M, const double *U, int64_t ldu, const double *V,
 /*
  * BiCGStab for nonsymmetric A (bicgstab_kernels.hip; spmv_*_bicgstab): the
  * matrix, the dot, the state block and the records of cg; minv == NULL is no
- * preconditioner, else Z = minv .* P is what the matrix multiplies.
+ * preconditioner, else Z = minv .* P is what the matrix multiplies.  plans !=
+ * NULL (minv NULL; spmv_*_bicgstab_trsv): Z = z(P) and z(S) are made by the
+ * plans and STORED, one more vector in the work buffer (trsv: 1).
  */
-int64_t bicgstab_work_bytes(int M, int k);
+int64_t bicgstab_work_bytes(int M, int k, int trsv);
 int bicgstab_solve(const cg_matrix *A, int k, const double *B, int64_t ldb,
-                   double *X, int64_t ldx, const double *minv, double tol,
-                   int maxit, int check_every, void *d_work, size_t work_bytes,
+                   double *X, int64_t ldx, const double *minv,
+                   const cg_plans *plans, double tol, int maxit,
+                   int check_every, void *d_work, size_t work_bytes,
                    spmv_cg_info *info, hipStream_t s);
 
 /*
@@ -658,6 +661,14 @@ typedef int (*ic0_alloc_fn)(int M, int N, int64_t NZ, int value_bytes,
 int ic0_factor_dev(const spmv_csr_dev *A, double shift, int max_levels,
                    int waves, ic0_alloc_fn alloc, spmv_csr_dev **out,
                    spmv_ic0_info *info, hipStream_t s);
+/*
+ * Zero-fill incomplete LU (ilu0_kernels.hip; spmv_csr_ilu0): the same
+ * arrangement.  *out holds A's irp and ja and the factor, L strictly below the
+ * diagonal (its unit diagonal implied), U on and above it.
+ */
+int ilu0_factor_dev(const spmv_csr_dev *A, double shift, int max_levels,
+                    int waves, ic0_alloc_fn alloc, spmv_csr_dev **out,
+                    spmv_ilu0_info *info, hipStream_t s);
 
 /*
  * Colouring and permutation (colour_kernels.hip; spmv_csr_colour,

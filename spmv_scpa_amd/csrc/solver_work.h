@@ -25,7 +25,7 @@
 #define CG_STATE_BYTES 512  /* cg_state, bi_state, ls_state */
 #define MR_STATE_BYTES 2048 /* mr_state */
 
-#define SOLVER_WORK_MAXV 6
+#define SOLVER_WORK_MAXV 7
 
 struct solver_work {
     int k;
@@ -71,6 +71,12 @@ static inline solver_work cg_work(int M, int k, int pre) {
 /* parts (rv | ts | rn | bb), (tt | rhon | rr);  R, Rh, P, V, T, Z */
 static inline solver_work bicgstab_work(int M, int k) {
     return solver_work{k, CG_STATE_BYTES, 2, 6, {M, M, M, M, M, M}};
+}
+
+/* spmv_*_bicgstab_trsv: the same parts;  R, Rh, P, V, T, Zp = z(P), Zs = z(S):
+ * the plans cannot recompute a z, so both are stored and live at the update */
+static inline solver_work bicgstab_trsv_work(int M, int k) {
+    return solver_work{k, CG_STATE_BYTES, 2, 7, {M, M, M, M, M, M, M}};
 }
 
 /* parts (qq | ss | sn | rr), atb, pp;  R, Q of M rows, S, P of N rows */
