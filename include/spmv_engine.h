@@ -1276,6 +1276,110 @@ int spmv_hll_bicgstab_trsv(const spmv_hll_dev *H, const spmv_launch_opts *opts,
                            spmv_cg_info *info, void *stream);
 
 /*
+ * Restarted GMRES(m) on the device for A X = B with a nonsymmetric A (added
+ * after 0.7; detect it by the symbol).  One product and one preconditioner
+ * apply per Arnoldi step, a residual estimate that never grows within a
+ * cycle, and no breakdown other than a singular matrix or a non-finite
+ * number.  The handles (f64 and f32 CSR, column-major HLL; -ENOTSUP on a
+ * handle with 16-bit offsets), the interleaved k = 1..8 systems and the
+ * strides, d_minv (a RIGHT diagonal preconditioner, NULL: none), the
+ * blocking, -EBUSY on a capturing stream, check_every (0 = 8), M == 0, d_work
+ * (NULL: the library allocates and frees it) and the argument checks in their
+ * order are those of spmv_*_bicgstab above, word for word; then restart
+ * outside 1..64 is -EINVAL, and for the _trsv pair the plan checks of
+ * spmv_*_bicgstab_trsv follow, in that order.  maxit counts Arnoldi steps over
+ * all cycles.
+ *
+ * spmv_gmres_work_bytes(M, k, m) = base(m) + (m + 3) * 8 * k * M, the same in
+ * all three preconditioner modes: base(m) holds the state (a head and, for 8
+ * columns, the rotated Hessenberg factor, the rotations and g: it depends on m
+ * alone) and m + 1 sets of partial sums; then the basis V_0..V_m as one vector
+ * of (m + 1) M rows, W and Z.
+ *
+ * Result contract, to the bit.  Every operation is rounded once, no fused
+ * multiply-add, divisions and square roots are correctly rounded; dot is the
+ * dot of spmv_cg_dot_shape; z(U) is U, rn(minv_i * u_i), or the two plan
+ * solves of spmv_*_bicgstab_trsv; tol2 = tol * tol on the host.
+ *
+ *   START (and every restart, for the columns still running):
+ *     V_0 = B;  V_0 = (-1) A X + 1 V_0  by the handle's launch_axpby
+ *     bb = dot(B, B) (once);  rr = dot(V_0, V_0);  est = rr
+ *     status 2 if rr or bb is not finite, else converged if rr <= tol2 * bb,
+ *     else running: beta = sqrt(rr);  g_0 = beta;  V_0 = V_0 / beta
+ *   STEP at position p = 0 .. m - 1 of a cycle, running columns:
+ *     W = A z(V_p)  by launch_multi (all k columns, the caller's opts)
+ *     a_i = dot(V_i, W), i = 0..p;  then W = W - a_i * V_i in increasing i
+ *     c_i = dot(V_i, W) of the new W;  then W = W - c_i * V_i likewise
+ *     h_i = a_i + c_i;  nn = dot(W, W);  h_{p+1} = sqrt(nn)
+ *     a non-finite h_i or nn: status 2, the step does not count
+ *     for i < p:  t = c_i * h_i + s_i * h_{i+1}
+ *                 h_{i+1} = c_i * h_{i+1} - s_i * h_i;  h_i = t
+ *     a = h_p;  b = h_{p+1};  d = sqrt(a * a + b * b)
+ *     d not finite or d == 0: status 2, the step does not count
+ *     c_p = a / d;  s_p = b / d;  r_ip = h_i (i < p);  r_pp = c_p * a + s_p * b
+ *     g_{p+1} = -(s_p * g_p);  g_p = c_p * g_p
+ *     iterations += 1;  est = g_{p+1} * g_{p+1}
+ *     est <= tol2 * bb: converged, else V_{p+1} = W / h_{p+1}
+ *   UPDATE after position m - 1 and once more when the call returns, for
+ *   every column with q > 0 counted steps of this cycle not yet in X:
+ *     for i = q - 1 .. 0:  s = 0.0;  s = s + r_il * y_l for l = i + 1 .. q - 1
+ *                          y_i = (g_i - s) / r_ii
+ *     U = y_0 * V_0;  U = U + y_i * V_i for i = 1 .. q - 1;  X = X + z(U)
+ *   after position m - 1 a column still running restarts (restarts += 1) and
+ *   converges there on the true rr.  Columns still running at the end:
+ *   status 1.  rr is then dot(R, R) of R = B - A X by launch_axpby, for every
+ *   column.
+ *
+ * h_{p+1} == 0 with a != 0 gets no rule of its own: s_p = 0, est = 0 and the
+ * column converges.  A matrix whose stored values are all 0.0 gives d == 0 in
+ * the first step: status 2, 0 iterations, X untouched.
+ *
+ * A column that left the running state receives exactly one more write to X:
+ * the update of the steps it completed in its last cycle, at the next restart
+ * boundary or when the call returns, whichever comes first, with the same
+ * bits.  Nothing else of it is written.  So the results do not depend on k,
+ * check_every, on who owns the work buffer, on waves_per_block, on the other
+ * columns or on how the basis is cut into launches.  d_minv of all 1.0, a plan
+ * of the identity, and a plan of a diagonal of powers of two against
+ * d_minv = 1 / d give the same bits, by arithmetic.
+ */
+typedef struct spmv_gmres_info {
+    int status;      /* 0 converged, 1 maxit reached, 2 breakdown */
+    int iterations;  /* Arnoldi steps whose update reached X */
+    int restarts;    /* cycles begun after the first */
+    int reserved;
+    double rr;       /* true r.r, r = b - A x, computed once when the call returns */
+    double est;      /* last squared residual estimate of the recurrence */
+    double bb;       /* b.b */
+} spmv_gmres_info;
+
+int64_t spmv_gmres_work_bytes(int M, int k, int restart); /* -EINVAL: M < 0, k outside 1..8, restart outside 1..64 */
+int spmv_csr_gmres(const spmv_csr_dev *A, const spmv_launch_opts *opts, int k,
+                   const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                   const double *d_minv, int restart, double tol, int maxit,
+                   int check_every, void *d_work, size_t work_bytes,
+                   spmv_gmres_info *info, void *stream);
+int spmv_hll_gmres(const spmv_hll_dev *H, const spmv_launch_opts *opts, int k,
+                   const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                   const double *d_minv, int restart, double tol, int maxit,
+                   int check_every, void *d_work, size_t work_bytes,
+                   spmv_gmres_info *info, void *stream);
+int spmv_csr_gmres_trsv(const spmv_csr_dev *A, const spmv_launch_opts *opts,
+                        int k, const double *d_B, int64_t ldb, double *d_X,
+                        int64_t ldx, const spmv_trsv_plan *first,
+                        const spmv_trsv_plan *second, const double *d_scale,
+                        int restart, double tol, int maxit, int check_every,
+                        void *d_work, size_t work_bytes,
+                        spmv_gmres_info *info, void *stream);
+int spmv_hll_gmres_trsv(const spmv_hll_dev *H, const spmv_launch_opts *opts,
+                        int k, const double *d_B, int64_t ldb, double *d_X,
+                        int64_t ldx, const spmv_trsv_plan *first,
+                        const spmv_trsv_plan *second, const double *d_scale,
+                        int restart, double tol, int maxit, int check_every,
+                        void *d_work, size_t work_bytes,
+                        spmv_gmres_info *info, void *stream);
+
+/*
  * CGLS on the device for rectangular least squares (added after 0.7;
  * spmv_version() is unchanged, detect it by the symbol): per column,
  *   min ||A x - b||^2 + damp^2 ||x||^2,

@@ -418,6 +418,14 @@ class MinresInfo(C.Structure):
                 ("bb", C.c_double)]
 
 
+class GmresInfo(C.Structure):
+    """spmv_gmres_info (include/spmv_engine.h): one column of a gmres()
+    solve"""
+    _fields_ = [("status", C.c_int), ("iterations", C.c_int),
+                ("restarts", C.c_int), ("reserved", C.c_int),
+                ("rr", C.c_double), ("est", C.c_double), ("bb", C.c_double)]
+
+
 class Ic0Info(C.Structure):
     """spmv_ic0_info (include/spmv_engine.h): one CsrDevice.ic0()"""
     _fields_ = [("levels", C.c_int), ("launches", C.c_int),
@@ -614,6 +622,7 @@ _sig("spmv_bicgstab_work_bytes", C.c_int64, C.c_int, C.c_int)
 _sig("spmv_bicgstab_trsv_work_bytes", C.c_int64, C.c_int, C.c_int)
 _sig("spmv_cgls_work_bytes", C.c_int64, C.c_int, C.c_int, C.c_int)
 _sig("spmv_minres_work_bytes", C.c_int64, C.c_int, C.c_int)
+_sig("spmv_gmres_work_bytes", C.c_int64, C.c_int, C.c_int, C.c_int)
 _sig("spmv_debug_sqrt", C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
      C.c_void_p)
 # spmv_csr_<name> and spmv_hll_<name>: the same argument types
@@ -682,6 +691,15 @@ _TWINS = (
      C.c_void_p, C.POINTER(LaunchOpts), C.c_int, C.c_void_p, C.c_int64,
      C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_int, C.c_int,
      C.c_void_p, C.c_size_t, C.POINTER(MinresInfo), C.c_void_p),
+    ("gmres", C.c_int,
+     C.c_void_p, C.POINTER(LaunchOpts), C.c_int, C.c_void_p, C.c_int64,
+     C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int,
+     C.c_void_p, C.c_size_t, C.POINTER(GmresInfo), C.c_void_p),
+    ("gmres_trsv", C.c_int,
+     C.c_void_p, C.POINTER(LaunchOpts), C.c_int, C.c_void_p, C.c_int64,
+     C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+     C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+     C.POINTER(GmresInfo), C.c_void_p),
     ("diag", C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p),
     ("time", C.c_int,
      C.c_void_p, C.c_int, C.POINTER(LaunchOpts), C.c_void_p, C.c_void_p,
@@ -820,6 +838,21 @@ def minres_work_bytes(M, k):
     needs: a base that depends on neither, and six vectors of 8 k M bytes"""
     return _check(_lib.spmv_minres_work_bytes(int(M), int(k)),
                   "spmv_minres_work_bytes")
+
+
+#: one column of a gmres() solve
+GmresResult = collections.namedtuple("GmresResult",
+                                     "status iterations restarts rr est bb")
+#: the longest cycle of gmres() (GM_MAXM)
+GMRES_MAX_RESTART = 64
+
+
+def gmres_work_bytes(M, k, restart):
+    """bytes of device memory one gmres() or gmres_trsv() solve of k systems
+    with M rows and cycles of `restart` steps needs: a base that depends on
+    restart alone, and restart + 3 vectors of 8 k M bytes (the basis, W, Z)"""
+    return _check(_lib.spmv_gmres_work_bytes(int(M), int(k), int(restart)),
+                  "spmv_gmres_work_bytes")
 
 
 #: CsrDevice.symmetry()
@@ -1675,6 +1708,59 @@ class _Device:
         return self._cg("minres", d_B, d_X, (d_minv,), k, tol, maxit,
                         check_every, ldb, ldx, work, waves_per_block, group,
                         stream, MinresInfo, MinresResult)
+
+    def gmres(self, d_B, d_X, k=1, restart=30, d_minv=None, tol=1e-8,
+              maxit=1000, check_every=0, ldb=0, ldx=0, work=None,
+              waves_per_block=0, group=0, stream=None):
+        """Restarted GMRES(restart) for A X = B on the device, A square and
+        otherwise arbitrary: one product and one preconditioner apply per
+        Arnoldi step, a residual estimate that never grows within a cycle,
+        and no breakdown other than a singular matrix or a non-finite number.
+        restart = 1..64 steps per cycle; maxit counts steps over all cycles.
+        k, the layout, d_X / d_B, d_minv (a right diagonal preconditioner or
+        None), the blocking, check_every and `work` (at least
+        gmres_work_bytes(M, k, restart) bytes) as bicgstab().  Stops a column
+        when est <= tol^2 b.b -- est the recurrence's squared residual
+        estimate; at a restart the true r.r -- after maxit steps, or on a
+        breakdown.  rr is the true r.r of b - A x, computed once at the end.
+        -> [GmresResult(status, iterations, restarts, rr, est, bb)] * k"""
+        restart = self._restart(restart)
+        return self._cg("gmres", d_B, d_X, (d_minv, restart), k, tol, maxit,
+                        check_every, ldb, ldx, work, waves_per_block, group,
+                        stream, GmresInfo, GmresResult)
+
+    def gmres_trsv(self, d_B, d_X, first, second=None, d_scale=None, k=1,
+                   restart=30, tol=1e-8, maxit=1000, check_every=0, ldb=0,
+                   ldx=0, work=None, waves_per_block=0, group=0, stream=None):
+        """gmres() with a right preconditioner made by triangular plans, as
+        bicgstab_trsv(): ILU(0) is (LU.trsv_analyse("lower", unit=True),
+        LU.trsv_analyse("upper")) of LU = A.ilu0()[0]; symmetric Gauss-Seidel
+        is gmres_trsv(d_B, d_X, *A.sgs().args).  Each step adds the launches
+        of the plans once (TrsvPlan.info["launches"]), where bicgstab_trsv()
+        adds them twice per iteration.  `work`: at least
+        gmres_work_bytes(M, k, restart) bytes.
+        -> [GmresResult(status, iterations, restarts, rr, est, bb)] * k"""
+        if not isinstance(first, TrsvPlan) or \
+                not (second is None or isinstance(second, TrsvPlan)):
+            raise ValueError("gmres_trsv: first is a TrsvPlan, second a "
+                             "TrsvPlan or None")
+        if d_scale is not None and second is None:
+            raise ValueError("gmres_trsv: d_scale scales the input of the "
+                             "second plan, and there is none")
+        restart = self._restart(restart)
+        return self._cg("gmres_trsv", d_B, d_X,
+                        (first.h, second.h if second is not None else None,
+                         d_scale, restart), k, tol, maxit, check_every, ldb,
+                        ldx, work, waves_per_block, group, stream, GmresInfo,
+                        GmresResult)
+
+    @staticmethod
+    def _restart(restart):
+        restart = int(restart)
+        if not 1 <= restart <= GMRES_MAX_RESTART:
+            raise ValueError("restart=%r: 1..%d steps per cycle"
+                             % (restart, GMRES_MAX_RESTART))
+        return restart
 
     def _cg(self, name, d_B, d_X, minv, k, tol, maxit, check_every, ldb, ldx,
             work, waves_per_block, group, stream, record=CgInfo,

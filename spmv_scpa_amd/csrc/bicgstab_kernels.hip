@@ -439,17 +439,6 @@ int64_t bicgstab_work_bytes(int M, int k, int trsv) {
 #define BI_LAUNCH(kernel, pre, k, M, s, ...)                                  \
     CG_K_SWITCH(k, BI_LAUNCH_K, kernel, pre, M, s, __VA_ARGS__)
 
-/* Z = z(U) of spmv_*_bicgstab_trsv, all k columns (a frozen column's Z
- * reaches nothing: every consumer is predicated); a refused plan solve is the
- * code that ends the batch */
-static int bi_apply(const cg_plans &pl, int k, const double *U, double *Z,
-                    hipStream_t s) {
-    int rc = trsv_solve_dev(pl.first, pl.waves, k, U, k, Z, k, NULL, s);
-    if (!rc && pl.second)
-        rc = trsv_solve_dev(pl.second, pl.waves, k, Z, k, Z, k, pl.scale, s);
-    return rc;
-}
-
 /* The arguments were checked by the caller (engine.hip, bicgstab /
  * bicgstab_trsv): k in 1..8, ldb, ldx >= k, M == N > 0, tol >= 0, maxit >= 0,
  * check_every > 0, live plans of M rows.  plans != NULL (and minv NULL): the

@@ -1,11 +1,12 @@
 /*
  * cg_common.h -- what the device-resident solvers share (cg_kernels.hip:
  * spmv_*_cg / spmv_*_pcg; bicgstab_kernels.hip: spmv_*_bicgstab;
- * cgls_kernels.hip: spmv_*_cgls; minres_kernels.hip: spmv_*_minres): the tile
- * of a vector kernel, the two halving trees of the dot order, the finite test,
- * the frozen-column test (cg_running) and the launch macros.  One text,
- * included by these files; the two kernels every solver launches (k_cg_copy,
- * k_cg_dot) stay in cg_kernels.hip and are reached through cg_launch_copy /
+ * cgls_kernels.hip: spmv_*_cgls; minres_kernels.hip: spmv_*_minres;
+ * gmres_kernels.hip: spmv_*_gmres): the tile of a vector kernel, the two
+ * halving trees of the dot order, the finite test, the square root (mr_sqrt),
+ * the frozen-column test (cg_running), the launch macros and the plan apply of
+ * the _trsv solvers (bi_apply).  One text, included by these files; the two
+ * kernels every solver launches (k_cg_copy, k_cg_dot) stay in cg_kernels.hip and are reached through cg_launch_copy /
  * cg_launch_dot (hip_common.h), so they exist once in the library.  The host
  * side the solvers share is included from here too: the work buffer
  * (solver_work.h, through hip_common.h) and the refusals, the own buffer and
@@ -120,6 +121,13 @@ __device__ __forceinline__ bool cg_finite(double v) {
     return __builtin_fabs(v) <= 1.7976931348623157e308; /* false for NaN */
 }
 
+/* The one square root of the library: correctly rounded (the v_rsq_f64
+ * refinement with two residual corrections the compiler expands
+ * __builtin_sqrt to; spmv_debug_sqrt checks it against the host's) */
+__device__ __forceinline__ double mr_sqrt(double a) {
+    return __builtin_sqrt(a);
+}
+
 /* ---- launches ---- */
 
 /* workgroups whose slots hold an element */
@@ -162,5 +170,16 @@ static inline unsigned cg_grid(int M) {
 /* kernel(...) in one workgroup on stream s: every finalising kernel */
 #define CG_FINAL(kernel, s, ...)                                              \
     hipLaunchKernelGGL(kernel, dim3(1), dim3(CG_FINAL_T), 0, s, __VA_ARGS__)
+
+/* Z = z(U) of spmv_*_bicgstab_trsv and spmv_*_gmres_trsv, all k columns (a
+ * frozen column's Z reaches nothing: every consumer is predicated); a refused
+ * plan solve is the code that ends the batch */
+static inline int bi_apply(const cg_plans &pl, int k, const double *U,
+                           double *Z, hipStream_t s) {
+    int rc = trsv_solve_dev(pl.first, pl.waves, k, U, k, Z, k, NULL, s);
+    if (!rc && pl.second)
+        rc = trsv_solve_dev(pl.second, pl.waves, k, Z, k, Z, k, pl.scale, s);
+    return rc;
+}
 
 #endif /* SPMV_CG_COMMON_H */

@@ -2335,6 +2335,50 @@ static int bicgstab_trsv(const D *d, const spmv_launch_opts *opts, int k,
                           (hipStream_t)stream);
 }
 
+/* GMRES(restart) (gmres_kernels.hip): bicgstab's checks, then restart in
+ * 1..GM_MAXM; d_minv may be NULL (no preconditioner) */
+template <typename D>
+static int gmres(const D *d, const spmv_launch_opts *opts, int k,
+                 const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                 const double *d_minv, int restart, double tol, int maxit,
+                 int check_every, void *d_work, size_t work_bytes,
+                 spmv_gmres_info *info, void *stream) {
+    const int rc = solver_check(
+        d, opts, k, d_B, &ldb, d_X, &ldx, tol, maxit, &check_every, info,
+        [&] { return restart < 1 || restart > GM_MAXM ? -EINVAL : 0; });
+    if (rc)
+        return rc < 0 ? rc : 0;
+    const cg_matrix A = cg_matrix_of(d, opts);
+    return gmres_solve(&A, k, d_B, ldb, d_X, ldx, d_minv, NULL, restart, tol,
+                       maxit, check_every, d_work, work_bytes, info,
+                       (hipStream_t)stream);
+}
+
+/* spmv_*_gmres_trsv: gmres's checks, then the plans' as cg_trsv's */
+template <typename D>
+static int gmres_trsv(const D *d, const spmv_launch_opts *opts, int k,
+                      const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                      const spmv_trsv_plan *first,
+                      const spmv_trsv_plan *second, const double *d_scale,
+                      int restart, double tol, int maxit, int check_every,
+                      void *d_work, size_t work_bytes, spmv_gmres_info *info,
+                      void *stream) {
+    const int rc = solver_check(
+        d, opts, k, d_B, &ldb, d_X, &ldx, tol, maxit, &check_every, info, [&] {
+            return restart < 1 || restart > GM_MAXM
+                       ? -EINVAL
+                       : plans_check(d->M, first, second, d_scale);
+        });
+    if (rc)
+        return rc < 0 ? rc : 0;
+    const cg_matrix A = cg_matrix_of(d, opts);
+    const cg_plans pl = {first, second, d_scale,
+                         opts ? opts->waves_per_block : 0};
+    return gmres_solve(&A, k, d_B, ldb, d_X, ldx, NULL, &pl, restart, tol,
+                       maxit, check_every, d_work, work_bytes, info,
+                       (hipStream_t)stream);
+}
+
 /* CGLS (cgls_kernels.hip): both handles go through cg's checks, A first, with
  * the one opts; that AT is the transpose of A is not checked, only its shape */
 template <typename D>
@@ -3039,6 +3083,25 @@ static int copy_tune_log(const D *d, char *buf, size_t len) {
                              d_scale, tol, maxit, check_every, d_work,         \
                              work_bytes, info, stream);                        \
     }                                                                          \
+    int spmv_##fmt##_gmres(const D *d, const spmv_launch_opts *opts, int k,    \
+                           const double *d_B, int64_t ldb, double *d_X,        \
+                           int64_t ldx, const double *d_minv, int restart,     \
+                           double tol, int maxit, int check_every,             \
+                           void *d_work, size_t work_bytes,                    \
+                           spmv_gmres_info *info, void *stream) {              \
+        return gmres(d, opts, k, d_B, ldb, d_X, ldx, d_minv, restart, tol,     \
+                     maxit, check_every, d_work, work_bytes, info, stream);    \
+    }                                                                          \
+    int spmv_##fmt##_gmres_trsv(                                               \
+        const D *d, const spmv_launch_opts *opts, int k, const double *d_B,    \
+        int64_t ldb, double *d_X, int64_t ldx, const spmv_trsv_plan *first,    \
+        const spmv_trsv_plan *second, const double *d_scale, int restart,      \
+        double tol, int maxit, int check_every, void *d_work,                  \
+        size_t work_bytes, spmv_gmres_info *info, void *stream) {              \
+        return gmres_trsv(d, opts, k, d_B, ldb, d_X, ldx, first, second,       \
+                          d_scale, restart, tol, maxit, check_every, d_work,   \
+                          work_bytes, info, stream);                           \
+    }                                                                          \
     int spmv_##fmt##_cgls(const D *d, const D *dt,                             \
                           const spmv_launch_opts *opts, int k,                 \
                           const double *d_B, int64_t ldb, double *d_X,         \
@@ -3139,6 +3202,9 @@ int64_t spmv_bicgstab_work_bytes(int M, int k) {
 }
 int64_t spmv_bicgstab_trsv_work_bytes(int M, int k) {
     return bicgstab_work_bytes(M, k, 1);
+}
+int64_t spmv_gmres_work_bytes(int M, int k, int restart) {
+    return gmres_work_bytes(M, k, restart);
 }
 int64_t spmv_cgls_work_bytes(int M, int N, int k) {
     return cgls_work_bytes(M, N, k);

@@ -596,6 +596,19 @@ int minres_solve(const cg_matrix *A, int k, const double *B, int64_t ldb,
 int minres_debug_sqrt(const double *d_in, double *d_out, int64_t n,
                       hipStream_t s);
 
+/*
+ * Restarted GMRES(m) for nonsymmetric A (gmres_kernels.hip; spmv_*_gmres): the
+ * matrix, the dot and the host loop of cg, the preconditioner modes of
+ * bicgstab (minv, or plans with minv NULL: spmv_*_gmres_trsv), a state of its
+ * own (gmres_work, solver_work.h; the dense arithmetic is gmres_small.h).
+ */
+int64_t gmres_work_bytes(int M, int k, int restart);
+int gmres_solve(const cg_matrix *A, int k, const double *B, int64_t ldb,
+                double *X, int64_t ldx, const double *minv,
+                const cg_plans *plans, int restart, double tol, int maxit,
+                int check_every, void *d_work, size_t work_bytes,
+                spmv_gmres_info *info, hipStream_t s);
+
 /* out[r] = the sum of row r's stored entries in column r, or 1 / that sum,
  * r < min(M, N) (diag_kernels.hip; spmv_*_diag); the caller has checked the
  * handle */

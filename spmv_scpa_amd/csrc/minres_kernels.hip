@@ -78,13 +78,6 @@ struct mr_state {
 };
 static_assert(sizeof(mr_state) <= MR_STATE_BYTES, "state block");
 
-/* The one square root of the library: correctly rounded (the v_rsq_f64
- * refinement with two residual corrections the compiler expands
- * __builtin_sqrt to; spmv_debug_sqrt checks it against the host's) */
-__device__ __forceinline__ double mr_sqrt(double a) {
-    return __builtin_sqrt(a);
-}
-
 /* z(u) of one element: rn(minv_i * u), or u itself */
 template <bool PRE>
 __device__ __forceinline__ double mr_z(double d, double u) {

@@ -1,6 +1,7 @@
 /*
  * solver_work.h -- the work buffer of the device-resident solvers
- * (cg_kernels.hip, bicgstab_kernels.hip, cgls_kernels.hip, minres_kernels.hip),
+ * (cg_kernels.hip, bicgstab_kernels.hip, cgls_kernels.hip, minres_kernels.hip,
+ * gmres_kernels.hip),
  * described ONCE: the size a caller is told (*_work_bytes) and the pointers a
  * solve cuts the buffer into come from the same description, so a vector added
  * to one cannot be forgotten in the other.
@@ -18,12 +19,15 @@
 #include <errno.h>
 #include <stdint.h>
 
+#include "gmres_small.h"
+
 #define CG_MAXK 8 /* right-hand sides of one solve */
 /* workgroups of a dot: part of the result contract (hip_common.h, CG_T) */
 #define CG_NWG 1024
 #define CG_PART_BYTES (CG_NWG * 8 * 8) /* CG_NWG workgroup sums of 8 columns */
 #define CG_STATE_BYTES 512  /* cg_state, bi_state, ls_state */
 #define MR_STATE_BYTES 2048 /* mr_state */
+#define GM_HEAD_BYTES 512   /* gm_state: the part of GMRES' state read back */
 
 #define SOLVER_WORK_MAXV 7
 
@@ -88,6 +92,24 @@ static inline solver_work cgls_work(int M, int N, int k) {
  * directions (the pair is zeroed by one memset: neighbours) */
 static inline solver_work minres_work(int M, int k) {
     return solver_work{k, MR_STATE_BYTES, 3, 6, {M, M, M, M, M, M}};
+}
+
+/* spmv_*_gmres and spmv_*_gmres_trsv, restart in 1..GM_MAXM (the caller's
+ * check; anything else gives a buffer solver_work_bytes refuses): the state is
+ * gm_state and, behind it, the blocks of gmres_small.h for 8 columns, so it
+ * depends on restart alone; one set of partial sums per basis vector (bb, rr
+ * and nn pass through sets 0 and 1);  the basis as ONE vector of
+ * (restart + 1) M rows -- basis vector i starts at element (size_t)i * M * k --
+ * then W and Z */
+static inline solver_work gmres_work(int M, int k, int restart) {
+    if (restart < 1 || restart > GM_MAXM)
+        return solver_work{k, GM_HEAD_BYTES, 0, 1, {-1}};
+    return solver_work{
+        k,
+        GM_HEAD_BYTES + 8 * CG_MAXK * (int64_t)gm_col_doubles(restart),
+        restart + 1,
+        3,
+        {(int64_t)(restart + 1) * M, M, M}};
 }
 
 #endif /* SPMV_SOLVER_WORK_H */
