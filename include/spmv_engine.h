@@ -404,6 +404,65 @@ int spmv_trsv_solve(const spmv_trsv_plan *P, const spmv_launch_opts *opts, int k
                     const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
                     const double *d_scale, void *stream);
 /*
+ * SWEEP PLANS: the triangular solve by a fixed number of Jacobi sweeps (added
+ * after 0.7; detect it by the symbol).  With T = D + S (S the strict part),
+ *     x(1) = D^-1 b,    x(m) = D^-1 (b - S x(m-1)),  m = 2 .. sweeps,
+ * X = x(sweeps): an APPROXIMATE solve (Anzt, Chow, Dongarra 2015) whose cost
+ * is `sweeps` launches over all rows whatever the ordering and the depth of
+ * the dependency graph.  S is nilpotent, so sweeps >= levels of the exact plan
+ * of the same triangle IS the exact solve, to the bit (below).
+ *
+ * spmv_csr_trsv_analyse_sweeps: A, uplo, unit as spmv_csr_trsv_analyse (f64 or
+ * f32 values, unsorted rows, duplicates, explicit zeros, both triangles
+ * stored).  sweeps in 1..4096; kmax in 1..8, the most right-hand sides one
+ * solve of this plan may take.  The plan owns the strict entries IN ROW ORDER
+ * -- order is the identity and rowptr / ja / as / diag are defined as above
+ * with that order -- and min(sweeps - 1, 2) scratch vectors of 8 * kmax * M
+ * bytes.  No levels are computed: no launch or read-back per level, and a deep
+ * chain (a tridiagonal matrix) gets a usable plan, -E2BIG cannot occur.
+ * Errors, in this order: NULL A or out, uplo / unit outside 0..1, sweeps
+ * outside 1..4096, kmax outside 1..8 -EINVAL; then those of
+ * spmv_csr_trsv_analyse from "no device" on.  Nothing is created on an error;
+ * M == 0 gives a valid plan.  The plan is a spmv_trsv_plan in every respect:
+ * live handle, generation, spmv_trsv_release*.
+ *
+ * spmv_trsv_sweeps: sweeps and kmax of a plan, 0 and 0 for an exact plan.
+ * spmv_trsv_info of a sweep plan: levels = 1 (0 for M == 0), widest_level = M,
+ * launches = sweeps, bytes with the scratch.  spmv_trsv_download: level all 0,
+ * order the identity, level_ptr = [0, M].
+ *
+ * spmv_trsv_solve of a sweep plan: the same arguments and checks, then k >
+ * kmax -EINVAL.  Asynchronous and capturable, the launches a function of the
+ * plan alone; d_X == d_B with ldx == ldb is allowed.  A SOLVE WRITES THE
+ * PLAN'S SCRATCH: two solves of one sweep plan must not overlap in time.  On
+ * one stream, or ordered by events, is fine; concurrent use of one sweep plan
+ * (two streams, two threads, two graphs in flight) is undefined.  Exact plans
+ * have no such state.
+ *
+ * THE RESULT IS DEFINED TO THE BIT.  With row(i; Xin) the row function of
+ * spmv_trsv_solve above -- G slots over the strict entries in stored order,
+ * the halving tree, rhs, rn(rhs - s), the division unless unit, no fused
+ * multiply-add -- and the gathers X[c_e, j] taken from Xin:
+ *     x(1)[i] = row(i) with s = +0.0 (the matrix is not read)
+ *     x(m)[i] = row(i; x(m-1)),  m = 2 .. sweeps
+ * A sweep reads only what the launch before it wrote: no waiting between
+ * workgroups, no atomics.  X depends on neither k, waves_per_block, kmax,
+ * in-place use, nor the run.  A row of level l of the exact plan is final
+ * after sweep l + 1, so sweeps >= levels gives the exact solve's bits for any
+ * B, NaN and inf included; a NaN in row r of B reaches exactly the rows within
+ * sweeps - 1 dependency steps of r; a zero diagonal is plain arithmetic.
+ *
+ * Every solver that takes plans takes sweep plans unchanged, with one more
+ * refusal after "a plan whose M is not A's": a sweep plan with kmax < k is
+ * -EINVAL.  For spmv_*_pcg_trsv give both plans THE SAME sweeps: then z(r) =
+ * B^T B r (IC) or B^T D B r (SGS) with B = P_s(D^-1 S) D^-1, symmetric positive
+ * definite.  Unequal counts make the preconditioner nonsymmetric and CG may
+ * end with its breakdown status; this is not checked.
+ */
+int spmv_csr_trsv_analyse_sweeps(const spmv_csr_dev *A, int uplo, int unit,
+                                 int sweeps, int kmax, spmv_trsv_plan **out);
+int spmv_trsv_sweeps(const spmv_trsv_plan *P, int *sweeps, int *kmax);
+/*
  * Zero-fill incomplete Cholesky A ~ L L^T on the device (added after 0.7;
  * detect it by the symbol).  A: a square CSR handle with f64 values.  Only the
  * entries with column <= row are read: the upper triangle may be present,

@@ -577,6 +577,9 @@ _sig("spmv_csr_symmetry", C.c_int, C.c_void_p, _ip)
 _i64p = C.POINTER(C.c_int64)
 _sig("spmv_csr_trsv_analyse", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
      C.POINTER(C.c_void_p))
+_sig("spmv_csr_trsv_analyse_sweeps", C.c_int, C.c_void_p, C.c_int, C.c_int,
+     C.c_int, C.c_int, C.POINTER(C.c_void_p))
+_sig("spmv_trsv_sweeps", C.c_int, C.c_void_p, _ip, _ip)
 _sig("spmv_trsv_info", C.c_int, C.c_void_p, _ip, _ip, _i64p, _ip, _i64p, _ip,
      _i64p)
 _sig("spmv_trsv_download", C.c_int, C.c_void_p, _ip, _ip, _ip, _ip, _ip, _dp,
@@ -1978,19 +1981,36 @@ class CsrDevice(_Device):
                "spmv_csr_symmetry")
         return out.value
 
-    def trsv_analyse(self, uplo="lower", unit=False, max_levels=0):
+    def trsv_analyse(self, uplo="lower", unit=False, max_levels=0, sweeps=0,
+                     kmax=8):
         """a TrsvPlan for T x = b with T the `uplo` triangle of this (square)
         handle: the level schedule and a copy of the strict entries, built on
         the device and defined to the byte (spmv_engine.h).  unit=True: unit
         diagonal.  More than max_levels levels (0: 1 << 20) is
-        OSError(E2BIG).  This handle stays valid and may be released"""
+        OSError(E2BIG).  sweeps > 0 (up to 4096): a SWEEP PLAN instead -- the
+        solve is that many Jacobi sweeps, one launch each, approximate below
+        the depth of the triangle and exact to the bit from there on; no
+        levels are computed, max_levels is ignored, and a solve takes at most
+        kmax (1..8) right-hand sides.  Two solves of one sweep plan must not
+        overlap in time (they share its scratch).  This handle stays valid
+        and may be released"""
         if uplo not in ("lower", "upper"):
             raise ValueError("uplo=%r: \"lower\" or \"upper\"" % (uplo,))
-        max_levels = int(max_levels)
+        max_levels, sweeps, kmax = int(max_levels), int(sweeps), int(kmax)
         if max_levels < 0:
             raise ValueError("max_levels=%d: 0 (the default) or more"
                              % max_levels)
+        if not 0 <= sweeps <= 4096:
+            raise ValueError("sweeps=%d: 0 (an exact plan) or 1..4096"
+                             % sweeps)
+        if not 1 <= kmax <= 8:
+            raise ValueError("kmax=%d: 1..8 right-hand sides" % kmax)
         h = C.c_void_p()
+        if sweeps:
+            _check(_lib.spmv_csr_trsv_analyse_sweeps(
+                self.h, int(uplo == "upper"), int(bool(unit)), sweeps, kmax,
+                C.byref(h)), "spmv_csr_trsv_analyse_sweeps")
+            return TrsvPlan(h)
         _check(_lib.spmv_csr_trsv_analyse(self.h, int(uplo == "upper"),
                                           int(bool(unit)), max_levels,
                                           C.byref(h)),
@@ -2074,10 +2094,12 @@ class CsrDevice(_Device):
                "spmv_csr_permute")
         return CsrDevice(h)
 
-    def sgs(self, max_levels=0):
+    def sgs(self, max_levels=0, sweeps=0, kmax=8):
         """an SgsPreconditioner of this (square) handle: its lower and upper
-        TrsvPlan and a DevBuffer with diag(A); release() frees the three"""
-        return SgsPreconditioner(self, max_levels)
+        TrsvPlan and a DevBuffer with diag(A); release() frees the three.
+        sweeps > 0: both are sweep plans of that many sweeps (trsv_analyse;
+        the same count in both keeps the preconditioner symmetric)"""
+        return SgsPreconditioner(self, max_levels, sweeps, kmax)
 
     @classmethod
     def generate(cls, kind, M, N, K, W, row0=0, seed=42):
@@ -2124,8 +2146,9 @@ class CsrDevice(_Device):
 
 
 class TrsvPlan:
-    """The level schedule of a sparse triangular solve, resident in HBM
-    (spmv_engine.h, spmv_trsv_plan; CsrDevice.trsv_analyse makes one)."""
+    """The level schedule of a sparse triangular solve, or the strict
+    triangle and scratch of a sweep plan, resident in HBM (spmv_engine.h,
+    spmv_trsv_plan; CsrDevice.trsv_analyse makes one)."""
 
     h = None
     _RANK = 1
@@ -2157,6 +2180,23 @@ class TrsvPlan:
         return dict(M=M.value, levels=lv.value, entries=en.value,
                     widest_level=wd.value, zero_diag=zd.value,
                     launches=ln.value, bytes=by.value)
+
+    def _sweeps(self):
+        s, k = C.c_int(), C.c_int()
+        _check(_lib.spmv_trsv_sweeps(self.h, C.byref(s), C.byref(k)),
+               "spmv_trsv_sweeps")
+        return s.value, k.value
+
+    @property
+    def sweeps(self):
+        """Jacobi sweeps of one solve of a sweep plan; 0 for an exact plan"""
+        return self._sweeps()[0]
+
+    @property
+    def kmax(self):
+        """the most right-hand sides a solve of a sweep plan takes; 0 for an
+        exact plan (which takes 1..8)"""
+        return self._sweeps()[1]
 
     def download(self):
         """dict(level, order, level_ptr, rowptr, ja: int32; as (the stored
@@ -2296,10 +2336,12 @@ class SgsPreconditioner:
 
     lower = upper = diag = None
 
-    def __init__(self, A, max_levels=0):
+    def __init__(self, A, max_levels=0, sweeps=0, kmax=8):
         try:
-            self.lower = A.trsv_analyse("lower", max_levels=max_levels)
-            self.upper = A.trsv_analyse("upper", max_levels=max_levels)
+            self.lower = A.trsv_analyse("lower", max_levels=max_levels,
+                                        sweeps=sweeps, kmax=kmax)
+            self.upper = A.trsv_analyse("upper", max_levels=max_levels,
+                                        sweeps=sweeps, kmax=kmax)
             self.diag = DevBuffer(max(A.M, 1) * 8)
             A.diag(self.diag.ptr)
             stream_sync()

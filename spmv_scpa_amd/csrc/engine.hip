@@ -1251,11 +1251,19 @@ void spmv_trsv_release_checked(spmv_trsv_plan *P, uint64_t generation) {
     free(P);
 }
 
-int spmv_csr_trsv_analyse(const spmv_csr_dev *A, int uplo, int unit,
-                          int max_levels, spmv_trsv_plan **out) {
-    if (!A || !out || uplo < 0 || uplo > 1 || unit < 0 || unit > 1 ||
-        max_levels < 0)
-        return -EINVAL;
+/* NULL -> -EINVAL; not a live plan -> -EBADF, or -ENODEV without a device */
+#define PLAN_OK(P)                                                            \
+    do {                                                                      \
+        if (!(P))                                                             \
+            return -EINVAL;                                                   \
+        if (!live_has(P))                                                     \
+            return spmv_device_count() == 0 ? -ENODEV : -EBADF;               \
+    } while (0)
+
+/* both kinds of plan; the caller has checked the numbers */
+static int trsv_analyse(const spmv_csr_dev *A, int uplo, int unit,
+                        int max_levels, int sweeps, int kmax,
+                        spmv_trsv_plan **out) {
     *out = NULL;
     if (spmv_device_count() == 0)
         return -ENODEV; /* no handle can be live: the more useful answer */
@@ -1268,7 +1276,8 @@ int spmv_csr_trsv_analyse(const spmv_csr_dev *A, int uplo, int unit,
     if (!P)
         return -ENOMEM;
     const int rc = trsv_analyse_dev(
-        A, uplo, unit, max_levels ? max_levels : TRSV_DEFAULT_MAX_LEVELS, P, 0);
+        A, uplo, unit, max_levels ? max_levels : TRSV_DEFAULT_MAX_LEVELS, sweeps,
+        kmax, P, 0);
     if (rc) {
         trsv_free_dev(P);
         free(P);
@@ -1279,14 +1288,30 @@ int spmv_csr_trsv_analyse(const spmv_csr_dev *A, int uplo, int unit,
     return 0;
 }
 
-/* NULL -> -EINVAL; not a live plan -> -EBADF, or -ENODEV without a device */
-#define PLAN_OK(P)                                                            \
-    do {                                                                      \
-        if (!(P))                                                             \
-            return -EINVAL;                                                   \
-        if (!live_has(P))                                                     \
-            return spmv_device_count() == 0 ? -ENODEV : -EBADF;               \
-    } while (0)
+int spmv_csr_trsv_analyse(const spmv_csr_dev *A, int uplo, int unit,
+                          int max_levels, spmv_trsv_plan **out) {
+    if (!A || !out || uplo < 0 || uplo > 1 || unit < 0 || unit > 1 ||
+        max_levels < 0)
+        return -EINVAL;
+    return trsv_analyse(A, uplo, unit, max_levels, 0, 0, out);
+}
+
+int spmv_csr_trsv_analyse_sweeps(const spmv_csr_dev *A, int uplo, int unit,
+                                 int sweeps, int kmax, spmv_trsv_plan **out) {
+    if (!A || !out || uplo < 0 || uplo > 1 || unit < 0 || unit > 1 ||
+        sweeps < 1 || sweeps > TRSV_MAX_SWEEPS || kmax < 1 || kmax > TRSV_MAX_K)
+        return -EINVAL;
+    return trsv_analyse(A, uplo, unit, 0, sweeps, kmax, out);
+}
+
+int spmv_trsv_sweeps(const spmv_trsv_plan *P, int *sweeps, int *kmax) {
+    PLAN_OK(P);
+    if (sweeps)
+        *sweeps = P->sweeps;
+    if (kmax)
+        *kmax = P->kmax;
+    return 0;
+}
 
 int spmv_trsv_info(const spmv_trsv_plan *P, int *M, int *levels,
                    int64_t *entries, int *widest_level, int64_t *zero_diag,
@@ -1303,7 +1328,7 @@ int spmv_trsv_info(const spmv_trsv_plan *P, int *M, int *levels,
     if (zero_diag)
         *zero_diag = P->zero_diag;
     if (launches)
-        *launches = P->n_segs;
+        *launches = P->sweeps ? P->sweeps : P->n_segs;
     if (bytes)
         *bytes = P->bytes;
     return 0;
@@ -1372,6 +1397,8 @@ int spmv_trsv_solve(const spmv_trsv_plan *P, const spmv_launch_opts *opts, int k
             if (r)
                 return -EINVAL;
     }
+    if (P->sweeps && k > P->kmax)
+        return -EINVAL; /* the scratch of a sweep plan holds kmax columns */
     if (P->M == 0)
         return 0;
     return trsv_solve_dev(P, opts ? opts->waves_per_block : 0, k, d_B, ldb, d_X,
@@ -2263,14 +2290,18 @@ static int cg(const D *d, const spmv_launch_opts *opts, int k,
                     check_every, d_work, work_bytes, info, (hipStream_t)stream);
 }
 
-/* the checks spmv_*_pcg_trsv and spmv_*_bicgstab_trsv add for their plans */
-static int plans_check(int M, const spmv_trsv_plan *first,
+/* the checks spmv_*_pcg_trsv, spmv_*_bicgstab_trsv and spmv_*_gmres_trsv add
+ * for their plans */
+static int plans_check(int M, int k, const spmv_trsv_plan *first,
                        const spmv_trsv_plan *second, const double *d_scale) {
     if (!first || (d_scale && !second))
         return -EINVAL;
     if (!live_has(first) || (second && !live_has(second)))
         return -EBADF;
     if (first->M != M || (second && second->M != M))
+        return -EINVAL;
+    if ((first->sweeps && first->kmax < k) ||
+        (second && second->sweeps && second->kmax < k))
         return -EINVAL;
     return 0;
 }
@@ -2286,7 +2317,7 @@ static int cg_trsv(const D *d, const spmv_launch_opts *opts, int k,
                    spmv_cg_info *info, void *stream) {
     const int rc = solver_check(
         d, opts, k, d_B, &ldb, d_X, &ldx, tol, maxit, &check_every, info,
-        [&] { return plans_check(d->M, first, second, d_scale); });
+        [&] { return plans_check(d->M, k, first, second, d_scale); });
     if (rc)
         return rc < 0 ? rc : 0;
     const cg_matrix A = cg_matrix_of(d, opts);
@@ -2324,7 +2355,7 @@ static int bicgstab_trsv(const D *d, const spmv_launch_opts *opts, int k,
                          size_t work_bytes, spmv_cg_info *info, void *stream) {
     const int rc = solver_check(
         d, opts, k, d_B, &ldb, d_X, &ldx, tol, maxit, &check_every, info,
-        [&] { return plans_check(d->M, first, second, d_scale); });
+        [&] { return plans_check(d->M, k, first, second, d_scale); });
     if (rc)
         return rc < 0 ? rc : 0;
     const cg_matrix A = cg_matrix_of(d, opts);
@@ -2367,7 +2398,7 @@ static int gmres_trsv(const D *d, const spmv_launch_opts *opts, int k,
         d, opts, k, d_B, &ldb, d_X, &ldx, tol, maxit, &check_every, info, [&] {
             return restart < 1 || restart > GM_MAXM
                        ? -EINVAL
-                       : plans_check(d->M, first, second, d_scale);
+                       : plans_check(d->M, k, first, second, d_scale);
         });
     if (rc)
         return rc < 0 ? rc : 0;

@@ -650,13 +650,19 @@ struct spmv_trsv_plan {
     int *h_level_ptr;  /* host copy (malloc) */
     trsv_segment *segs; /* host, the launches of one solve (malloc) */
     int n_segs;
+    /* a sweep plan (spmv_csr_trsv_analyse_sweeps): sweeps > 0, one level, order
+     * the identity, no segs; a solve is `sweeps` launches (trsv_sweep_route) */
+    int sweeps, kmax;
+    double *sweep_buf[2]; /* trsv_sweep_scratch(sweeps) of kmax * M doubles */
 };
 /* fills *P (zeroed by the caller) from A's chosen triangle; blocks; on an error
- * the caller runs trsv_free_dev.  -E2BIG: more than max_levels levels */
+ * the caller runs trsv_free_dev.  -E2BIG: more than max_levels levels.
+ * sweeps > 0: a sweep plan for at most kmax right-hand sides, max_levels unread */
 int trsv_analyse_dev(const spmv_csr_dev *A, int uplo, int unit, int max_levels,
-                     spmv_trsv_plan *P, hipStream_t s);
+                     int sweeps, int kmax, spmv_trsv_plan *P, hipStream_t s);
 void trsv_free_dev(spmv_trsv_plan *P); /* the arrays, not P itself */
-/* the arguments were checked by the caller; waves 0 = each kernel's default */
+/* the arguments were checked by the caller (k <= kmax of a sweep plan too);
+ * waves 0 = each kernel's default */
 int trsv_solve_dev(const spmv_trsv_plan *P, int waves, int k, const double *B,
                    int64_t ldb, double *X, int64_t ldx, const double *scale,
                    hipStream_t s);

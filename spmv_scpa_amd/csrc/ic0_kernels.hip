@@ -213,7 +213,7 @@ int ic0_factor_dev(const spmv_csr_dev *A, double shift, int max_levels,
         goto fail;
     }
     /* the schedule, before anything is allocated for the result: -E2BIG */
-    rc = trsv_analyse_dev(A, 0, 0, max_levels, &P, s);
+    rc = trsv_analyse_dev(A, 0, 0, max_levels, 0, 0, &P, s);
     if (rc)
         goto fail;
     rc = alloc(M, M, lnz, 8, &L);

@@ -40,6 +40,11 @@
  * barrier (chain: producer and consumer share the CU's vector L1, workgroup
  * scope suffices).  X is read and written through one plain, non-restrict
  * pointer: vector loads only, never the scalar cache, never non-temporal.
+ *
+ * SWEEP PLANS (spmv_csr_trsv_analyse_sweeps): the analysis stops after
+ * k_trsv_fill -- the strict entries stay in row order, one level, no Kahn pass
+ * -- and the solve is `sweeps` launches over all rows, k_trsv_first and then
+ * k_trsv_sweep, by the route of trsv_plan.h (further down).
  */
 #include <algorithm>
 #include <stdlib.h>
@@ -237,17 +242,32 @@ void trsv_free_dev(spmv_trsv_plan *P) {
     (void)hipFree(P->ja);
     (void)hipFree(P->as);
     (void)hipFree(P->diag);
+    (void)hipFree(P->sweep_buf[0]);
+    (void)hipFree(P->sweep_buf[1]);
     free(P->h_level_ptr);
     free(P->segs);
     P->level = P->order = P->level_ptr = P->rowptr = P->ja = NULL;
     P->as = NULL;
     P->diag = NULL;
+    P->sweep_buf[0] = P->sweep_buf[1] = NULL;
     P->h_level_ptr = NULL;
     P->segs = NULL;
 }
 
+/* order[i] = i, level[i] = 0: the one level of a sweep plan */
+__global__ void __launch_bounds__(TV_T)
+k_trsv_natural(int M, int *__restrict__ order, int *__restrict__ level) {
+    const int64_t i = (int64_t)blockIdx.x * TV_T + threadIdx.x;
+    if (i >= M)
+        return;
+    order[i] = (int)i;
+    level[i] = 0;
+}
+
+/* sweeps > 0: a sweep plan (kmax right-hand sides at most) -- the strict
+ * entries stay in row order, there is no Kahn pass and max_levels is not read */
 int trsv_analyse_dev(const spmv_csr_dev *A, int uplo, int unit, int max_levels,
-                     spmv_trsv_plan *P, hipStream_t s) {
+                     int sweeps, int kmax, spmv_trsv_plan *P, hipStream_t s) {
     int rc = 0;
     const int M = A->M;
     trsv_scratch scratch;
@@ -265,6 +285,8 @@ int trsv_analyse_dev(const spmv_csr_dev *A, int uplo, int unit, int max_levels,
     P->unit = unit;
     P->value_bytes = A->value_bytes;
     P->device = A->device;
+    P->sweeps = sweeps;
+    P->kmax = sweeps ? kmax : 0;
     (void)hipGetLastError(); /* an earlier caller's unread error is not ours */
     HIP_TRY(trsv_keep(P, &P->level_ptr, 1)); /* grown below once levels is known */
     if (M == 0) {
@@ -318,15 +340,39 @@ int trsv_analyse_dev(const spmv_csr_dev *A, int uplo, int unit, int max_levels,
     HIP_TRY(trsv_keep(P, (char **)&P->as, z.sja, (size_t)A->value_bytes));
     HIP_TRY(scratch.get(&sja, z.sja));
     HIP_TRY(scratch.get(&spos, z.spos));
+    hipLaunchKernelGGL(k_trsv_fill, tv_grid(M), dim3(TV_T), 0, s, M, uplo,
+                       A->irp, A->ja, cnt, sja, spos);
+    HIP_TRY(hipGetLastError());
+    if (sweeps) { /* one level of M rows, the identity order, cnt is rowptr */
+        (void)hipFree(P->level_ptr);
+        P->level_ptr = NULL;
+        P->bytes -= (int64_t)sizeof(int);
+        HIP_TRY(trsv_keep(P, &P->level_ptr, 2));
+        for (int b = 0; b < trsv_sweep_scratch(sweeps); ++b)
+            HIP_TRY(trsv_keep(P, &P->sweep_buf[b], (int64_t)kmax * M));
+        P->h_level_ptr = (int *)malloc(2 * sizeof(int));
+        if (!P->h_level_ptr) {
+            rc = -ENOMEM;
+            goto fail;
+        }
+        P->h_level_ptr[0] = 0;
+        P->h_level_ptr[1] = M;
+        P->levels = 1;
+        P->widest_level = M;
+        HIP_TRY(hipMemcpyAsync(P->level_ptr, P->h_level_ptr, 2 * sizeof(int),
+                               hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(P->rowptr, cnt, ((size_t)M + 1) * sizeof(int),
+                               hipMemcpyDeviceToDevice, s));
+        hipLaunchKernelGGL(k_trsv_natural, tv_grid(M), dim3(TV_T), 0, s, M,
+                           P->order, P->level);
+        goto gather;
+    }
     HIP_TRY(scratch.get(&succ_ptr, z.succ_ptr));
     HIP_TRY(scratch.get(&succ, z.succ));
     HIP_TRY(scratch.get(&succ_pos, z.succ));
     HIP_TRY(scratch.get(&indeg, z.indeg));
     HIP_TRY(scratch.get(&frontier, z.frontier));
     HIP_TRY(scratch.get(&iota, z.iota));
-    hipLaunchKernelGGL(k_trsv_fill, tv_grid(M), dim3(TV_T), 0, s, M, uplo,
-                       A->irp, A->ja, cnt, sja, spos);
-    HIP_TRY(hipGetLastError());
     { /* the successor lists: S^T, the positions riding as 4-byte values */
         spmv_csr_dev S, ST;
         memset(&S, 0, sizeof S);
@@ -413,6 +459,7 @@ int trsv_analyse_dev(const spmv_csr_dev *A, int uplo, int unit, int max_levels,
     hipLaunchKernelGGL(k_trsv_newcnt, tv_grid(M), dim3(TV_T), 0, s, M, P->order,
                        cnt, P->rowptr);
     tr_scan(P->rowptr, (int64_t)M + 1, sums, s);
+gather:
     if (A->value_bytes == 4)
         hipLaunchKernelGGL((k_trsv_gather<uint32_t>), tv_grid(M), dim3(TV_T), 0,
                            s, M, P->order, cnt, sja, spos,
@@ -424,6 +471,10 @@ int trsv_analyse_dev(const spmv_csr_dev *A, int uplo, int unit, int max_levels,
                            (const uint64_t *)A->as, P->rowptr, P->ja,
                            (uint64_t *)P->as);
     HIP_TRY(hipGetLastError());
+    if (sweeps) {
+        HIP_TRY(hipStreamSynchronize(s));
+        return 0;
+    }
     P->h_level_ptr = (int *)malloc(((size_t)levels + 1) * sizeof(int));
     if (!P->h_level_ptr) {
         rc = -ENOMEM;
@@ -477,18 +528,21 @@ __device__ __forceinline__ void trsv_load(const double *X, int64_t ldx, int c,
  * Position p of the plan (row order[p]) by the TV_G lanes `sub` = 0 .. G - 1
  * of one lane group; `live` = false: the lanes only take part in the moves of
  * the sum.  THE RESULT CONTRACT (spmv_engine.h), every operation rounded once.
+ * The gathers read Xin, the row is stored to Xout: the level kernels pass their
+ * one X for both, a Jacobi sweep (below) the previous iterate and the next.
+ * NATURAL: the position is the row and `order` is not read (sweep plans).
  */
-template <int K, typename V>
+template <int K, typename V, bool NATURAL = false>
 __device__ __forceinline__ void
 trsv_row(bool live, int64_t p, int sub, int unit, const int *__restrict__ order,
          const int *__restrict__ rowptr, const int *__restrict__ ja,
          const V *__restrict__ as, const double *__restrict__ diag,
          const double *__restrict__ scale, const double *B, int64_t ldb,
-         double *X, int64_t ldx) {
+         const double *Xin, int64_t ldin, double *Xout, int64_t ldout) {
 #pragma clang fp contract(off)
     int row = 0, beg = 0, n = 0;
     if (live) {
-        row = order[p];
+        row = NATURAL ? (int)p : order[p];
         beg = rowptr[p];
         n = rowptr[p + 1] - beg;
     }
@@ -517,8 +571,8 @@ trsv_row(bool live, int64_t p, int sub, int unit, const int *__restrict__ order,
         const int c0 = ld_stream(ja + k), c1 = ld_stream(ja + k + TV_G);
         const V a0 = ld_stream(as + k), a1 = ld_stream(as + k + TV_G);
         double x0[K], x1[K];
-        trsv_load<K>(X, ldx, c0, x0);
-        trsv_load<K>(X, ldx, c1, x1);
+        trsv_load<K>(Xin, ldin, c0, x0);
+        trsv_load<K>(Xin, ldin, c1, x1);
         const double w0 = widen(a0), w1 = widen(a1);
 #pragma unroll
         for (int j = 0; j < K; ++j) {
@@ -535,7 +589,7 @@ trsv_row(bool live, int64_t p, int sub, int unit, const int *__restrict__ order,
         const int c0 = ld_stream(ja + k);
         const double w0 = widen(ld_stream(as + k));
         double x0[K];
-        trsv_load<K>(X, ldx, c0, x0);
+        trsv_load<K>(Xin, ldin, c0, x0);
 #pragma unroll
         for (int j = 0; j < K; ++j) {
             const double t = w0 * x0[j];
@@ -546,7 +600,7 @@ trsv_row(bool live, int64_t p, int sub, int unit, const int *__restrict__ order,
     for (int j = 0; j < K; ++j)
         acc[j] = group_sum<TV_G>(acc[j]); /* every lane takes part */
     if (writer) {
-        double *xr = X + (int64_t)row * ldx;
+        double *xr = Xout + (int64_t)row * ldout;
 #pragma unroll
         for (int j = 0; j < K; ++j) {
             double r = rhs[j];
@@ -571,7 +625,7 @@ k_trsv_wide(int first, int end, int unit, const int *__restrict__ order,
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t p = first + t / TV_G;
     trsv_row<K, V>(p < end, p, (int)(threadIdx.x & (TV_G - 1)), unit, order,
-                   rowptr, ja, as, diag, scale, B, ldb, X, ldx);
+                   rowptr, ja, as, diag, scale, B, ldb, X, ldx, X, ldx);
 }
 
 /* levels l0 .. l1 by ONE workgroup: the loop bounds are workgroup-uniform, so
@@ -590,9 +644,189 @@ k_trsv_chain(int l0, int l1, int unit, const int *__restrict__ level_ptr,
         for (int64_t base = beg; base < end; base += rows) {
             const int64_t p = base + mine;
             trsv_row<K, V>(p < end, p, sub, unit, order, rowptr, ja, as, diag,
-                           scale, B, ldb, X, ldx);
+                           scale, B, ldb, X, ldx, X, ldx);
         }
         __syncthreads(); /* the level's X is visible to the workgroup */
+    }
+}
+
+/*
+ * SWEEP PLANS (spmv_csr_trsv_analyse_sweeps): x(1) = D^-1 b, x(m) = D^-1 (b -
+ * S x(m-1)).  Every sweep is ONE launch over all M rows that reads only what
+ * the launch before it wrote: no waiting between workgroups, no atomics.
+ *
+ * k_trsv_first: trsv_row with s = +0.0, so the matrix is not read and the sweep
+ * is elementwise.  Lanes run over the M * k elements, not over the rows (the
+ * tile of cg_common.h): a wavefront's load is 512 consecutive bytes at ld = k.
+ * Nothing is kept per column, so k is an argument and the kernel exists once:
+ * the workgroup's first element is split into row and column once (uniform),
+ * a lane then divides a number below blockDim + k.  Each lane reads its own B
+ * before it stores: Xout may be B.
+ */
+__global__ void __launch_bounds__(1024)
+k_trsv_first(int M, int k, int unit, const double *__restrict__ diag,
+             const double *__restrict__ scale, const double *B, int64_t ldb,
+             double *Xout, int64_t ldout) {
+#pragma clang fp contract(off)
+    const int64_t f0 = (int64_t)blockIdx.x * blockDim.x;
+    const unsigned at = (unsigned)(f0 % k) + threadIdx.x;
+    const int64_t row = f0 / k + at / (unsigned)k;
+    const int j = (int)(at % (unsigned)k);
+    if (row >= M)
+        return;
+    double r = B[row * ldb + j];
+    if (scale)
+        r = scale[row] * r;
+    double zero = 0.0; /* opaque: the subtraction trsv_row does is done here
+                          too (it quietens a signalling NaN), never folded */
+    asm volatile("" : "+v"(zero));
+    double t = r - zero;
+    if (!unit)
+        t = t / diag[row];
+    Xout[row * ldout + j] = t;
+}
+
+/*
+ * Row `row` of a sweep by L < G lanes, for plans of short rows (trsv_plan.h:
+ * trsv_sweep_lanes; on two strict entries a row G lanes leave six idle and a
+ * sweep ran 2 - 3x slower, profiles/trsv_sweeps.md).  The G slots are the
+ * contract, the lanes are not: lane `sub` owns the slots sub, sub + L, .., one
+ * accumulator each, adds the same products in the same order, and the halving
+ * tree runs inside the lane down to h = L and across the L lanes below it --
+ * the same additions of the same operands as trsv_row, so the same bits.
+ */
+template <int K, typename V, int L>
+__device__ __forceinline__ void
+trsv_row_few(bool live, int64_t row, int sub, int unit,
+             const int *__restrict__ rowptr, const int *__restrict__ ja,
+             const V *__restrict__ as, const double *__restrict__ diag,
+             const double *__restrict__ scale, const double *B, int64_t ldb,
+             const double *Xin, int64_t ldin, double *Xout, int64_t ldout) {
+#pragma clang fp contract(off)
+    constexpr int S = TV_G / L; /* slots of one lane */
+    int beg = 0, n = 0;
+    if (live) {
+        beg = rowptr[row];
+        n = rowptr[row + 1] - beg;
+    }
+    double rhs[K], d = 1.0, sc = 1.0;
+    const bool writer = live && sub == 0;
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+        rhs[j] = 0.0;
+    if (writer) {
+        trsv_load<K>(B, ldb, (int)row, rhs);
+        if (!unit)
+            d = diag[row];
+        if (scale)
+            sc = scale[row];
+    }
+    double acc[S][K];
+#pragma unroll
+    for (int t = 0; t < S; ++t)
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+            acc[t][j] = 0.0;
+    ja += beg;
+    as += beg;
+    for (int q0 = 0; q0 < n; q0 += TV_G) { /* one round of the G slots */
+#pragma unroll
+        for (int t = 0; t < S; ++t) {
+            const int q = q0 + sub + t * L; /* slot sub + t L */
+            if (q < n) {
+                const int c = ld_stream(ja + q);
+                const double w = widen(ld_stream(as + q));
+                double x[K];
+                trsv_load<K>(Xin, ldin, c, x);
+#pragma unroll
+                for (int j = 0; j < K; ++j) {
+                    const double p = w * x[j];
+                    acc[t][j] = acc[t][j] + p;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int h = S / 2; h >= 1; h /= 2) /* p[g] += p[g + h L], inside the lane */
+#pragma unroll
+        for (int t = 0; t < h; ++t)
+#pragma unroll
+            for (int j = 0; j < K; ++j)
+                acc[t][j] = acc[t][j] + acc[t + h][j];
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+        acc[0][j] = group_sum<L>(acc[0][j]); /* h = L / 2 .. 1 */
+    if (writer) {
+        double *xr = Xout + row * ldout;
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            double r = rhs[j];
+            if (scale)
+                r = sc * r;
+            double t = r - acc[0][j];
+            if (!unit)
+                t = t / d;
+            xr[j] = t;
+        }
+    }
+}
+
+/* sweep m > 1: row i by L = G or TRSV_FEW_LANES lanes, the gathers from the iterate the launch
+ * before wrote (never written here), the row to Xout.  In the last sweep Xout
+ * is the caller's X and may be B: a row's writer lane holds its rhs before it
+ * stores, and no other lane reads that row of B */
+template <int K, typename V, int L>
+__global__ void __launch_bounds__(1024)
+k_trsv_sweep(int M, int unit, const int *__restrict__ rowptr,
+             const int *__restrict__ ja, const V *__restrict__ as,
+             const double *__restrict__ diag, const double *__restrict__ scale,
+             const double *B, int64_t ldb, const double *__restrict__ Xin,
+             int64_t ldin, double *Xout, int64_t ldout) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = t / L;
+    const int sub = (int)(threadIdx.x & (L - 1));
+    if (L == TV_G)
+        trsv_row<K, V, true>(i < M, i, sub, unit, NULL, rowptr, ja, as, diag,
+                             scale, B, ldb, Xin, ldin, Xout, ldout);
+    else
+        trsv_row_few<K, V, L>(i < M, i, sub, unit, rowptr, ja, as, diag, scale,
+                              B, ldb, Xin, ldin, Xout, ldout);
+}
+
+/* the sweeps of a sweep plan by the route of trsv_plan.h; the scratch has
+ * ld = K, the caller saw K <= kmax */
+template <int K, typename V>
+static void trsv_launch_sweeps(const spmv_trsv_plan *P, int waves,
+                               const double *B, int64_t ldb, double *X,
+                               int64_t ldx, const double *scale,
+                               hipStream_t s) {
+    const int threads = waves > 0 ? waves * WAVE : TRSV_WIDE_THREADS;
+    const V *as = (const V *)P->as;
+    double *const buf[3] = {X, P->sweep_buf[0], P->sweep_buf[1]};
+    const int64_t ld[3] = {ldx, K, K};
+    const int lanes = trsv_sweep_lanes(P->M, P->entries);
+    for (int m = 1; m <= P->sweeps; ++m) {
+        const trsv_route r = trsv_sweep_route(P->sweeps, m);
+        if (m == 1)
+            hipLaunchKernelGGL(
+                k_trsv_first,
+                dim3((unsigned)trsv_ceil_div((int64_t)P->M * K, threads)),
+                dim3(threads), 0, s, P->M, K, P->unit, P->diag, scale, B, ldb,
+                buf[r.out], ld[r.out]);
+        else if (lanes == TV_G)
+            hipLaunchKernelGGL(
+                (k_trsv_sweep<K, V, TV_G>),
+                dim3((unsigned)trsv_sweep_grid(P->M, threads, lanes)),
+                dim3(threads), 0, s, P->M, P->unit, P->rowptr, P->ja, as,
+                P->diag, scale, B, ldb, buf[r.in], ld[r.in], buf[r.out],
+                ld[r.out]);
+        else
+            hipLaunchKernelGGL(
+                (k_trsv_sweep<K, V, TRSV_FEW_LANES>),
+                dim3((unsigned)trsv_sweep_grid(P->M, threads, lanes)),
+                dim3(threads), 0, s, P->M, P->unit, P->rowptr, P->ja, as,
+                P->diag, scale, B, ldb, buf[r.in], ld[r.in], buf[r.out],
+                ld[r.out]);
     }
 }
 
@@ -629,7 +863,10 @@ static void trsv_launch_k(const spmv_trsv_plan *P, int waves, int k,
     switch (k) {
 #define TRSV_CASE(K)                                                          \
     case K:                                                                   \
-        trsv_launch<K, V>(P, waves, B, ldb, X, ldx, scale, s);                \
+        if (P->sweeps)                                                        \
+            trsv_launch_sweeps<K, V>(P, waves, B, ldb, X, ldx, scale, s);     \
+        else                                                                  \
+            trsv_launch<K, V>(P, waves, B, ldb, X, ldx, scale, s);            \
         break;
         TRSV_CASE(1)
         TRSV_CASE(2)

@@ -97,6 +97,55 @@ static inline int64_t trsv_segments(const int *level_ptr, int levels,
 }
 
 /*
+ * SWEEP PLANS (spmv_csr_trsv_analyse_sweeps): a solve is `sweeps` launches over
+ * all rows, x(1) = D^-1 b, x(m) = D^-1 (b - S x(m-1)).  The route says which
+ * buffer sweep m (1 .. sweeps) gathers from and which it writes: the caller's X
+ * or the plan's scratch T1, T2 (ld = k).  Every sweep reads its right-hand side
+ * from B, and nothing but the last sweep writes X, so X may be B.  The
+ * launcher, `bytes` and tests/asan/trsv_sweep_asan.cc read this one function.
+ */
+#define TRSV_FEW_LANES 2   /* lanes per row of a sweep over short rows */
+#define TRSV_FEW_ENTRIES 4 /* "short": at most this many strict entries a row
+                              on average (measured at 2.0 and at 12.9 only:
+                              profiles/trsv_sweeps.md) */
+#define TRSV_MAX_SWEEPS 4096
+#define TRSV_MAX_K 8
+#define TRSV_BUF_NONE (-1) /* the first sweep gathers nothing */
+#define TRSV_BUF_X 0
+#define TRSV_BUF_T1 1
+#define TRSV_BUF_T2 2
+
+struct trsv_route {
+    int in;  /* TRSV_BUF_NONE, _T1, _T2: never the buffer `out` names */
+    int out; /* TRSV_BUF_X in the last sweep, else _T1 / _T2 alternately */
+};
+
+/* scratch vectors of kmax * M doubles a plan of `sweeps` sweeps owns */
+static inline int trsv_sweep_scratch(int sweeps) {
+    return sweeps < 2 ? 0 : sweeps == 2 ? 1 : 2;
+}
+
+/* lanes per row of the sweeps of a plan: a function of the plan alone.  The
+ * G slots of a row's sum are the contract, the lanes are not: the bits are the
+ * same either way */
+static inline int trsv_sweep_lanes(int64_t M, int64_t entries) {
+    return entries <= TRSV_FEW_ENTRIES * M ? TRSV_FEW_LANES : TRSV_GROUP;
+}
+
+/* workgroups of one sweep over M rows, `lanes` lanes a row, `threads` a group */
+static inline int64_t trsv_sweep_grid(int64_t M, int threads, int lanes) {
+    return trsv_ceil_div(M, threads / lanes);
+}
+
+/* 1 <= m <= sweeps */
+static inline trsv_route trsv_sweep_route(int sweeps, int m) {
+    trsv_route r;
+    r.in = m == 1 ? TRSV_BUF_NONE : (m & 1) ? TRSV_BUF_T2 : TRSV_BUF_T1;
+    r.out = m == sweeps ? TRSV_BUF_X : (m & 1) ? TRSV_BUF_T1 : TRSV_BUF_T2;
+    return r;
+}
+
+/*
  * Element counts of the analysis' device arrays for M rows, NZ stored and
  * SNZ strict entries (the launcher allocates exactly these; the sanitizer
  * program restates the kernels over heap blocks of these sizes).
