@@ -698,6 +698,88 @@ int spmv_csr_permute(const spmv_csr_dev *A,
 int spmv_permute_vectors(const int *d_new_of_old, int M, int k, int inverse,
                          const double *d_in, int64_t ldin, double *d_out,
                          int64_t ldout, void *stream);
+/*
+ * The sparse product on the device: spmv_csr_spgemm makes a NEW, ordinary
+ * M x N CSR handle C = A B from an M x K handle A and a K x N handle B.  Each
+ * operand is f64 or f32-stored (f32 values are widened exactly); C is f64 and
+ * owns all its arrays.  A may be B itself; both are unchanged and may be
+ * released afterwards.  Every kernel id, launch_multi, spmv_hll_from_csr,
+ * spmv_csr_to_f32, transpose, trsv_analyse, ic0 / ilu0, the solvers, download
+ * and release work on C as on any handle.
+ *
+ * THE RESULT IS DEFINED TO THE BIT.  For row r, walk A's stored entries p of
+ * that row in stored order; for each p, walk the stored entries q of B's row
+ * JA_A[p] in stored order.  Each pair gives one product
+ *     t = rn(AS_A[p] * AS_B[q])        with column JA_B[q].
+ * Row r of C holds every column that occurs, once, in ascending order; the
+ * value of a column is the SEQUENTIAL sum of its products in that walk order:
+ * s = t1, then s = rn(s + ti).  The first product initialises the sum -- there
+ * is no 0.0 +, so a lone -0.0 keeps its sign -- and nothing is fused: no
+ * multiply-add anywhere.  An entry exists because a product exists: exact
+ * cancellation and explicit zeros store a 0.0, inf * 0 stores a NaN in that
+ * entry and nowhere else.  An empty row of B contributes nothing; a row with
+ * no products is empty.  A may have unsorted rows, duplicates (two steps of
+ * the walk) and explicit zeros.  THE ROWS OF B MUST BE STRICTLY ASCENDING BY
+ * COLUMN (what spmv_csr_permute and a double spmv_csr_transpose give for a
+ * source without duplicates): that is what lets the lanes of one step p write
+ * distinct slots without atomics on values.  The bits do not depend on
+ * scheduling, nor on which size class served a row.
+ *
+ * How: the rows are put into four size classes by their number of products
+ * ub[r] = sum over the entries (r, k) of A of len(row k of B) (64-bit).
+ * Classes 0..2 keep a row's columns in an LDS table worked by 16 lanes, a
+ * wavefront or a workgroup; the last class is the fallback for wider rows (hub
+ * rows, A A^T of anything with a dense column): one workgroup per row with N
+ * doubles and N bits of global scratch, in batches, which costs O(N) per such
+ * row.  A symbolic pass counts the distinct columns, a scan gives C's IRP, a
+ * numeric pass writes JA and AS.  No workgroup waits for another.
+ * spmv_spgemm_shape reports the constants (host arithmetic, no device; any
+ * out-pointer may be NULL): edges[c] the largest ub of class c = 0..2,
+ * tables[c] the slots of its table (twice the edge: never more than half
+ * full), teams[c] its lanes, lds_bytes[c] the dynamic LDS of its workgroups,
+ * and the fallback's bounds -- at most *fallback_batch rows a launch, their
+ * scratch together at most *fallback_bytes (or one row's, when that is more).
+ *
+ * Errors, in this order: NULL A, B or out -EINVAL; no device -ENODEV; a dead
+ * handle -EBADF; A.N != B.M -EINVAL; either handle after
+ * spmv_csr_release_source -ENODATA; a column of A outside [0, K) or of B
+ * outside [0, N) -EDOM; a row of B not strictly ascending -EINVAL (a device
+ * check, before anything is allocated for the result); more than INT32_MAX
+ * entries in C -EOVERFLOW (known after the symbolic pass, before C is
+ * allocated); a failed allocation -ENOMEM.  On any error nothing is created,
+ * *out is NULL, *info is not written, all scratch is freed and
+ * spmv_live_handles() is unchanged.  M, K, N or either NZ may be 0.  The call
+ * blocks.  Peak device memory besides A, B and C, freed before the call
+ * returns: 16 M bytes and, when the fallback serves a row, its scratch.
+ *
+ * spmv_csr_galerkin: *out = PT (A P), two products and nothing else, so its
+ * bits are those of the two products.  PT NULL: P^T is built by
+ * spmv_csr_transpose and released.  The intermediate A P is released.  Errors
+ * as the calls it is made of; info (or NULL) describes the SECOND product.
+ *
+ * Not in scope: C = alpha A + beta B, a masked or filtered product, reuse of
+ * a symbolic pass, HLL and compact handles as operands, an f32 result
+ * (spmv_csr_to_f32 makes one), B with duplicates or unsorted rows.
+ */
+typedef struct spmv_spgemm_info {
+    int64_t products;       /* sum over entries (r,k) of A of len(row k of B) */
+    int64_t widest;         /* most products of one row */
+    int64_t rows_in_bin[4]; /* rows handled by each size class, last = fallback */
+    int nz;                 /* entries of C */
+} spmv_spgemm_info;
+int spmv_csr_spgemm(const spmv_csr_dev *A, const spmv_csr_dev *B,
+                    spmv_csr_dev **out, spmv_spgemm_info *info /* or NULL */);
+int spmv_spgemm_shape(int64_t *edges /* [3] */, int *tables /* [3] */,
+                      int *teams /* [3] */, int *lds_bytes /* [3] */,
+                      int *fallback_batch, int64_t *fallback_bytes);
+/* MEASUREMENT (tools/spgemm_report.py): host-clock ms of the last successful
+ * spmv_csr_spgemm of this process -- [0] checks and bounds, [1] class lists
+ * and symbolic pass, [2] scan, allocation of C and numeric pass, [3] the part
+ * of [1] and [2] spent in the fallback's launches.  Not thread-safe. */
+void spmv_spgemm_last_phases(double ms[4]);
+int spmv_csr_galerkin(const spmv_csr_dev *A, const spmv_csr_dev *P,
+                      const spmv_csr_dev *PT /* or NULL */, spmv_csr_dev **out,
+                      spmv_spgemm_info *info /* or NULL */);
 /* Build a synthetic matrix (spmv_synth.h) directly in device memory. */
 int spmv_csr_generate(int kind, int M, int N, int K, int64_t W, int64_t row0,
                       uint64_t seed, spmv_csr_dev **out);

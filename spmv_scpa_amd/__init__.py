@@ -444,6 +444,12 @@ class ColourInfo(C.Structure):
                 ("widest", C.c_int), ("narrowest", C.c_int)]
 
 
+class SpgemmInfo(C.Structure):
+    """spmv_spgemm_info (include/spmv_engine.h): one CsrDevice.matmul()"""
+    _fields_ = [("products", C.c_int64), ("widest", C.c_int64),
+                ("rows_in_bin", C.c_int64 * 4), ("nz", C.c_int)]
+
+
 _CSRp = C.POINTER(SparseCSR)
 _HLLp = C.POINTER(SparseHLL)
 
@@ -575,6 +581,12 @@ _sig("spmv_transpose_plan", C.c_int, C.c_int, C.c_int64, _ip, _ip, _ip,
      C.POINTER(C.c_int64), C.POINTER(C.c_int64))
 _sig("spmv_csr_symmetry", C.c_int, C.c_void_p, _ip)
 _i64p = C.POINTER(C.c_int64)
+_sig("spmv_csr_spgemm", C.c_int, C.c_void_p, C.c_void_p,
+     C.POINTER(C.c_void_p), C.POINTER(SpgemmInfo))
+_sig("spmv_spgemm_shape", C.c_int, _i64p, _ip, _ip, _ip, _ip, _i64p)
+_sig("spmv_spgemm_last_phases", None, _dp)
+_sig("spmv_csr_galerkin", C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.POINTER(C.c_void_p), C.POINTER(SpgemmInfo))
 _sig("spmv_csr_trsv_analyse", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
      C.POINTER(C.c_void_p))
 _sig("spmv_csr_trsv_analyse_sweeps", C.c_int, C.c_void_p, C.c_int, C.c_int,
@@ -873,6 +885,39 @@ def transpose_plan(N, NZ):
            "spmv_transpose_plan")
     return dict(passes=p.value, digit_bits=d.value, tile=t.value,
                 workgroups=w.value, scratch_bytes=s.value)
+
+
+#: CsrDevice.spgemm_info of a matmul() / galerkin() result
+SpgemmResult = collections.namedtuple("SpgemmResult",
+                                      "products widest rows_in_bin nz")
+
+
+def spgemm_shape():
+    """the constants of CsrDevice.matmul() (host, no device): dict(edges,
+    tables, teams, lds_bytes, fallback_batch, fallback_bytes) -- a row with ub
+    products goes to the first class c = 0..2 with ub <= edges[c], whose
+    teams[c] lanes keep its columns in an LDS table of tables[c] slots
+    (lds_bytes[c] per workgroup), and to the fallback (class 3) beyond; the
+    fallback runs at most fallback_batch rows a launch within fallback_bytes
+    of scratch (or one row's)"""
+    e, t = (C.c_int64 * 3)(), (C.c_int * 3)()
+    m, b = (C.c_int * 3)(), (C.c_int * 3)()
+    fb, fs = C.c_int(), C.c_int64()
+    _check(_lib.spmv_spgemm_shape(e, t, m, b, C.byref(fb), C.byref(fs)),
+           "spmv_spgemm_shape")
+    return dict(edges=list(e), tables=list(t), teams=list(m),
+                lds_bytes=list(b), fallback_batch=fb.value,
+                fallback_bytes=fs.value)
+
+
+def spgemm_last_phases():
+    """host-clock ms of the last successful matmul() of this process:
+    dict(bound, symbolic, numeric, fallback) -- checks and bounds; class
+    lists and symbolic pass; scan, allocation and numeric pass; the part of
+    the last two spent in the fallback's launches (a measurement aid)"""
+    ms = (C.c_double * 4)()
+    _lib.spmv_spgemm_last_phases(ms)
+    return dict(zip(("bound", "symbolic", "numeric", "fallback"), ms))
 
 
 def trsv_shape():
@@ -1971,6 +2016,47 @@ class CsrDevice(_Device):
         _check(_lib.spmv_csr_transpose(self.h, C.byref(h)),
                "spmv_csr_transpose")
         return CsrDevice(h)
+
+    def _product(self, h, info):
+        d = CsrDevice(h)
+        d.spgemm_info = SpgemmResult(info.products, info.widest,
+                                     tuple(info.rows_in_bin), info.nz)
+        return d
+
+    def matmul(self, other):
+        """a new M x N f64 handle C = self . other built on the device
+        (spmv_engine.h, spmv_csr_spgemm): every column a product meets, once,
+        ascending; each value the sequential sum of its products in the order
+        of the walk over this handle's stored entries and other's rows, the
+        first product initialising the sum, nothing fused -- defined to the
+        bit.  Either operand may be f32-stored; `other` may be this handle.
+        other's rows must be strictly ascending by column
+        (OSError(EINVAL); transpose().transpose() sorts rows).  The result
+        carries .spgemm_info (products, widest, rows_in_bin, nz).  Both
+        operands stay valid"""
+        if not isinstance(other, CsrDevice):
+            raise TypeError("matmul: a CsrDevice, not %s"
+                            % type(other).__name__)
+        h, info = C.c_void_p(), SpgemmInfo()
+        _check(_lib.spmv_csr_spgemm(self.h, other.h, C.byref(h),
+                                    C.byref(info)), "spmv_csr_spgemm")
+        return self._product(h, info)
+
+    def galerkin(self, dP, dPT=None):
+        """a new handle dPT . (self . dP): the coarse operator of a
+        prolongation dP, two matmul() and nothing else (spmv_csr_galerkin).
+        dPT None: dP.transpose(), built and released; the intermediate
+        product is released.  .spgemm_info describes the second product"""
+        for d in (dP,) + ((dPT,) if dPT is not None else ()):
+            if not isinstance(d, CsrDevice):
+                raise TypeError("galerkin: a CsrDevice, not %s"
+                                % type(d).__name__)
+        h, info = C.c_void_p(), SpgemmInfo()
+        _check(_lib.spmv_csr_galerkin(self.h, dP.h,
+                                      dPT.h if dPT is not None else None,
+                                      C.byref(h), C.byref(info)),
+               "spmv_csr_galerkin")
+        return self._product(h, info)
 
     def symmetry(self):
         """SYM_NONE, SYM_PATTERN or SYM_VALUES: entries compared position by

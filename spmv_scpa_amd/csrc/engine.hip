@@ -25,6 +25,7 @@
 #include "hip_csr.h"
 #include "hip_hll.h"
 #include "mat_ref.h"
+#include "spgemm_plan.h"
 #include "spmv_synth.h"
 #include "stream_table.h"
 #include "transpose_plan.h"
@@ -1128,6 +1129,83 @@ int spmv_csr_ilu0(const spmv_csr_dev *A, double shift, int max_levels,
         *info = got;
     *out = d;
     return 0;
+}
+
+/* the constants of the sparse product (spgemm_plan.h); host arithmetic */
+int spmv_spgemm_shape(int64_t *edges, int *tables, int *teams, int *lds_bytes,
+                      int *fallback_batch, int64_t *fallback_bytes) {
+    for (int c = 0; c < SPGEMM_CLASSES - 1; ++c) {
+        if (edges)
+            edges[c] = spgemm_edge(c);
+        if (tables)
+            tables[c] = spgemm_table(c);
+        if (teams)
+            teams[c] = spgemm_team(c);
+        if (lds_bytes)
+            lds_bytes[c] = spgemm_lds(c);
+    }
+    if (fallback_batch)
+        *fallback_batch = SPGEMM_FALLBACK_MAX_BATCH;
+    if (fallback_bytes)
+        *fallback_bytes = SPGEMM_FALLBACK_BYTES;
+    return 0;
+}
+
+void spmv_spgemm_last_phases(double ms[4]) {
+    if (ms)
+        csr_spgemm_last_phases(ms);
+}
+
+/* a new M x N f64 handle C = A B (spgemm_kernels.hip) */
+int spmv_csr_spgemm(const spmv_csr_dev *A, const spmv_csr_dev *B,
+                    spmv_csr_dev **out, spmv_spgemm_info *info) {
+    if (out)
+        *out = NULL; /* on ANY error, the argument checks included */
+    if (!A || !B || !out)
+        return -EINVAL;
+    if (spmv_device_count() == 0)
+        return -ENODEV; /* no handle can be live: the more useful answer */
+    HANDLE_OK(A);
+    HANDLE_OK(B);
+    if (A->N != B->M)
+        return -EINVAL;
+    if ((!A->ja && A->NZ > 0) || (!B->ja && B->NZ > 0))
+        return -ENODATA; /* spmv_csr_release_source() */
+    spmv_csr_dev *d = NULL;
+    spmv_spgemm_info got;
+    int rc = csr_spgemm_dev(A, B, csr_alloc_dev, &d, &got, 0);
+    if (rc)
+        return rc;
+    rc = finish_csr_handle(d, NULL);
+    if (rc) {
+        spmv_csr_release(d);
+        return rc;
+    }
+    if (info)
+        *info = got;
+    *out = d;
+    return 0;
+}
+
+/* PT (A P): the two products, the intermediate released */
+int spmv_csr_galerkin(const spmv_csr_dev *A, const spmv_csr_dev *P,
+                      const spmv_csr_dev *PT, spmv_csr_dev **out,
+                      spmv_spgemm_info *info) {
+    if (out)
+        *out = NULL;
+    if (!A || !P || !out)
+        return -EINVAL;
+    spmv_csr_dev *AP = NULL, *T = NULL;
+    int rc = spmv_csr_spgemm(A, P, &AP, NULL);
+    if (!rc && !PT) {
+        rc = spmv_csr_transpose(P, &T);
+        PT = T;
+    }
+    if (!rc)
+        rc = spmv_csr_spgemm(PT, AP, out, info);
+    spmv_csr_release(T); /* NULL: ignored */
+    spmv_csr_release(AP);
+    return rc;
 }
 
 /* 0: not symmetric, 1: the pattern is, 2: the stored values are too */

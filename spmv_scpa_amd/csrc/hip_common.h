@@ -702,6 +702,20 @@ int csr_colour_dev(const spmv_csr_dev *A, uint32_t seed, int max_rounds,
                    hipStream_t s);
 int csr_permute_dev(const spmv_csr_dev *A, const int *p, const int *q,
                     ic0_alloc_fn alloc, spmv_csr_dev **out, hipStream_t s);
+/*
+ * C = A B (spgemm_kernels.hip; spmv_csr_spgemm).  The caller has checked the
+ * handles (live, with their sources, A->N == B->M).  *out comes from `alloc`
+ * once the entries of C are known and holds irp, ja and the values; the caller
+ * finishes it as spmv_csr_transpose does.  Blocks; on an error *out and *info
+ * are untouched and everything is freed.
+ */
+int csr_spgemm_dev(const spmv_csr_dev *A, const spmv_csr_dev *B,
+                   ic0_alloc_fn alloc, spmv_csr_dev **out,
+                   spmv_spgemm_info *info, hipStream_t s);
+/* host-clock ms of the last successful product of this process: checks and
+ * bounds, lists and symbolic pass, scan + allocation + numeric pass, and the
+ * part of the last two spent in the fallback's launches */
+void csr_spgemm_last_phases(double ms[4]);
 int permute_vectors_dev(const int *p, int M, int k, int inverse,
                         const double *in, int64_t ldin, double *out,
                         int64_t ldout, hipStream_t s);
