@@ -1279,6 +1279,168 @@ int spmv_hll_pcg_trsv(const spmv_hll_dev *H, const spmv_launch_opts *opts,
                       size_t work_bytes, spmv_cg_info *info, void *stream);
 
 /*
+ * Smoothed-aggregation algebraic multigrid on the device, and conjugate
+ * gradients preconditioned by one V cycle (added after 0.7; spmv_version() is
+ * unchanged, detect them by the symbols).  Everything is defined to the
+ * integer or to the bit; tests/_amg.py restates it in numpy.
+ *
+ * AGGREGATION.  spmv_csr_aggregate: A square, f64, with its source, every row
+ * strictly ascending by column and holding its diagonal.  theta2 = theta *
+ * theta is formed on the host.  Entry (i, j), j != i, is STRONG iff
+ *     rn(a_ij * a_ij) >= rn(theta2 * |rn(d_i * d_j)|)
+ * (d the stored diagonal; a comparison with a NaN is false, so a NaN entry is
+ * never strong; theta == 0 makes every stored off-diagonal with a finite
+ * d_i d_j strong, explicit zeros included).  Only row i's own entries are
+ * read: nothing assumes symmetry, the neighbours of i are the strong columns
+ * of row i.
+ *   Roots: a maximal independent set of distance 2 in that graph by parallel
+ * rounds (Bell, Dalton, Olson 2012).  Row i carries the tuple (state,
+ * fmix32(i ^ seed), i), ordered lexicographically with out < undecided < root.
+ * A round takes the maximum over a row and its neighbours twice (the second
+ * time of the first maxima) and decides: an undecided row whose distance-2
+ * maximum is its own tuple becomes a root, one whose maximum is a root becomes
+ * out.  One round is three launches and one 4-byte read-back of the number of
+ * undecided rows; every launch reads arrays earlier launches wrote and writes
+ * another; no workgroup waits for another.  More than max_rounds rounds (0:
+ * 4096) is -E2BIG.
+ *   Aggregates, in this order.  Roots are numbered in ascending row order.
+ * Pass 1: a row that is no root joins the root among its strong neighbours of
+ * the greatest |a_ij|, the first in stored order among equals.  Pass 2: a row
+ * still free joins the aggregate its strong neighbour of the greatest |a_ij|
+ * (the first among equals) had AFTER pass 1.  Pass 3: rows still free become
+ * singletons, numbered behind the roots in row order.  (A row put out has a
+ * root within two strong steps, and the row between them joined in pass 1: as
+ * defined here pass 3 finds no row; it is kept as the guard of that argument.)
+ *   d_agg: M ints or NULL.  info (or NULL): aggregates = roots + singletons,
+ * rounds, widest = the rows of the largest aggregate.  M == 0: zeros.
+ *   Errors, in this order: NULL A, theta not finite or negative, max_rounds
+ * < 0 -EINVAL; no device -ENODEV; a dead handle -EBADF; not square -EINVAL; an
+ * f32 handle -ENOTSUP; after spmv_csr_release_source -ENODATA; a column
+ * outside [0, M) -EDOM; a row not strictly ascending or without its diagonal
+ * -EINVAL (a device check, before anything else is allocated); -E2BIG;
+ * -ENOMEM.  On any error d_agg and *info are not written and all scratch is
+ * freed.  The call blocks.
+ *
+ * SETUP.  spmv_csr_amg_setup builds a hierarchy from A_0 = A (the checks of
+ * spmv_csr_aggregate; sweeps and coarse_sweeps in 1..64, min_rows >= 1,
+ * max_levels in 1..32 or 0 = 16, kmax in 1..8, else -EINVAL).  Per level l of
+ * M_l rows:
+ *   1. rho = max_i rn(S_i / |d_i|), S_i the sequential sum of |a_ij| in stored
+ *      order from 0.0: the Gershgorin bound of D^-1 A (a maximum is exact in
+ *      any order).  A rho that is not finite or not positive is -EDOM (so is
+ *      M == 0).
+ *   2. omega = (4.0 / 3.0) / rho on the host; w_i = rn(omega / d_i).
+ *   3. The level is the coarsest when M_l <= min_rows, or it is the
+ *      max_levels-th, or the aggregation (theta, seed) gives M_l aggregates.
+ *   4. Otherwise T is M_l x aggregates with one 1.0 per row at column agg[i];
+ *      AT = spmv_csr_spgemm(A_l, T);  P = T - diag(w) AT in place on AT's
+ *      values, p = rn(t - rn(w_i * at)) with t = 1.0 at column agg[i] and 0.0
+ *      elsewhere;  PT = spmv_csr_transpose(P);  A_{l+1} =
+ *      spmv_csr_galerkin(A_l, P, PT).
+ * The hierarchy owns A_1.., every P and PT (ordinary live handles: they count
+ * in spmv_live_handles() until the hierarchy is released), w, and one scratch
+ * allocation of four vectors of kmax * M_l doubles per level (two on level
+ * 0).  It BORROWS A_0: releasing A makes every later apply -EBADF.  On any
+ * error nothing is left allocated and spmv_live_handles() is what it was.
+ * spmv_amg_info: the numbers of the hierarchy (any level beyond `levels` is
+ * zero; rounds and aggregates of the coarsest level are 0 when it was not
+ * aggregated); spmv_amg_level: the borrowed handles and w of level l (P and PT
+ * NULL on the coarsest); any out-pointer may be NULL.  spmv_amg_last_phases:
+ * host-clock ms of the last successful setup of this process -- [0] rho and w,
+ * [1] aggregation, [2] T, A T and the smoothing, [3] the transposition, [4] the
+ * Galerkin product, [5] scratch and bookkeeping.  Not thread-safe.
+ *
+ * THE CYCLE.  spmv_amg_apply: Z = V(R) for k <= kmax interleaved vectors (ldr,
+ * ldz >= k; 0 = k), asynchronous on `stream` and capturable: the launches are
+ * a function of the hierarchy and k alone.  Two applies of one hierarchy must
+ * not overlap in time (they share its scratch).  At level l with right-hand
+ * side b:
+ *   1. x = rn(w_i * b_i)
+ *   2. sweeps - 1 times  x <- rn(x + rn(w_i * rn(b - s))),  s = the row of
+ *      A_l x
+ *   3. on the coarsest level the same with coarse_sweeps for sweeps; return
+ *   4. r = rn(b - s);  b_c = PT r;  x_c from level l + 1;
+ *      x <- rn(x + (P x_c));  sweeps more sweeps.
+ * Every s and both transfer products have the bits of spmv_csr_launch_multi on
+ * that level's handle (group 0), rn(b - s) is what spmv_csr_launch_axpby(-1,
+ * 1) stores and rn(x + P x_c) what launch_axpby(1, 1) stores; nothing else is
+ * fused: no multiply-add outside those products.  The bits depend on neither
+ * k, nor waves_per_block, nor the other columns.  A sweep is either ONE
+ * launch of the fused kernel (amg_kernels.hip: the walk of launch_multi, then
+ * x_new = rn(x_old + rn(w_i rn(b - s))) written to the other buffer of a
+ * ping-pong; its residual mode stores rn(b - s)) or the composition it
+ * replaces, launch_axpby into r followed by one vector kernel -- the same bits
+ * either way.  Which one is a measured rule (profiles/amg.md): the fused
+ * kernel for k >= 4, the composition below, and always the composition on a
+ * level whose handle holds a row of more than 2048 entries.
+ * spmv_amg_set_fused(mode) overrides the rule for the process (MEASUREMENT and
+ * tests; not thread-safe): 0 the composition everywhere, 2 the fused kernel
+ * wherever it can run, 1 the rule; returns the previous mode, -EINVAL for
+ * another value.  spmv_amg_summary.launches is the count at k = kmax.  opts: waves_per_block
+ * only (group, variant, reserved 0).  Errors: NULL H, d_R or d_Z, k outside
+ * 1..kmax, a leading dimension below k, d_R == d_Z, bad opts -EINVAL; a dead
+ * hierarchy, or one whose A_0 was released -EBADF (-ENODEV without a device).
+ *
+ * THE SOLVER.  spmv_*_pcg_amg is spmv_*_pcg_trsv word for word with
+ * Z = spmv_amg_apply(H, R) where that has the plans' solves: the handles (the
+ * fine matrix may be HLL; H was built from a CSR handle of the same rows), the
+ * blocking, check_every, the records, the frozen-column rule, d_work of
+ * spmv_pcg_trsv_work_bytes(M, k) bytes.  Checks added after pcg's, in this
+ * order: NULL H -EINVAL; a dead hierarchy -EBADF; H's M is not A's -EINVAL;
+ * k > kmax -EINVAL.
+ *
+ * Not in scope: AMG inside bicgstab / gmres / minres, W or K cycles, Chebyshev
+ * or Gauss-Seidel smoothing, a direct coarse solve, strength-filtered
+ * smoothing, f32 or HLL levels, reuse of a pattern for new values.
+ */
+typedef struct spmv_aggregate_info {
+    int aggregates, roots, rounds;
+    int widest;     /* rows of the largest aggregate */
+    int singletons; /* aggregates made by pass 3 */
+} spmv_aggregate_info;
+int spmv_csr_aggregate(const spmv_csr_dev *A, double theta, uint32_t seed,
+                       int max_rounds, int *d_agg /* M ints or NULL */,
+                       spmv_aggregate_info *info /* or NULL */);
+
+#define SPMV_AMG_MAX_LEVELS 32
+typedef struct spmv_amg spmv_amg;
+typedef struct spmv_amg_summary {
+    int levels, sweeps, coarse_sweeps, kmax;
+    int rows[SPMV_AMG_MAX_LEVELS];
+    int rounds[SPMV_AMG_MAX_LEVELS];
+    int aggregates[SPMV_AMG_MAX_LEVELS];
+    int launches; /* of one apply */
+    int64_t entries[SPMV_AMG_MAX_LEVELS];
+    double rho[SPMV_AMG_MAX_LEVELS], omega[SPMV_AMG_MAX_LEVELS];
+    double complexity; /* sum of entries / entries[0] */
+    int64_t scratch_bytes;
+} spmv_amg_summary;
+int spmv_csr_amg_setup(const spmv_csr_dev *A, double theta, int sweeps,
+                       int coarse_sweeps, int min_rows, int max_levels,
+                       uint32_t seed, int kmax, spmv_amg **out);
+int spmv_amg_info(const spmv_amg *H, spmv_amg_summary *out);
+int spmv_amg_level(const spmv_amg *H, int level, const spmv_csr_dev **A,
+                   const spmv_csr_dev **P, const spmv_csr_dev **PT,
+                   const double **d_w);
+void spmv_amg_last_phases(double ms[6]);
+int spmv_amg_set_fused(int mode);
+void spmv_amg_release(spmv_amg *H);
+void spmv_amg_release_checked(spmv_amg *H, uint64_t generation);
+int spmv_amg_apply(const spmv_amg *H, const spmv_launch_opts *opts, int k,
+                   const double *d_R, int64_t ldr, double *d_Z, int64_t ldz,
+                   void *stream);
+int spmv_csr_pcg_amg(const spmv_csr_dev *A, const spmv_launch_opts *opts,
+                     int k, const double *d_B, int64_t ldb, double *d_X,
+                     int64_t ldx, const spmv_amg *H, double tol, int maxit,
+                     int check_every, void *d_work, size_t work_bytes,
+                     spmv_cg_info *info, void *stream);
+int spmv_hll_pcg_amg(const spmv_hll_dev *A, const spmv_launch_opts *opts,
+                     int k, const double *d_B, int64_t ldb, double *d_X,
+                     int64_t ldx, const spmv_amg *H, double tol, int maxit,
+                     int check_every, void *d_work, size_t work_bytes,
+                     spmv_cg_info *info, void *stream);
+
+/*
  * BiCGStab on the device for A X = B with a nonsymmetric A (added after 0.7;
  * spmv_version() is unchanged, detect it by the symbol).  A: square, otherwise
  * arbitrary, a CSR or column-major HLL handle of either value type.  Only A x

@@ -444,6 +444,30 @@ class ColourInfo(C.Structure):
                 ("widest", C.c_int), ("narrowest", C.c_int)]
 
 
+class AggregateInfo(C.Structure):
+    """spmv_aggregate_info (include/spmv_engine.h): one CsrDevice.aggregate()"""
+    _fields_ = [("aggregates", C.c_int), ("roots", C.c_int),
+                ("rounds", C.c_int), ("widest", C.c_int),
+                ("singletons", C.c_int)]
+
+
+AMG_MAX_LEVELS = 32
+
+
+class AmgSummary(C.Structure):
+    """spmv_amg_summary (include/spmv_engine.h): AmgHierarchy.info"""
+    _fields_ = [("levels", C.c_int), ("sweeps", C.c_int),
+                ("coarse_sweeps", C.c_int), ("kmax", C.c_int),
+                ("rows", C.c_int * AMG_MAX_LEVELS),
+                ("rounds", C.c_int * AMG_MAX_LEVELS),
+                ("aggregates", C.c_int * AMG_MAX_LEVELS),
+                ("launches", C.c_int),
+                ("entries", C.c_int64 * AMG_MAX_LEVELS),
+                ("rho", C.c_double * AMG_MAX_LEVELS),
+                ("omega", C.c_double * AMG_MAX_LEVELS),
+                ("complexity", C.c_double), ("scratch_bytes", C.c_int64)]
+
+
 class SpgemmInfo(C.Structure):
     """spmv_spgemm_info (include/spmv_engine.h): one CsrDevice.matmul()"""
     _fields_ = [("products", C.c_int64), ("widest", C.c_int64),
@@ -609,6 +633,19 @@ _sig("spmv_csr_colour", C.c_int, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p,
      C.c_void_p, C.POINTER(ColourInfo))
 _sig("spmv_csr_permute", C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
      C.POINTER(C.c_void_p))
+_sig("spmv_csr_aggregate", C.c_int, C.c_void_p, C.c_double, C.c_uint32,
+     C.c_int, C.c_void_p, C.POINTER(AggregateInfo))
+_sig("spmv_csr_amg_setup", C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_int,
+     C.c_int, C.c_int, C.c_uint32, C.c_int, C.POINTER(C.c_void_p))
+_sig("spmv_amg_info", C.c_int, C.c_void_p, C.POINTER(AmgSummary))
+_sig("spmv_amg_level", C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p),
+     C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p))
+_sig("spmv_amg_last_phases", None, _dp)
+_sig("spmv_amg_set_fused", C.c_int, C.c_int)
+_sig("spmv_amg_release", None, C.c_void_p)
+_sig("spmv_amg_release_checked", None, C.c_void_p, C.c_uint64)
+_sig("spmv_amg_apply", C.c_int, C.c_void_p, C.POINTER(LaunchOpts), C.c_int,
+     C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p)
 _sig("spmv_permute_vectors", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
      C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p)
 _sig("spmv_csr_generate", C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -690,6 +727,10 @@ _TWINS = (
      C.c_void_p, C.POINTER(LaunchOpts), C.c_int, C.c_void_p, C.c_int64,
      C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
      C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(CgInfo), C.c_void_p),
+    ("pcg_amg", C.c_int,
+     C.c_void_p, C.POINTER(LaunchOpts), C.c_int, C.c_void_p, C.c_int64,
+     C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_int, C.c_int,
+     C.c_void_p, C.c_size_t, C.POINTER(CgInfo), C.c_void_p),
     ("bicgstab", C.c_int,
      C.c_void_p, C.POINTER(LaunchOpts), C.c_int, C.c_void_p, C.c_int64,
      C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_int, C.c_int,
@@ -1693,6 +1734,21 @@ class _Device:
                          d_scale), k, tol, maxit, check_every, ldb, ldx, work,
                         waves_per_block, group, stream)
 
+    def pcg_amg(self, d_B, d_X, H, k=1, tol=1e-8, maxit=1000, check_every=0,
+                ldb=0, ldx=0, work=None, waves_per_block=0, group=0,
+                stream=None):
+        """cg() preconditioned by one V cycle of an AmgHierarchy H
+        (CsrDevice.amg() of a CSR handle of the same rows): pcg_trsv() word
+        for word with Z = H.apply(R) where that has the plans' solves, k <=
+        H.kmax (`work`: at least pcg_trsv_work_bytes(M, k) bytes).  H is not
+        written and may serve any number of solves, one at a time.
+        -> [CgResult(status, iterations, rr, bb)] * k"""
+        if not isinstance(H, AmgHierarchy):
+            raise ValueError("pcg_amg: H is an AmgHierarchy")
+        return self._cg("pcg_amg", d_B, d_X, (H.h,), k, tol, maxit,
+                        check_every, ldb, ldx, work, waves_per_block, group,
+                        stream)
+
     def bicgstab(self, d_B, d_X, k=1, d_minv=None, tol=1e-8, maxit=1000,
                  check_every=0, ldb=0, ldx=0, work=None, waves_per_block=0,
                  group=0, stream=None):
@@ -2180,6 +2236,57 @@ class CsrDevice(_Device):
                "spmv_csr_permute")
         return CsrDevice(h)
 
+    def aggregate(self, theta=0.0, seed=0, max_rounds=0):
+        """an Aggregation of this (square, f64) handle, rows strictly
+        ascending with their diagonal: the roots are a distance-2 maximal
+        independent set of the strength graph (entry (i, j) strong iff
+        a_ij^2 >= theta^2 |d_i d_j|) found by parallel rounds with the
+        priority fmix32(row ^ seed), every other row joins its strongest
+        strong neighbour's aggregate -- defined to the integer
+        (spmv_engine.h).  More than max_rounds rounds (0: 4096) is
+        OSError(E2BIG)"""
+        theta, seed, max_rounds = float(theta), int(seed), int(max_rounds)
+        if not (theta >= 0.0 and np.isfinite(theta)):
+            raise ValueError("theta=%r: a finite number, 0 or more" % (theta,))
+        if not 0 <= seed < 1 << 32:
+            raise ValueError("seed=%d: a 32-bit unsigned number" % seed)
+        if max_rounds < 0:
+            raise ValueError("max_rounds=%d: 0 (the default) or more"
+                             % max_rounds)
+        return Aggregation(self, theta, seed, max_rounds)
+
+    def amg(self, theta=0.0, sweeps=1, coarse_sweeps=8, min_rows=32,
+            max_levels=16, seed=0, kmax=8):
+        """an AmgHierarchy of this (square, f64) handle: smoothed aggregation
+        (aggregate(theta, seed), P = (I - 4/3 / rho D^-1 A) T, Galerkin
+        products) down to a level of at most min_rows rows or max_levels
+        levels, built on the device and defined to the bit (spmv_engine.h).
+        Its cycle is V(sweeps, sweeps) with damped Jacobi and coarse_sweeps
+        sweeps on the coarsest level, for at most kmax right-hand sides.  The
+        hierarchy BORROWS this handle: keep it alive while the hierarchy is
+        used"""
+        theta = float(theta)
+        sweeps, coarse_sweeps = int(sweeps), int(coarse_sweeps)
+        min_rows, max_levels = int(min_rows), int(max_levels)
+        seed, kmax = int(seed), int(kmax)
+        if not (theta >= 0.0 and np.isfinite(theta)):
+            raise ValueError("theta=%r: a finite number, 0 or more" % (theta,))
+        if not (1 <= sweeps <= 64 and 1 <= coarse_sweeps <= 64):
+            raise ValueError("sweeps=%d, coarse_sweeps=%d: 1..64"
+                             % (sweeps, coarse_sweeps))
+        if min_rows < 1 or not 1 <= max_levels <= AMG_MAX_LEVELS:
+            raise ValueError("min_rows=%d (1 or more), max_levels=%d (1..%d)"
+                             % (min_rows, max_levels, AMG_MAX_LEVELS))
+        if not 0 <= seed < 1 << 32:
+            raise ValueError("seed=%d: a 32-bit unsigned number" % seed)
+        if not 1 <= kmax <= 8:
+            raise ValueError("kmax=%d: 1..8 right-hand sides" % kmax)
+        h = C.c_void_p()
+        _check(_lib.spmv_csr_amg_setup(self.h, theta, sweeps, coarse_sweeps,
+                                       min_rows, max_levels, seed, kmax,
+                                       C.byref(h)), "spmv_csr_amg_setup")
+        return AmgHierarchy(h, self)
+
     def sgs(self, max_levels=0, sweeps=0, kmax=8):
         """an SgsPreconditioner of this (square) handle: its lower and upper
         TrsvPlan and a DevBuffer with diag(A); release() frees the three.
@@ -2365,6 +2472,160 @@ class Colouring:
             if buf is not None:
                 buf.free()
         self.colour = self.perm = None
+
+
+class Aggregation:
+    """The result of CsrDevice.aggregate(): `agg` (DevBuffer, M int32: the
+    aggregate of every row), `aggregates`, `roots`, `rounds`, `widest`,
+    `singletons` (spmv_engine.h, spmv_aggregate_info) and `M`."""
+
+    agg = None
+    _RANK = 1
+
+    def __init__(self, A, theta, seed, max_rounds):
+        self.M = A.M
+        info = AggregateInfo()
+        try:
+            self.agg = DevBuffer(max(A.M, 1) * 4)
+            _check(_lib.spmv_csr_aggregate(A.h, theta, seed, max_rounds,
+                                           self.agg.ptr, C.byref(info)),
+                   "spmv_csr_aggregate")
+        except BaseException:
+            self.release()
+            raise
+        self.aggregates, self.roots = info.aggregates, info.roots
+        self.rounds, self.widest = info.rounds, info.widest
+        self.singletons = info.singletons
+        _live.add(self)
+
+    def _released(self):
+        return self.agg is None
+
+    def _release_now(self):
+        self.release()
+
+    def release(self):
+        if self.agg is not None:
+            self.agg.free()
+        self.agg = None
+
+
+AmgLevel = collections.namedtuple("AmgLevel", "A P PT w")
+
+
+class AmgHierarchy:
+    """A smoothed-aggregation hierarchy resident in HBM (spmv_engine.h,
+    spmv_amg; CsrDevice.amg makes one).  It owns its coarse operators,
+    transfers, weights and scratch and borrows the fine handle (`fine`)."""
+
+    h = None
+    _RANK = 2  # released before the handle it borrows
+
+    def __init__(self, handle, fine):
+        self.h = handle
+        self.fine = fine
+        self.gen = _lib.spmv_handle_generation(self.h)
+        if not self.gen:
+            raise OSError(9, "spmv_handle_generation: %r is not a live "
+                             "hierarchy of this library" % (self.h,))
+        self.kmax = self._summary().kmax
+        _live.add(self)
+
+    def _released(self):
+        return not self.h
+
+    def _release_now(self):
+        self.release()
+
+    def _summary(self):
+        s = AmgSummary()
+        _check(_lib.spmv_amg_info(self.h, C.byref(s)), "spmv_amg_info")
+        return s
+
+    @property
+    def info(self):
+        """dict(levels, sweeps, coarse_sweeps, kmax, launches, complexity,
+        scratch_bytes; rows, entries, rho, omega, rounds, aggregates: one
+        per level)"""
+        s = self._summary()
+        n = s.levels
+        out = dict(levels=n, sweeps=s.sweeps, coarse_sweeps=s.coarse_sweeps,
+                   kmax=s.kmax, launches=s.launches, complexity=s.complexity,
+                   scratch_bytes=s.scratch_bytes)
+        for name in ("rows", "entries", "rho", "omega", "rounds",
+                     "aggregates"):
+            out[name] = list(getattr(s, name))[:n]
+        return out
+
+    def level(self, l):
+        """AmgLevel(A, P, PT, w) of level l downloaded to the host: each
+        matrix as (M, N, IRP, JA, AS) numpy arrays (P and PT None on the
+        coarsest level), w as M doubles"""
+        A, P, PT, w = (C.c_void_p() for _ in range(4))
+        _check(_lib.spmv_amg_level(self.h, int(l), C.byref(A), C.byref(P),
+                                   C.byref(PT), C.byref(w)),
+               "spmv_amg_level")
+
+        def host(h):
+            if not h.value:
+                return None
+            p = _CSRp()
+            _check(_lib.spmv_csr_download(h, C.byref(p)), "spmv_csr_download")
+            M, N = p.contents.M, p.contents.N
+            IRP, JA, AS = (np.array(a) for a in csr_arrays(p))
+            csr_free(p)
+            return M, N, IRP, JA, AS
+        mats = [host(h) for h in (A, P, PT)]
+        M = mats[0][0]
+        wv = np.empty(M, np.float64)
+        if M:
+            _check(_lib.spmv_copy_d2h(wv.ctypes.data, w, wv.nbytes),
+                   "spmv_copy_d2h")
+        return AmgLevel(mats[0], mats[1], mats[2], wv)
+
+    def apply(self, d_R, d_Z, k=1, ldr=0, ldz=0, waves_per_block=0,
+              stream=None):
+        """Z = V(R): one V cycle for k <= kmax interleaved vectors (ldr, ldz
+        >= k or 0), asynchronous on `stream` and capturable.  The bits are
+        fixed by the contract in spmv_engine.h and depend on neither
+        waves_per_block nor k.  Two applies of one hierarchy must not
+        overlap in time"""
+        k, ldr, ldz = int(k), int(ldr), int(ldz)
+        if not 1 <= k <= self.kmax:
+            raise ValueError("k=%r: 1..kmax=%d vectors per apply"
+                             % (k, self.kmax))
+        if (ldr and ldr < k) or (ldz and ldz < k):
+            raise ValueError("ldr=%d, ldz=%d: at least k=%d (or 0)"
+                             % (ldr, ldz, k))
+        o = _opts(waves_per_block)
+        _check(_lib.spmv_amg_apply(self.h, C.byref(o), k, d_R, ldr, d_Z, ldz,
+                                   stream), "spmv_amg_apply")
+
+    def release(self):
+        h, self.h = self.h, None
+        if h and _closed is False and _lib is not None:
+            _lib.spmv_amg_release_checked(h, self.gen)
+
+    def __del__(self):
+        if _closed is False:  # None / True at or after interpreter shutdown
+            self.release()
+
+
+def amg_set_fused(mode):
+    """MEASUREMENT and tests: how every hierarchy sweeps from now on -- 0 by
+    the composition (launch_axpby and a vector kernel), 2 by the fused kernel
+    wherever it can run, 1 (the default) by the measured rule (fused from
+    k = 4 on); the bits of a cycle are the same.  -> the previous mode"""
+    return _check(_lib.spmv_amg_set_fused(int(mode)), "spmv_amg_set_fused")
+
+
+def amg_last_phases():
+    """host-clock ms of the last successful CsrDevice.amg() of this process:
+    dict(rho_w, aggregate, prolongator, transpose, galerkin, finish)"""
+    ms = (C.c_double * 6)()
+    _lib.spmv_amg_last_phases(ms)
+    return dict(zip(("rho_w", "aggregate", "prolongator", "transpose",
+                     "galerkin", "finish"), ms))
 
 
 def _perm_ptr(p, what):

@@ -19,7 +19,9 @@
  * k_cg_* and the k_pcg_* kernel of a pair are one text.  The solver
  * preconditioned by triangular plans (spmv_*_pcg_trsv) has no kernel of its
  * own: pcgt_start / pcgt_iterate below enqueue the plain vector kernels, the
- * plans' solves and the finalising kernels of the preconditioned pass.
+ * plans' solves and the finalising kernels of the preconditioned pass.  The
+ * solver preconditioned by an AMG cycle (spmv_*_pcg_amg) is the same text with
+ * the cycle (cg_plans.apply, engine.hip) where the plans' solves are.
  *
  * The dot order, the tile of a vector kernel (cg_lanes), the halving trees and
  * the launch macros are in cg_common.h, shared with the other solvers.
@@ -177,9 +179,12 @@ struct cg_run {
  */
 static void pcgt_apply(const cg_run &c) {
     const cg_plans &pl = *c.plans;
-    int rc = trsv_solve_dev(pl.first, pl.waves, c.k, c.R, c.k, c.Z, c.k, NULL,
-                            c.s);
-    if (!rc && pl.second)
+    /* the one place the two stored-Z preconditioners part: the cycle of a
+     * hierarchy (spmv_*_pcg_amg) or the plans' solves */
+    int rc = pl.apply ? pl.apply(pl.ctx, pl.waves, c.k, c.R, c.Z, c.s)
+                      : trsv_solve_dev(pl.first, pl.waves, c.k, c.R, c.k, c.Z,
+                                       c.k, NULL, c.s);
+    if (!rc && !pl.apply && pl.second)
         rc = trsv_solve_dev(pl.second, pl.waves, c.k, c.Z, c.k, c.Z, c.k,
                             pl.scale, c.s);
     if (rc && !*c.err)

@@ -20,6 +20,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "amg_plan.h"
 #include "err.h"
 #include "hip_common.h"
 #include "hip_csr.h"
@@ -2405,6 +2406,336 @@ static int cg_trsv(const D *d, const spmv_launch_opts *opts, int k,
                     check_every, d_work, work_bytes, info, (hipStream_t)stream);
 }
 
+/* ------------------------------------------------------------------ */
+/* smoothed-aggregation AMG (amg_kernels.hip, amg_plan.h)               */
+/* ------------------------------------------------------------------ */
+
+struct amg_level {
+    const spmv_csr_dev *A; /* level 0: borrowed; below: owned */
+    spmv_csr_dev *P, *PT;  /* NULL on the coarsest level */
+    double *w;             /* M doubles */
+    double rho, omega;
+    int rounds, aggregates;
+};
+struct spmv_amg {
+    int levels, sweeps, coarse_sweeps, kmax, M;
+    amg_level lv[AMG_MAX_LEVELS];
+    amg_layout lay;
+    double *scratch;
+    uint64_t fine_gen; /* the generation of lv[0].A at setup */
+};
+static_assert(AMG_MAX_LEVELS == SPMV_AMG_MAX_LEVELS && AMG_MAX_K == 8,
+              "amg_plan.h and spmv_engine.h agree");
+
+static double g_amg_phases[6];
+
+static void amg_teardown(spmv_amg *H) {
+    for (int l = 0; l < H->levels; ++l) {
+        amg_level &L = H->lv[l];
+        (void)hipFree(L.w);
+        spmv_csr_release(L.P); /* NULL: ignored */
+        spmv_csr_release(L.PT);
+        if (l > 0)
+            spmv_csr_release((spmv_csr_dev *)L.A);
+    }
+    (void)hipFree(H->scratch);
+    free(H);
+}
+
+/* the caller has checked A (live, square, f64, with its source) and the
+ * numbers */
+static int amg_setup(const spmv_csr_dev *A0, double theta, int sweeps,
+                     int coarse_sweeps, int min_rows, int max_levels,
+                     uint32_t seed, int kmax, spmv_amg **out) {
+    int rc = 0;
+    double ph[6] = {0, 0, 0, 0, 0, 0};
+    int rows[AMG_MAX_LEVELS];
+    int *d_agg = NULL;
+    spmv_csr_dev *T = NULL;
+    const spmv_csr_dev *A = A0;
+    const auto now = [] { return 1e3 * panels_ops::now_s(); };
+    double t = now();
+    const auto lap = [&](int phase) {
+        const double n = now();
+        ph[phase] += n - t;
+        t = n;
+    };
+    spmv_amg *H = (spmv_amg *)calloc(1, sizeof *H);
+    if (!H)
+        return -ENOMEM;
+    H->sweeps = sweeps;
+    H->coarse_sweeps = coarse_sweeps;
+    H->kmax = kmax;
+    H->M = A0->M;
+    H->lv[0].A = A0;
+    H->fine_gen = spmv_handle_generation(A0);
+    H->levels = 1;
+    rc = amg_check_dev(A0, NULL, 0);
+    if (rc)
+        goto fail;
+    for (int l = 0;; ++l) {
+        amg_level &L = H->lv[l];
+        spmv_aggregate_info ai;
+        spmv_csr_dev *C = NULL;
+        rows[l] = A->M;
+        HIP_TRY(hipMalloc((void **)&L.w,
+                          (size_t)(A->M > 0 ? A->M : 1) * sizeof(double)));
+        rc = amg_rho_dev(A, L.w, &L.rho, 0);
+        if (rc)
+            goto fail;
+        if (!std::isfinite(L.rho) || !(L.rho > 0.0)) {
+            rc = -EDOM;
+            goto fail;
+        }
+        L.omega = (4.0 / 3.0) / L.rho;
+        rc = amg_w_dev(A->M, L.omega, L.w, 0);
+        if (rc)
+            goto fail;
+        lap(0);
+        if (A->M <= min_rows || l + 1 == max_levels)
+            break;
+        HIP_TRY(hipMalloc((void **)&d_agg, (size_t)A->M * sizeof(int)));
+        rc = amg_aggregate_dev(A, theta * theta, seed, AMG_DEFAULT_MAX_ROUNDS,
+                               d_agg, &ai, 0);
+        if (rc)
+            goto fail;
+        L.rounds = ai.rounds;
+        L.aggregates = ai.aggregates;
+        lap(1);
+        if (ai.aggregates == A->M)
+            break;
+        rc = csr_alloc_dev(A->M, ai.aggregates, A->M, 8, &T);
+        if (rc)
+            goto fail;
+        rc = amg_tentative_dev(A->M, d_agg, T, 0);
+        if (!rc)
+            rc = finish_csr_handle(T, NULL);
+        if (!rc)
+            rc = spmv_csr_spgemm(A, T, &L.P, NULL);
+        if (!rc)
+            rc = amg_smooth_p_dev(L.P, d_agg, L.w, 0);
+        if (rc)
+            goto fail;
+        spmv_csr_release(T);
+        T = NULL;
+        (void)hipFree(d_agg); /* waits for the smoothing */
+        d_agg = NULL;
+        lap(2);
+        rc = spmv_csr_transpose(L.P, &L.PT);
+        if (rc)
+            goto fail;
+        lap(3);
+        rc = spmv_csr_galerkin(A, L.P, L.PT, &C, NULL);
+        if (rc)
+            goto fail;
+        H->lv[l + 1].A = C;
+        H->levels = l + 2;
+        A = C;
+        lap(4);
+    }
+    rc = amg_layout_make(rows, H->levels, kmax, &H->lay);
+    if (rc)
+        goto fail;
+    HIP_TRY(hipMalloc((void **)&H->scratch,
+                      (size_t)(H->lay.doubles > 0 ? H->lay.doubles : 1) *
+                          sizeof(double)));
+    HIP_TRY(hipStreamSynchronize(0));
+    lap(5);
+    memcpy(g_amg_phases, ph, sizeof ph);
+    live_add(H);
+    *out = H;
+    return 0;
+fail:
+    (void)hipStreamSynchronize(0);
+    (void)hipFree(d_agg);
+    spmv_csr_release(T); /* NULL: ignored */
+    amg_teardown(H);
+    return rc;
+}
+
+/* MEASUREMENT (spmv_amg_set_fused): 0 makes every level sweep by the
+ * composition, 2 by the fused kernel wherever it can run, 1 (the default) by
+ * the measured rule of amg_plan.h (amg_use_fused); the bits are the same */
+static int g_amg_fused = 1;
+
+static bool amg_level_fused(const spmv_amg *H, int l, int k) {
+    return amg_use_fused(g_amg_fused, k) && amg_sweep_fusable(H->lv[l].A);
+}
+
+/* Z = V(R): the launch list of spmv_amg_apply (spmv_engine.h).  The caller
+ * has checked everything; waves 0 = the default of every level's launch.
+ *
+ * A level sweeps by the fused kernel (amg_sweep_dev: x_new to the other buffer
+ * of a ping-pong, `cur` and `alt` below) unless its handle has long rows; then
+ * by the composition (launch_axpby(-1, 1) into an r that holds b, and the
+ * vector kernel, in place).  Both give the same bits.  Level 0's iterate must
+ * END in the caller's Z: it starts in the buffer that the level's swaps lead
+ * back from (amg_start_buffer). */
+static int amg_cycle(const spmv_amg *H, int waves, int k, const double *R,
+                     int64_t ldr, double *Z, int64_t ldz, hipStream_t s) {
+    spmv_launch_opts o;
+    memset(&o, 0, sizeof o);
+    o.waves_per_block = waves;
+    int rc = 0;
+    const int last = H->levels - 1;
+    struct view {
+        const double *b;
+        double *cur, *alt, *r; /* the iterate, the other buffer, r (ld = k) */
+        int64_t ldb, ldcur, ldalt;
+        bool fused;
+        int w; /* workgroup size of the fused sweep, in wavefronts */
+    } v[AMG_MAX_LEVELS];
+    for (int l = 0; l <= last; ++l) {
+        view &t = v[l];
+        t.fused = amg_level_fused(H, l, k);
+        t.w = pick_waves(&o, default_waves(g_csr_waves, H->lv[l].A->M));
+        t.b = l ? H->scratch + H->lay.b[l] : R;
+        t.ldb = l ? k : ldr;
+        t.r = H->scratch + H->lay.r[l];
+        t.cur = l ? H->scratch + H->lay.x[l] : Z;
+        t.ldcur = l ? k : ldz;
+        t.alt = H->scratch + H->lay.x2[l];
+        t.ldalt = k;
+        const int swaps = !t.fused ? 0
+                          : l == last ? H->coarse_sweeps - 1
+                                      : 2 * H->sweeps - 1;
+        if (amg_start_buffer(swaps)) {
+            std::swap(t.cur, t.alt);
+            std::swap(t.ldcur, t.ldalt);
+        }
+    }
+    /* n sweeps.  Composed: behind an r that holds b; refill_last: r = b
+     * behind the last one too */
+    const auto sweeps = [&](int l, int n, bool refill_last) {
+        const amg_level &L = H->lv[l];
+        view &t = v[l];
+        for (int i = 0; i < n && !rc; ++i) {
+            if (t.fused) {
+                amg_sweep_dev(L.A, t.w, k, t.cur, t.ldcur, t.b, t.ldb, L.w,
+                              t.alt, t.ldalt, s);
+                std::swap(t.cur, t.alt);
+                std::swap(t.ldcur, t.ldalt);
+                continue;
+            }
+            rc = axpby_direct(L.A, &o, k, -1.0, 1.0, t.cur, t.ldcur, t.r, k, s);
+            amg_update_dev(L.A->M, k, i + 1 < n || refill_last, L.w, t.b, t.ldb,
+                           t.cur, t.ldcur, t.r, s);
+        }
+    };
+    for (int l = 0; l <= last && !rc; ++l) {
+        const amg_level &L = H->lv[l];
+        view &t = v[l];
+        amg_first_dev(L.A->M, k, L.w, t.b, t.ldb, t.cur, t.ldcur,
+                      t.fused ? NULL : t.r, s);
+        if (l == last) {
+            sweeps(l, H->coarse_sweeps - 1, false);
+            break;
+        }
+        sweeps(l, H->sweeps - 1, true);
+        if (rc)
+            break;
+        if (t.fused) /* r = b - A x: the residual mode */
+            amg_sweep_dev(L.A, t.w, k, t.cur, t.ldcur, t.b, t.ldb, NULL, t.r, k,
+                          s);
+        else
+            rc = axpby_direct(L.A, &o, k, -1.0, 1.0, t.cur, t.ldcur, t.r, k, s);
+        if (!rc) /* b_c = PT r */
+            rc = multi_direct(L.PT, &o, k, t.r, k, (double *)v[l + 1].b, k, s);
+    }
+    for (int l = last - 1; l >= 0 && !rc; --l) {
+        const amg_level &L = H->lv[l];
+        view &t = v[l];
+        /* x += P x_c */
+        rc = axpby_direct(L.P, &o, k, 1.0, 1.0, v[l + 1].cur, v[l + 1].ldcur,
+                          t.cur, t.ldcur, s);
+        if (!t.fused)
+            cg_launch_copy(k, L.A->M, t.b, t.ldb, t.r, k, s);
+        sweeps(l, H->sweeps, false);
+    }
+    if (!rc)
+        rc = hip_errno(hipGetLastError());
+    return rc;
+}
+
+/* the borrowed fine handle is still the one the hierarchy was built from: a
+ * live handle at that address WITH THE GENERATION it had at setup (an address
+ * the allocator gave to a newer handle is not it) */
+static bool amg_fine_alive(const spmv_amg *H) {
+    return spmv_handle_generation(H->lv[0].A) == H->fine_gen;
+}
+
+/* NULL -> -EINVAL; not a live hierarchy -> -EBADF, or -ENODEV without a
+ * device; a hierarchy whose A_0 was released -> -EBADF */
+static int amg_ok(const spmv_amg *H) {
+    if (!H)
+        return -EINVAL;
+    if (!live_has(H))
+        return spmv_device_count() == 0 ? -ENODEV : -EBADF;
+    if (!amg_fine_alive(H))
+        return -EBADF;
+    if (!has_source(H->lv[0].A))
+        return -ENODATA;
+    return 0;
+}
+
+static int amg_apply(const spmv_amg *H, const spmv_launch_opts *opts, int k,
+                     const double *d_R, int64_t ldr, double *d_Z, int64_t ldz,
+                     void *stream) {
+    const int ok = amg_ok(H);
+    if (ok)
+        return ok;
+    if (k < 1 || k > H->kmax)
+        return -EINVAL;
+    if (ldr == 0)
+        ldr = k;
+    if (ldz == 0)
+        ldz = k;
+    if (ldr < k || ldz < k || !d_R || !d_Z || d_R == d_Z)
+        return -EINVAL;
+    if (opts) {
+        if (opts->waves_per_block < 0 || opts->waves_per_block > 16 ||
+            opts->group || opts->variant)
+            return -EINVAL;
+        for (int r : opts->reserved)
+            if (r)
+                return -EINVAL;
+    }
+    (void)hipGetLastError(); /* an earlier caller's unread error is not ours */
+    return amg_cycle(H, opts ? opts->waves_per_block : 0, k, d_R, ldr, d_Z,
+                     ldz, (hipStream_t)stream);
+}
+
+static int amg_apply_of(const void *ctx, int waves, int k, const double *R,
+                        double *Z, hipStream_t s) {
+    return amg_cycle((const spmv_amg *)ctx, waves, k, R, k, Z, k, s);
+}
+
+/* spmv_*_pcg_amg: cg_trsv with the cycle of H where that has the plans */
+template <typename D>
+static int cg_amg(const D *d, const spmv_launch_opts *opts, int k,
+                  const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                  const spmv_amg *H, double tol, int maxit, int check_every,
+                  void *d_work, size_t work_bytes, spmv_cg_info *info,
+                  void *stream) {
+    const int rc = solver_check(
+        d, opts, k, d_B, &ldb, d_X, &ldx, tol, maxit, &check_every, info, [&] {
+            if (!H)
+                return -EINVAL;
+            if (!live_has(H) || !amg_fine_alive(H))
+                return -EBADF;
+            if (H->M != d->M || k > H->kmax)
+                return -EINVAL;
+            return has_source(H->lv[0].A) ? 0 : -ENODATA;
+        });
+    if (rc)
+        return rc < 0 ? rc : 0;
+    const cg_matrix A = cg_matrix_of(d, opts);
+    const cg_plans pl = {NULL, NULL, NULL, opts ? opts->waves_per_block : 0,
+                         amg_apply_of, H};
+    return cg_solve(&A, k, d_B, ldb, d_X, ldx, NULL, &pl, tol, maxit,
+                    check_every, d_work, work_bytes, info, (hipStream_t)stream);
+}
+
 /* BiCGStab (bicgstab_kernels.hip): cg's checks and cg's view of the matrix;
  * d_minv may be NULL (no preconditioner) */
 template <typename D>
@@ -3173,6 +3504,14 @@ static int copy_tune_log(const D *d, char *buf, size_t len) {
                        d_scale, tol, maxit, check_every, d_work, work_bytes,   \
                        info, stream);                                          \
     }                                                                          \
+    int spmv_##fmt##_pcg_amg(                                                  \
+        const D *d, const spmv_launch_opts *opts, int k, const double *d_B,    \
+        int64_t ldb, double *d_X, int64_t ldx, const spmv_amg *H, double tol,  \
+        int maxit, int check_every, void *d_work, size_t work_bytes,           \
+        spmv_cg_info *info, void *stream) {                                    \
+        return cg_amg(d, opts, k, d_B, ldb, d_X, ldx, H, tol, maxit,           \
+                      check_every, d_work, work_bytes, info, stream);          \
+    }                                                                          \
     int spmv_##fmt##_bicgstab(const D *d, const spmv_launch_opts *opts,        \
                               int k, const double *d_B, int64_t ldb,           \
                               double *d_X, int64_t ldx, const double *d_minv,  \
@@ -3300,6 +3639,126 @@ extern "C" {
 
 HANDLE_API(csr, spmv_csr_dev, launch_rows)
 HANDLE_API(hll, spmv_hll_dev, launch_blocks)
+
+/* ---- smoothed-aggregation AMG: the checked entry points ---- */
+int spmv_csr_aggregate(const spmv_csr_dev *A, double theta, uint32_t seed,
+                       int max_rounds, int *d_agg, spmv_aggregate_info *info) {
+    if (!A || !(theta >= 0.0) || !std::isfinite(theta) || max_rounds < 0)
+        return -EINVAL;
+    if (spmv_device_count() == 0)
+        return -ENODEV; /* no handle can be live: the more useful answer */
+    HANDLE_OK(A);
+    if (A->M != A->N)
+        return -EINVAL;
+    if (A->value_bytes != 8)
+        return -ENOTSUP;
+    if (!A->ja && A->NZ > 0)
+        return -ENODATA; /* spmv_csr_release_source() */
+    return amg_aggregate_dev(A, theta * theta, seed, amg_max_rounds(max_rounds),
+                             d_agg, info, 0);
+}
+
+int spmv_csr_amg_setup(const spmv_csr_dev *A, double theta, int sweeps,
+                       int coarse_sweeps, int min_rows, int max_levels,
+                       uint32_t seed, int kmax, spmv_amg **out) {
+    if (out)
+        *out = NULL; /* on ANY error, the argument checks included */
+    if (!A || !out || !(theta >= 0.0) || !std::isfinite(theta) || sweeps < 1 ||
+        sweeps > AMG_MAX_SWEEPS || coarse_sweeps < 1 ||
+        coarse_sweeps > AMG_MAX_SWEEPS || min_rows < 1 || max_levels < 0 ||
+        max_levels > AMG_MAX_LEVELS || kmax < 1 || kmax > AMG_MAX_K)
+        return -EINVAL;
+    if (spmv_device_count() == 0)
+        return -ENODEV; /* no handle can be live: the more useful answer */
+    HANDLE_OK(A);
+    if (A->M != A->N)
+        return -EINVAL;
+    if (A->value_bytes != 8)
+        return -ENOTSUP;
+    if (!A->ja && A->NZ > 0)
+        return -ENODATA; /* spmv_csr_release_source() */
+    return amg_setup(A, theta, sweeps, coarse_sweeps, min_rows,
+                     max_levels ? max_levels : 16, seed, kmax, out);
+}
+
+int spmv_amg_info(const spmv_amg *H, spmv_amg_summary *out) {
+    if (!H || !out)
+        return -EINVAL;
+    if (!live_has(H))
+        return spmv_device_count() == 0 ? -ENODEV : -EBADF;
+    memset(out, 0, sizeof *out);
+    out->levels = H->levels;
+    out->sweeps = H->sweeps;
+    out->coarse_sweeps = H->coarse_sweeps;
+    out->kmax = H->kmax;
+    /* level 0 is borrowed: its numbers were the handle's when it was live */
+    const bool fine = amg_fine_alive(H);
+    for (int l = 0; l < H->levels; ++l) {
+        const amg_level &L = H->lv[l];
+        out->rows[l] = l || fine ? L.A->M : H->M;
+        out->entries[l] = l || fine ? L.A->NZ : 0;
+        out->rounds[l] = L.rounds;
+        out->aggregates[l] = L.aggregates;
+        out->rho[l] = L.rho;
+        out->omega[l] = L.omega;
+        out->launches += amg_level_launches(
+            l == H->levels - 1, H->sweeps, H->coarse_sweeps,
+            (l || fine) && amg_level_fused(H, l, H->kmax));
+    }
+    out->complexity = amg_complexity(out->entries, H->levels);
+    out->scratch_bytes = H->lay.doubles * 8;
+    return 0;
+}
+
+int spmv_amg_level(const spmv_amg *H, int level, const spmv_csr_dev **A,
+                   const spmv_csr_dev **P, const spmv_csr_dev **PT,
+                   const double **d_w) {
+    if (!H)
+        return -EINVAL;
+    if (!live_has(H))
+        return spmv_device_count() == 0 ? -ENODEV : -EBADF;
+    if (level < 0 || level >= H->levels)
+        return -EINVAL;
+    const amg_level &L = H->lv[level];
+    if (A)
+        *A = L.A;
+    if (P)
+        *P = L.P;
+    if (PT)
+        *PT = L.PT;
+    if (d_w)
+        *d_w = L.w;
+    return 0;
+}
+
+int spmv_amg_set_fused(int on) {
+    const int was = g_amg_fused;
+    if (on < 0 || on > 2)
+        return -EINVAL;
+    g_amg_fused = on;
+    return was;
+}
+
+void spmv_amg_last_phases(double ms[6]) {
+    if (ms)
+        memcpy(ms, g_amg_phases, sizeof g_amg_phases);
+}
+
+void spmv_amg_release(spmv_amg *H) {
+    if (H && live_take(H))
+        amg_teardown(H);
+}
+
+void spmv_amg_release_checked(spmv_amg *H, uint64_t generation) {
+    if (H && generation && live_take(H, generation))
+        amg_teardown(H);
+}
+
+int spmv_amg_apply(const spmv_amg *H, const spmv_launch_opts *opts, int k,
+                   const double *d_R, int64_t ldr, double *d_Z, int64_t ldz,
+                   void *stream) {
+    return amg_apply(H, opts, k, d_R, ldr, d_Z, ldz, stream);
+}
 
 int64_t spmv_cg_work_bytes(int M, int k) { return cg_work_bytes(M, k, 0); }
 int64_t spmv_pcg_work_bytes(int M, int k) { return cg_work_bytes(M, k, 1); }

@@ -3,7 +3,7 @@
  * (engine.hip, csr_kernels.hip, hll_kernels.hip, multi_kernels.hip,
  * cg_kernels.hip, bicgstab_kernels.hip, cgls_kernels.hip, minres_kernels.hip,
  * diag_kernels.hip, transpose_kernels.hip, trsv_kernels.hip, ic0_kernels.hip,
- * ilu0_kernels.hip, panels.hip, mgpu.hip, and
+ * ilu0_kernels.hip, amg_kernels.hip, panels.hip, mgpu.hip, and
  * mat_ref.h on behalf of the first and the last).
  * Not installed.
  */
@@ -539,6 +539,12 @@ struct cg_plans {
     const spmv_trsv_plan *first, *second; /* second may be NULL */
     const double *scale;                  /* M doubles or NULL */
     int waves;
+    /* the other preconditioner with a stored Z (spmv_*_pcg_amg): apply !=
+     * NULL makes Z = apply(ctx, waves, k, R) where the plans' solves are, R
+     * and Z with ld = k; first, second and scale are then unused */
+    int (*apply)(const void *ctx, int waves, int k, const double *R, double *Z,
+                 hipStream_t s);
+    const void *ctx;
 };
 /* minv == NULL: plain (spmv_*_cg); else preconditioned with z = minv .* r,
  * minv[M] (spmv_*_pcg, pre == 1): the same loop, one more set of partial sums
@@ -719,6 +725,41 @@ void csr_spgemm_last_phases(double ms[4]);
 int permute_vectors_dev(const int *p, int M, int k, int inverse,
                         const double *in, int64_t ldin, double *out,
                         int64_t ldout, hipStream_t s);
+
+/*
+ * Smoothed-aggregation AMG (amg_kernels.hip; spmv_csr_aggregate,
+ * spmv_csr_amg_setup, spmv_amg_apply).  The caller has checked the handles
+ * (square, f64, with their sources).  amg_check_dev: 0, -EDOM (a column
+ * outside) or -EINVAL (a row not strictly ascending, or without its diagonal);
+ * d_diag (M doubles or NULL) receives the diagonal.  amg_aggregate_dev makes
+ * that check itself, blocks, frees its scratch on every path and leaves d_agg
+ * and *info untouched on an error.  amg_rho_dev: d_w receives the diagonal and
+ * *rho the Gershgorin bound of D^-1 A (one read-back); amg_w_dev then turns
+ * d_w into w = omega / d in place.  amg_tentative_dev fills the arrays of an
+ * M x n handle with M entries; amg_smooth_p_dev turns the values of A T into
+ * those of P in place.  amg_first_dev / amg_update_dev: the two vector
+ * kernels of a sweep (r has ld = k), asynchronous.
+ */
+int amg_check_dev(const spmv_csr_dev *A, double *d_diag, hipStream_t s);
+int amg_aggregate_dev(const spmv_csr_dev *A, double theta2, uint32_t seed,
+                      int max_rounds, int *d_agg, spmv_aggregate_info *info,
+                      hipStream_t s);
+int amg_rho_dev(const spmv_csr_dev *A, double *d_w, double *rho, hipStream_t s);
+int amg_w_dev(int M, double omega, double *d_w, hipStream_t s);
+int amg_tentative_dev(int M, const int *d_agg, spmv_csr_dev *T, hipStream_t s);
+int amg_smooth_p_dev(spmv_csr_dev *AT, const int *d_agg, const double *d_w,
+                     hipStream_t s);
+void amg_first_dev(int M, int k, const double *w, const double *b, int64_t ldb,
+                   double *x, int64_t ldx, double *r, hipStream_t s);
+/* the fused sweep (k_amg_sweep): W NULL is its residual mode.  Only for a
+ * handle without long rows (amg_sweep_fusable); OUT apart from X */
+bool amg_sweep_fusable(const spmv_csr_dev *A);
+void amg_sweep_dev(const spmv_csr_dev *A, int waves, int k, const double *X,
+                   int64_t ldx, const double *B, int64_t ldb, const double *W,
+                   double *OUT, int64_t ldo, hipStream_t s);
+void amg_update_dev(int M, int k, int refill, const double *w, const double *b,
+                    int64_t ldb, double *x, int64_t ldx, double *r,
+                    hipStream_t s);
 
 /* kernel launchers (csr_kernels.hip / hll_kernels.hip) */
 int csr_launch_kernel(const spmv_csr_dev *A, int kernel, int waves, int group,
