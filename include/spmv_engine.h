@@ -757,9 +757,10 @@ int spmv_permute_vectors(const int *d_new_of_old, int M, int k, int inverse,
  * spmv_csr_transpose and released.  The intermediate A P is released.  Errors
  * as the calls it is made of; info (or NULL) describes the SECOND product.
  *
- * Not in scope: C = alpha A + beta B, a masked or filtered product, reuse of
- * a symbolic pass, HLL and compact handles as operands, an f32 result
- * (spmv_csr_to_f32 makes one), B with duplicates or unsorted rows.
+ * Not in scope: a masked or filtered product, reuse of a symbolic pass, HLL
+ * and compact handles as operands, an f32 result (spmv_csr_to_f32 makes one),
+ * B with duplicates or unsorted rows.  (C = alpha A + beta B: spmv_csr_add
+ * below.)
  */
 typedef struct spmv_spgemm_info {
     int64_t products;       /* sum over entries (r,k) of A of len(row k of B) */
@@ -780,6 +781,102 @@ void spmv_spgemm_last_phases(double ms[4]);
 int spmv_csr_galerkin(const spmv_csr_dev *A, const spmv_csr_dev *P,
                       const spmv_csr_dev *PT /* or NULL */, spmv_csr_dev **out,
                       spmv_spgemm_info *info /* or NULL */);
+/*
+ * The sparse sum on the device: spmv_csr_add makes a NEW, ordinary M x N CSR
+ * handle C = alpha A + beta B from two M x N handles.  Each operand is f64 or
+ * f32-stored (f32 values are widened exactly); C is f64 and owns all its
+ * arrays.  B may be A itself; both are unchanged and may be released
+ * afterwards.  Everything that works on a handle works on C.  The call blocks.
+ *
+ * THE RESULT IS DEFINED TO THE BYTE.  THE ROWS OF BOTH OPERANDS MUST BE
+ * STRICTLY ASCENDING BY COLUMN (what spmv_csr_permute and a double
+ * spmv_csr_transpose give for a source without duplicates).  Row r of C holds
+ * the union of the two rows' columns, once each, ascending; the pattern never
+ * depends on the values.  With ta = rn(alpha a) and tb = rn(beta b), the value
+ * of a column is
+ *     ta              stored in A only,
+ *     tb              stored in B only,
+ *     rn(ta + tb)     stored in both, ta the left operand.
+ * Each operation is rounded once; nothing is fused: no multiply-add anywhere.
+ * So cancellation and explicit zeros store a 0.0 (A - A has A's pattern full
+ * of +0.0), a lone -0.0 under alpha = 1 keeps its sign, alpha == 0 is no
+ * special case (the union stays, 0 * inf is a NaN in that entry only), and
+ * inf - inf is a NaN in that entry and nowhere else.  The bytes do not depend
+ * on scheduling, nor on which size class served a row.
+ *
+ * How: two passes over the rows, each a merge of two ascending index lists by
+ * rank.  The count pass reads only IRP and JA and writes len_A + len_B -
+ * matches per row; the exclusive scan of the transposition makes C's IRP; the
+ * total comes back in one small read-back before C is allocated; the fill
+ * pass writes JA and AS.  Every position is computed, none comes from an
+ * atomic: entry i of A's row lands at i + lower_bound_B(column) - (matched
+ * entries of A before i), an unmatched entry j of B at j +
+ * lower_bound_A(column) - (matched entries of B before j); a matched pair is
+ * written by its A-side lane.  Every slot of C is written exactly once, by
+ * one lane.  No workgroup waits for another.  Two size classes by len_A(r) +
+ * len_B(r): up to *edge a group of lanes per row (its width one of widths[],
+ * the smallest that is not below the mean (NZ_A + NZ_B) / M), beyond it a
+ * workgroup of *threads lanes per row; both walk a row in chunks of their
+ * width and carry the matched-prefix count across chunks.  spmv_add_shape
+ * reports these constants (host arithmetic, no device; any out-pointer may be
+ * NULL; widths has room for 8 ints, *n_widths of them are written).
+ *
+ * spmv_add_set_class is for MEASUREMENT and for the tests: 0 the rule above,
+ * 1 every row by lane groups, 2 every row by the workgroup class.  Returns the
+ * previous mode, -EINVAL for another value.  The bytes of C do not depend on
+ * it.  Not thread-safe.  Mode 2 is one workgroup per row, whatever its length:
+ * meant for matrices of at most 2^24 rows (a larger launch is refused by the
+ * runtime, -EINVAL, and creates nothing).  spmv_add_last_phases: host-clock ms of the last
+ * successful spmv_csr_add of this process -- [0] checks, [1] count and scan,
+ * [2] allocation, fill and the finishing of the handle.  Not thread-safe.
+ *
+ * Errors, in this order: NULL A, B or out, or a non-finite alpha or beta
+ * -EINVAL; no device -ENODEV; a dead handle -EBADF; shapes differ -EINVAL;
+ * either handle after spmv_csr_release_source -ENODATA; a column outside
+ * [0, N) -EDOM; a row of either operand not strictly ascending -EINVAL (a
+ * device check, before anything is allocated for the result); more than
+ * INT32_MAX entries in C -EOVERFLOW (before C is allocated); a failed
+ * allocation -ENOMEM.  On any error nothing is created, *out is NULL, *info
+ * is not written, all scratch is freed and spmv_live_handles() is unchanged.
+ * M, N or either NZ may be 0.  Peak device memory besides A, B and C, freed
+ * before the call returns: about 8 M bytes.
+ *
+ * Two companions, each one streaming kernel and a new ordinary f64 handle:
+ *
+ * spmv_csr_from_diag: the M x M handle with the one entry (i, i) per row, its
+ * value the bits of d_diag[i] (a NaN or 0.0 is stored as it is), or 1.0 when
+ * d_diag is NULL.  M == 0 is fine; M < 0 or NULL out -EINVAL; no device
+ * -ENODEV.  A - sigma I is spmv_csr_add(1, A, -sigma, I).
+ *
+ * spmv_csr_scale: a handle with A's IRP and JA byte for byte (rows may be
+ * unsorted; duplicates and explicit zeros are kept) and the values
+ * rn(rn(l_i a) r_j) for entry (i, j); with d_left only rn(l_i a), with
+ * d_right only rn(a r_j).  d_left holds M, d_right N doubles on the device.
+ * A may be f32-stored and of any shape.  Both vectors NULL -EINVAL; otherwise
+ * the errors of spmv_csr_to_f32 (-EINVAL, -ENODEV, -EBADF, -ENODATA,
+ * -ENOMEM), and -EDOM when d_right is given and a column lies outside [0, N).
+ *
+ * Not in scope: a sum into an existing handle or the reuse of a pattern for
+ * new values, operands with unsorted rows or duplicates, HLL, compact or f32
+ * results, pruning of zeros, a masked sum, more than two operands.
+ */
+typedef struct spmv_add_info {
+    int nz;                 /* entries of C */
+    int64_t matched;        /* columns stored in both operands, over all rows */
+    int64_t widest;         /* largest len_A(r) + len_B(r) */
+    int64_t rows_in_bin[2]; /* rows served by each size class */
+} spmv_add_info;
+int spmv_csr_add(double alpha, const spmv_csr_dev *A, double beta,
+                 const spmv_csr_dev *B, spmv_csr_dev **out,
+                 spmv_add_info *info /* or NULL */);
+int spmv_add_shape(int64_t *edge, int *widths /* [8] */, int *n_widths,
+                   int *threads);
+int spmv_add_set_class(int mode);
+void spmv_add_last_phases(double ms[3]);
+int spmv_csr_from_diag(int M, const double *d_diag /* device, or NULL: 1.0 */,
+                       spmv_csr_dev **out);
+int spmv_csr_scale(const spmv_csr_dev *A, const double *d_left,
+                   const double *d_right, spmv_csr_dev **out);
 /* Build a synthetic matrix (spmv_synth.h) directly in device memory. */
 int spmv_csr_generate(int kind, int M, int N, int K, int64_t W, int64_t row0,
                       uint64_t seed, spmv_csr_dev **out);

@@ -474,6 +474,12 @@ class SpgemmInfo(C.Structure):
                 ("rows_in_bin", C.c_int64 * 4), ("nz", C.c_int)]
 
 
+class AddInfo(C.Structure):
+    """spmv_add_info (include/spmv_engine.h): one CsrDevice.add()"""
+    _fields_ = [("nz", C.c_int), ("matched", C.c_int64),
+                ("widest", C.c_int64), ("rows_in_bin", C.c_int64 * 2)]
+
+
 _CSRp = C.POINTER(SparseCSR)
 _HLLp = C.POINTER(SparseHLL)
 
@@ -611,6 +617,15 @@ _sig("spmv_spgemm_shape", C.c_int, _i64p, _ip, _ip, _ip, _ip, _i64p)
 _sig("spmv_spgemm_last_phases", None, _dp)
 _sig("spmv_csr_galerkin", C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
      C.POINTER(C.c_void_p), C.POINTER(SpgemmInfo))
+_sig("spmv_csr_add", C.c_int, C.c_double, C.c_void_p, C.c_double, C.c_void_p,
+     C.POINTER(C.c_void_p), C.POINTER(AddInfo))
+_sig("spmv_add_shape", C.c_int, _i64p, _ip, _ip, _ip)
+_sig("spmv_add_set_class", C.c_int, C.c_int)
+_sig("spmv_add_last_phases", None, _dp)
+_sig("spmv_csr_from_diag", C.c_int, C.c_int, C.c_void_p,
+     C.POINTER(C.c_void_p))
+_sig("spmv_csr_scale", C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.POINTER(C.c_void_p))
 _sig("spmv_csr_trsv_analyse", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
      C.POINTER(C.c_void_p))
 _sig("spmv_csr_trsv_analyse_sweeps", C.c_int, C.c_void_p, C.c_int, C.c_int,
@@ -949,6 +964,38 @@ def spgemm_shape():
     return dict(edges=list(e), tables=list(t), teams=list(m),
                 lds_bytes=list(b), fallback_batch=fb.value,
                 fallback_bytes=fs.value)
+
+
+#: CsrDevice.add_info of an add() result
+AddResult = collections.namedtuple("AddResult",
+                                   "nz matched widest rows_in_bin")
+
+
+def add_shape():
+    """the constants of CsrDevice.add() (host, no device): dict(edge, widths,
+    threads) -- a row with len_A + len_B <= edge is served by a group of
+    lanes, its width the smallest of widths that is not below the mean
+    (NZ_A + NZ_B) / M, a longer one by a workgroup of `threads` lanes"""
+    e, w = C.c_int64(), (C.c_int * 8)()
+    n, t = C.c_int(), C.c_int()
+    _check(_lib.spmv_add_shape(C.byref(e), w, C.byref(n), C.byref(t)),
+           "spmv_add_shape")
+    return dict(edge=e.value, widths=list(w)[:n.value], threads=t.value)
+
+
+def add_set_class(mode):
+    """MEASUREMENT and tests: which size class serves the rows of every add()
+    from now on -- 0 the rule, 1 lane groups, 2 a workgroup per row; the
+    bytes of a sum are the same.  -> the previous mode"""
+    return _check(_lib.spmv_add_set_class(int(mode)), "spmv_add_set_class")
+
+
+def add_last_phases():
+    """host-clock ms of the last successful add() of this process:
+    dict(checks, count, fill)"""
+    ms = (C.c_double * 3)()
+    _lib.spmv_add_last_phases(ms)
+    return dict(zip(("checks", "count", "fill"), ms))
 
 
 def spgemm_last_phases():
@@ -2097,6 +2144,47 @@ class CsrDevice(_Device):
         _check(_lib.spmv_csr_spgemm(self.h, other.h, C.byref(h),
                                     C.byref(info)), "spmv_csr_spgemm")
         return self._product(h, info)
+
+    def add(self, other, alpha=1.0, beta=1.0):
+        """a new M x N f64 handle C = alpha self + beta other built on the
+        device (spmv_engine.h, spmv_csr_add): in every row the union of the
+        two rows' columns, once each, ascending; rn(alpha a), rn(beta b), or
+        the rounded sum of the two where both store the column, nothing
+        fused -- defined to the byte.  Either operand may be f32-stored;
+        `other` may be this handle.  The rows of both must be strictly
+        ascending by column (OSError(EINVAL); transpose().transpose() sorts
+        rows); alpha and beta must be finite.  The result carries .add_info
+        (nz, matched, widest, rows_in_bin).  Both operands stay valid"""
+        if not isinstance(other, CsrDevice):
+            raise TypeError("add: a CsrDevice, not %s" % type(other).__name__)
+        h, info = C.c_void_p(), AddInfo()
+        _check(_lib.spmv_csr_add(float(alpha), self.h, float(beta), other.h,
+                                 C.byref(h), C.byref(info)), "spmv_csr_add")
+        d = CsrDevice(h)
+        d.add_info = AddResult(info.nz, info.matched, info.widest,
+                               tuple(info.rows_in_bin))
+        return d
+
+    @classmethod
+    def from_diag(cls, M, d_diag=None):
+        """a new M x M f64 handle with the one entry (i, i) per row: the bits
+        of the M doubles at the device pointer d_diag, or 1.0 (the identity)
+        when it is None (spmv_csr_from_diag)"""
+        h = C.c_void_p()
+        _check(_lib.spmv_csr_from_diag(int(M), d_diag, C.byref(h)),
+               "spmv_csr_from_diag")
+        return cls(h)
+
+    def scale(self, d_left=None, d_right=None):
+        """a new f64 handle with this one's pattern byte for byte and the
+        values rn(rn(l_i a) r_j): d_left M and d_right N doubles on the
+        device, either may be None but not both (spmv_csr_scale).  This
+        handle may be f32-stored, of any shape, with unsorted rows and
+        duplicates, and stays valid"""
+        h = C.c_void_p()
+        _check(_lib.spmv_csr_scale(self.h, d_left, d_right, C.byref(h)),
+               "spmv_csr_scale")
+        return CsrDevice(h)
 
     def galerkin(self, dP, dPT=None):
         """a new handle dPT . (self . dP): the coarse operator of a

@@ -20,6 +20,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "add_plan.h"
 #include "amg_plan.h"
 #include "err.h"
 #include "hip_common.h"
@@ -1184,6 +1185,121 @@ int spmv_csr_spgemm(const spmv_csr_dev *A, const spmv_csr_dev *B,
     }
     if (info)
         *info = got;
+    *out = d;
+    return 0;
+}
+
+/* the constants of the sparse sum (add_plan.h); host arithmetic */
+int spmv_add_shape(int64_t *edge, int *widths, int *n_widths, int *threads) {
+    if (edge)
+        *edge = ADD_EDGE;
+    if (widths)
+        for (int i = 0; i < ADD_WIDTHS; ++i)
+            widths[i] = add_width(i);
+    if (n_widths)
+        *n_widths = ADD_WIDTHS;
+    if (threads)
+        *threads = ADD_THREADS;
+    return 0;
+}
+
+/* MEASUREMENT (spmv_add_set_class): which class serves the rows of a sum */
+static int g_add_class = 0;
+
+int spmv_add_set_class(int mode) {
+    const int was = g_add_class;
+    if (mode < 0 || mode > 2)
+        return -EINVAL;
+    g_add_class = mode;
+    return was;
+}
+
+void spmv_add_last_phases(double ms[3]) {
+    if (ms)
+        csr_add_last_phases(ms);
+}
+
+/* a new M x N f64 handle C = alpha A + beta B (add_kernels.hip) */
+int spmv_csr_add(double alpha, const spmv_csr_dev *A, double beta,
+                 const spmv_csr_dev *B, spmv_csr_dev **out,
+                 spmv_add_info *info) {
+    if (out)
+        *out = NULL; /* on ANY error, the argument checks included */
+    if (!A || !B || !out || !std::isfinite(alpha) || !std::isfinite(beta))
+        return -EINVAL;
+    if (spmv_device_count() == 0)
+        return -ENODEV; /* no handle can be live: the more useful answer */
+    HANDLE_OK(A);
+    HANDLE_OK(B);
+    if (A->M != B->M || A->N != B->N)
+        return -EINVAL;
+    if ((!A->ja && A->NZ > 0) || (!B->ja && B->NZ > 0))
+        return -ENODATA; /* spmv_csr_release_source() */
+    spmv_csr_dev *d = NULL;
+    spmv_add_info got;
+    int rc = csr_add_dev(alpha, A, beta, B, g_add_class, csr_alloc_dev, &d,
+                         &got, 0);
+    if (rc)
+        return rc;
+    const double t = csr_add_now_ms();
+    rc = finish_csr_handle(d, NULL);
+    if (rc) {
+        spmv_csr_release(d);
+        return rc;
+    }
+    csr_add_finish_ms(csr_add_now_ms() - t);
+    if (info)
+        *info = got;
+    *out = d;
+    return 0;
+}
+
+/* a new M x M f64 handle with the one entry (i, i) = d_diag[i] per row */
+int spmv_csr_from_diag(int M, const double *d_diag, spmv_csr_dev **out) {
+    if (out)
+        *out = NULL;
+    if (!out || M < 0)
+        return -EINVAL;
+    if (spmv_device_count() == 0)
+        return -ENODEV;
+    spmv_csr_dev *d = NULL;
+    int rc = csr_alloc_dev(M, M, M, 8, &d);
+    if (rc)
+        return rc;
+    rc = csr_from_diag_dev(d_diag, d, 0);
+    if (!rc)
+        rc = finish_csr_handle(d, NULL);
+    if (rc) {
+        spmv_csr_release(d);
+        return rc;
+    }
+    *out = d;
+    return 0;
+}
+
+/* a new f64 handle with A's pattern and the values l_i a r_j */
+int spmv_csr_scale(const spmv_csr_dev *A, const double *d_left,
+                   const double *d_right, spmv_csr_dev **out) {
+    if (out)
+        *out = NULL;
+    if (!A || !out || (!d_left && !d_right))
+        return -EINVAL;
+    if (spmv_device_count() == 0)
+        return -ENODEV; /* no handle can be live: the more useful answer */
+    HANDLE_OK(A);
+    if (!A->ja && A->NZ > 0)
+        return -ENODATA; /* spmv_csr_release_source() */
+    spmv_csr_dev *d = NULL;
+    int rc = csr_alloc_dev(A->M, A->N, A->NZ, 8, &d);
+    if (rc)
+        return rc;
+    rc = csr_scale_dev(A, d_left, d_right, d, 0);
+    if (!rc)
+        rc = finish_csr_handle(d, NULL);
+    if (rc) {
+        spmv_csr_release(d);
+        return rc;
+    }
     *out = d;
     return 0;
 }

@@ -3,7 +3,8 @@
  * (engine.hip, csr_kernels.hip, hll_kernels.hip, multi_kernels.hip,
  * cg_kernels.hip, bicgstab_kernels.hip, cgls_kernels.hip, minres_kernels.hip,
  * diag_kernels.hip, transpose_kernels.hip, trsv_kernels.hip, ic0_kernels.hip,
- * ilu0_kernels.hip, amg_kernels.hip, panels.hip, mgpu.hip, and
+ * ilu0_kernels.hip, spgemm_kernels.hip, add_kernels.hip, amg_kernels.hip,
+ * panels.hip, mgpu.hip, and
  * mat_ref.h on behalf of the first and the last).
  * Not installed.
  */
@@ -722,6 +723,33 @@ int csr_spgemm_dev(const spmv_csr_dev *A, const spmv_csr_dev *B,
  * bounds, lists and symbolic pass, scan + allocation + numeric pass, and the
  * part of the last two spent in the fallback's launches */
 void csr_spgemm_last_phases(double ms[4]);
+/* the product's device check of B, for the sum's two operands: *d_flags |= 1
+ * for a column outside [0, B->N), |= 2 for a row that is not strictly
+ * ascending; asynchronous */
+int csr_check_rows_dev(const spmv_csr_dev *B, unsigned long long *d_flags,
+                       hipStream_t s);
+/*
+ * C = alpha A + beta B (add_kernels.hip; spmv_csr_add).  The caller has
+ * checked the handles (live, with their sources, one shape) and the scalars.
+ * mode: spmv_add_set_class.  *out comes from `alloc` once the entries of C are
+ * known and holds irp, ja and the values; the caller finishes it as
+ * spmv_csr_transpose does and reports the time of that with
+ * csr_add_finish_ms.  Blocks; on an error *out and *info are untouched and
+ * everything is freed.
+ */
+int csr_add_dev(double alpha, const spmv_csr_dev *A, double beta,
+                const spmv_csr_dev *B, int mode, ic0_alloc_fn alloc,
+                spmv_csr_dev **out, spmv_add_info *info, hipStream_t s);
+void csr_add_last_phases(double ms[3]);
+void csr_add_finish_ms(double ms);
+double csr_add_now_ms(void);
+/* the companions: D (M x M, M entries, f64, allocated) gets the arrays of
+ * diag(d) (d NULL: the identity); S (A's shape and entry count, f64,
+ * allocated) gets A's irp and ja and the scaled values, -EDOM when d_right is
+ * given and a column lies outside [0, N).  Both block */
+int csr_from_diag_dev(const double *d_diag, spmv_csr_dev *D, hipStream_t s);
+int csr_scale_dev(const spmv_csr_dev *A, const double *d_left,
+                  const double *d_right, spmv_csr_dev *S, hipStream_t s);
 int permute_vectors_dev(const int *p, int M, int k, int inverse,
                         const double *in, int64_t ldin, double *out,
                         int64_t ldout, hipStream_t s);

@@ -125,6 +125,19 @@ k_sg_check_b(const int *__restrict__ irp, const int *__restrict__ ja, int K,
         atomicOr(head + SG_FLAGS, (sg_u64)f);
 }
 
+/* *d_flags |= 1: a column of B outside [0, B->N); |= 2: a row of B that is not
+ * strictly ascending.  Asynchronous; the sum checks both its operands with it
+ * (add_kernels.hip) */
+int csr_check_rows_dev(const spmv_csr_dev *B, unsigned long long *d_flags,
+                       hipStream_t s) {
+    if (B->NZ > 0)
+        hipLaunchKernelGGL(k_sg_check_b,
+                           dim3((unsigned)spgemm_ceil_div(B->NZ, SG_T)),
+                           dim3(SG_T), 0, s, B->irp, B->ja, B->M, B->NZ, B->N,
+                           d_flags + SG_FLAGS);
+    return hip_errno(hipGetLastError());
+}
+
 __global__ void __launch_bounds__(SG_T)
 k_sg_bound(int M, int K, const int *__restrict__ irp_a,
            const int *__restrict__ ja_a, const int *__restrict__ irp_b,
@@ -639,10 +652,9 @@ int csr_spgemm_dev(const spmv_csr_dev *A, const spmv_csr_dev *B,
     HIP_TRY(hipMemsetAsync(head, 0, SPGEMM_HEAD_WORDS * 8, s));
     HIP_TRY(hipMemsetAsync(count, 0, ((size_t)M + 1) * sizeof(int), s));
     /* 1. the checks and the bounds */
-    if (B->NZ > 0)
-        hipLaunchKernelGGL(k_sg_check_b,
-                           dim3((unsigned)spgemm_ceil_div(B->NZ, SG_T)), block,
-                           0, s, B->irp, B->ja, B->M, B->NZ, N, head);
+    rc = csr_check_rows_dev(B, head, s);
+    if (rc)
+        goto fail;
     if (M > 0)
         hipLaunchKernelGGL(k_sg_bound, row_grid, block, 0, s, M, K, A->irp,
                            A->ja, B->irp, ub, head);
