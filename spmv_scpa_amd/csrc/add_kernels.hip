@@ -10,22 +10,19 @@
  * both rn(ta + tb) -- every operation rounded on its own (this file is
  * compiled with contraction off: no fused multiply-add).
  *
- * The geometry (size classes, widths, scratch) is add_plan.h's.  The
- * launches, in order -- the kernel boundary is the only ordering between
- * workgroups, nothing waits on another workgroup:
+ * The geometry (size classes, widths, scratch) is add_plan.h's; the steps
+ * every builder of a handle shares are csr_build.h's.  The launches, in order
+ * -- the kernel boundary is the only ordering between workgroups, nothing
+ * waits on another workgroup:
  *
- *   csr_check_rows_dev (A, B)   one lane per entry: column inside [0, N), and
- *                  above its left neighbour in the same row (the check that
- *                  serves B of the product, spgemm_kernels.hip)
+ *   csr_check_rows_dev (A, B)
  *   k_add_bound    the rows beyond the class edge and the widest row, over
  *                  all rows (integer atomics, one pair a workgroup: a COUNT
  *                  and a MAXIMUM do not depend on the order of arrival)
- *   k_add_lists    the rows of each class, listed -- only when both classes
- *                  hold rows.  The order inside a list comes from an atomic
- *                  cursor; nothing of C depends on it: a list only says which
- *                  team serves which row
+ *   csr_lists_dev  the rows of each class (the length rule), listed -- only
+ *                  when both classes hold rows
  *   k_add_count_*  len_A + len_B - matches per row (reads IRP and JA only)
- *   k_add_total, the exclusive scan of the transposition      C's IRP
+ *   csr_total_dev, csr_alloc_scanned_dev      C's IRP
  *   k_add_rows_*   JA and AS of C
  *
  * Both row kernels are a merge of two ascending index lists BY RANK, searched
@@ -50,11 +47,9 @@
  */
 #include <algorithm>
 #include <string.h>
-#include <time.h>
 
 #include "add_plan.h"
-#include "hip_common.h"
-#include "transpose_plan.h"
+#include "csr_build.h"
 
 /* every product and every sum is rounded on its own */
 #pragma clang fp contract(off)
@@ -78,18 +73,6 @@ enum {
 };
 static_assert(AD_NZ < ADD_HEAD_WORDS, "the head holds every word");
 
-__device__ __forceinline__ unsigned ad_lanes_below(ad_u64 mask) {
-    return __builtin_amdgcn_mbcnt_hi(
-        (unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
-
-__device__ __forceinline__ ad_u64 ad_wave_sum(ad_u64 v) {
-#pragma unroll
-    for (int d = WAVE / 2; d > 0; d >>= 1)
-        v += __shfl_down(v, d, WAVE);
-    return v; /* lane 0 */
-}
-
 /* first place of row[0 .. n) (ascending) that holds c or more: at most
  * log2(n) + 1 probes */
 __device__ __forceinline__ int ad_lower_bound(const int *__restrict__ row,
@@ -106,19 +89,15 @@ __device__ __forceinline__ int ad_lower_bound(const int *__restrict__ row,
 }
 
 /* ------------------------------------------------------------------ */
-/* bounds, lists, total                                                 */
+/* bounds, the class of a row                                           */
 /* ------------------------------------------------------------------ */
 
 /* the workgroup's sum and maximum of v in thread 0 (all threads call) */
 __device__ __forceinline__ void ad_block_sum_max(ad_u64 &sum, ad_u64 &most) {
     __shared__ ad_u64 part[2][AD_WAVES];
     const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-#pragma unroll
-    for (int d = WAVE / 2; d > 0; d >>= 1) {
-        const ad_u64 o = __shfl_down(most, d, WAVE);
-        most = o > most ? o : most;
-    }
-    sum = ad_wave_sum(sum);
+    most = wave_max(most);
+    sum = wave_sum(sum);
     if (lane == 0) {
         part[0][wave] = sum;
         part[1][wave] = most;
@@ -156,45 +135,18 @@ k_add_bound(int M, const int *__restrict__ irp_a, const int *__restrict__ irp_b,
     }
 }
 
-/* the cursors start at the classes' first places (set by the host) */
-__global__ void __launch_bounds__(AD_T)
-k_add_lists(int M, const int *__restrict__ irp_a, const int *__restrict__ irp_b,
-            int64_t edge, ad_u64 *__restrict__ head, int *__restrict__ list) {
-    const int64_t r = (int64_t)blockIdx.x * AD_T + threadIdx.x;
-    const int lane = threadIdx.x & (WAVE - 1);
-    int cls = -1;
-    if (r < M)
-        cls = ((int64_t)irp_a[r + 1] - irp_a[r]) +
-                          ((int64_t)irp_b[r + 1] - irp_b[r]) <=
-                      edge
-                  ? 0
-                  : 1;
-#pragma unroll
-    for (int c = 0; c < ADD_CLASSES; ++c) {
-        const ad_u64 mask = __ballot(cls == c);
-        if (!mask) /* wavefront-uniform */
-            continue;
-        const int leader = __ffsll((long long)mask) - 1;
-        ad_u64 base = 0;
-        if (lane == leader)
-            base = atomicAdd(head + AD_CURSOR + c, (ad_u64)__popcll(mask));
-        base = __shfl(base, leader, WAVE);
-        if (cls == c) /* base + rank < M: the classes' counts sum to M */
-            list[base + ad_lanes_below(mask)] = (int)r;
+/* the class of a row, for csr_lists_dev */
+struct ad_row_class {
+    const int *irp_a, *irp_b;
+    int64_t edge;
+    __device__ int operator()(int64_t r) const {
+        return ((int64_t)irp_a[r + 1] - irp_a[r]) +
+                           ((int64_t)irp_b[r + 1] - irp_b[r]) <=
+                       edge
+                   ? 0
+                   : 1;
     }
-}
-
-__global__ void __launch_bounds__(AD_T)
-k_add_total(const int *__restrict__ count, int M, ad_u64 *__restrict__ head) {
-    const int64_t first = (int64_t)blockIdx.x * AD_T + threadIdx.x;
-    const int64_t stride = (int64_t)gridDim.x * AD_T;
-    ad_u64 n = 0, unused = 0;
-    for (int64_t r = first; r < M; r += stride)
-        n += (ad_u64)count[r];
-    ad_block_sum_max(n, unused);
-    if (threadIdx.x == 0 && n)
-        atomicAdd(head + AD_NZ, n);
-}
+};
 
 /* ------------------------------------------------------------------ */
 /* class 0: a group of G lanes per row                                  */
@@ -327,7 +279,7 @@ k_add_count_wg(const int *__restrict__ list, const int *__restrict__ irp_a,
             const int p = ad_lower_bound(ja_b + b0, lb, c);
             matches += p < lb && ja_b[b0 + p] == c;
         }
-    matches = (int)ad_wave_sum((ad_u64)matches);
+    matches = (int)wave_sum((ad_u64)matches);
     if (lane == 0)
         wsum[wave] = matches;
     __syncthreads();
@@ -391,8 +343,8 @@ k_add_rows_wg(const int *__restrict__ list, double alpha,
         }
         if (on && (side_a || !match)) {
             const int before =
-                side_a ? carry_a + before_a + (int)ad_lanes_below(ma)
-                       : carry_b + before_b + (int)ad_lanes_below(mb);
+                side_a ? carry_a + before_a + (int)lanes_below(ma)
+                       : carry_b + before_b + (int)lanes_below(mb);
             const int64_t pos = (int64_t)c0 + at + p - before;
             double v;
             if (side_a) {
@@ -434,12 +386,6 @@ void csr_add_last_phases(double ms[3]) {
         ms[i] = g_ad_phase_ms[i];
 }
 void csr_add_finish_ms(double ms) { g_ad_phase_ms[2] += ms; }
-
-double csr_add_now_ms(void) {
-    struct timespec t;
-    clock_gettime(CLOCK_MONOTONIC, &t);
-    return 1e3 * (double)t.tv_sec + 1e-6 * (double)t.tv_nsec;
-}
 
 struct ad_args {
     const spmv_csr_dev *A, *B;
@@ -504,13 +450,13 @@ static int ad_rows(const ad_args &g, hipStream_t s) {
     return hip_errno(hipGetLastError());
 }
 
-/* *out (M x N, f64, from `alloc` once the entries of C are known) gets its
+/* *out (M x N, f64, allocated once the entries of C are known) gets its
  * irp, ja and values.  Blocks.  -EDOM: a column outside [0, N); -EINVAL: a row
  * that is not strictly ascending; -EOVERFLOW: more than INT32_MAX entries.  On
  * an error *out and *info are untouched and everything is freed. */
 int csr_add_dev(double alpha, const spmv_csr_dev *A, double beta,
-                const spmv_csr_dev *B, int mode, ic0_alloc_fn alloc,
-                spmv_csr_dev **out, spmv_add_info *info, hipStream_t s) {
+                const spmv_csr_dev *B, int mode, spmv_csr_dev **out,
+                spmv_add_info *info, hipStream_t s) {
     int rc = 0;
     const int M = A->M, N = A->N;
     add_plan pl;
@@ -522,10 +468,9 @@ int csr_add_dev(double alpha, const spmv_csr_dev *A, double beta,
     int *count = NULL, *list = NULL, *sums = NULL;
     int64_t nz = 0, matched = 0;
     ad_args g;
-    double t0 = csr_add_now_ms(), t1 = 0, t2 = 0;
+    double t0 = csr_now_ms(), t1 = 0, t2 = 0;
     const dim3 block(AD_T);
-    const dim3 row_grid((unsigned)add_ceil_div(M, AD_T));
-    /* the two reductions over the rows: grid-stride, an atomic a workgroup */
+    /* the reduction over the rows: grid-stride, an atomic a workgroup */
     const dim3 reduce_grid(
         (unsigned)std::min<int64_t>(ADD_REDUCE_GRID, add_ceil_div(M, AD_T)));
     /* class 0 serves len <= edge */
@@ -553,15 +498,10 @@ int csr_add_dev(double alpha, const spmv_csr_dev *A, double beta,
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(h, head, sizeof h, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    t1 = csr_add_now_ms();
-    if (h[AD_FLAGS] & 1u) {
-        rc = -EDOM;
+    t1 = csr_now_ms();
+    rc = csr_flags_errno(h[AD_FLAGS]);
+    if (rc)
         goto fail;
-    }
-    if (h[AD_FLAGS] & 2u) {
-        rc = -EINVAL;
-        goto fail;
-    }
     g.A = A;
     g.B = B;
     g.alpha = alpha;
@@ -583,8 +523,8 @@ int csr_add_dev(double alpha, const spmv_csr_dev *A, double beta,
         cursor[1] = (ad_u64)g.rows[0];
         HIP_TRY(hipMemcpyAsync(head + AD_CURSOR, cursor, sizeof cursor,
                                hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_add_lists, row_grid, block, 0, s, M, A->irp,
-                           B->irp, edge, head, list);
+        csr_lists_dev<ADD_CLASSES>(M, ad_row_class{A->irp, B->irp, edge},
+                                   head + AD_CURSOR, list, s);
         g.list[0] = list;
         g.list[1] = list + g.rows[0];
     }
@@ -593,43 +533,30 @@ int csr_add_dev(double alpha, const spmv_csr_dev *A, double beta,
     rc = ad_count(g, s);
     if (rc)
         goto fail;
-    if (M > 0)
-        hipLaunchKernelGGL(k_add_total, reduce_grid, block, 0, s, count, M,
-                           head);
-    HIP_TRY(hipGetLastError());
+    rc = csr_total_dev(count, M, head + AD_NZ, s);
+    if (rc)
+        goto fail;
     HIP_TRY(hipMemcpyAsync(h, head, sizeof h, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     nz = (int64_t)h[AD_NZ];
     rc = add_nz_guard(nz);
     if (!rc)
         rc = add_matched(A->NZ, B->NZ, nz, &matched);
+    /* 4. C, its IRP (the scan ends the second phase), the fill pass */
+    if (!rc)
+        rc = csr_alloc_scanned_dev(M, N, nz, count, sums, &t2, &Cm, s);
     if (rc)
         goto fail;
-    tr_scan(count, (int64_t)M + 1, sums, s);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(s));
-    t2 = csr_add_now_ms();
-    /* 4. C, its IRP, the fill pass */
-    rc = alloc(M, N, nz, 8, &Cm);
-    if (rc)
-        goto fail;
-    HIP_TRY(hipMemcpyAsync(Cm->irp, count, ((size_t)M + 1) * sizeof(int),
-                           hipMemcpyDeviceToDevice, s));
     g.C = Cm;
-    if (A->value_bytes == 4 && B->value_bytes == 4)
-        rc = ad_rows<float, float>(g, s);
-    else if (A->value_bytes == 4)
-        rc = ad_rows<float, double>(g, s);
-    else if (B->value_bytes == 4)
-        rc = ad_rows<double, float>(g, s);
-    else
-        rc = ad_rows<double, double>(g, s);
+    rc = csr_value_types(A, B, [&](auto va, auto vb) {
+        return ad_rows<decltype(va), decltype(vb)>(g, s);
+    });
     if (rc)
         goto fail;
     HIP_TRY(hipStreamSynchronize(s));
     g_ad_phase_ms[0] = t1 - t0;
     g_ad_phase_ms[1] = t2 - t1;
-    g_ad_phase_ms[2] = csr_add_now_ms() - t2;
+    g_ad_phase_ms[2] = csr_now_ms() - t2;
     if (info) {
         info->nz = (int)nz;
         info->matched = matched;
@@ -665,9 +592,9 @@ k_add_from_diag(int M, const ad_u64 *__restrict__ diag, int *__restrict__ irp,
 int csr_from_diag_dev(const double *d_diag, spmv_csr_dev *D, hipStream_t s) {
     (void)hipGetLastError();
     hipLaunchKernelGGL(k_add_from_diag,
-                       dim3((unsigned)add_ceil_div((int64_t)D->M + 1, AD_T)),
-                       dim3(AD_T), 0, s, D->M, (const ad_u64 *)d_diag, D->irp,
-                       D->ja, (ad_u64 *)D->as);
+                       grid_for((int64_t)D->M + 1, AD_T), dim3(AD_T), 0, s,
+                       D->M, (const ad_u64 *)d_diag, D->irp, D->ja,
+                       (ad_u64 *)D->as);
     HIP_RET(hipGetLastError());
     HIP_RET(hipStreamSynchronize(s));
     return 0;
@@ -702,7 +629,7 @@ k_add_scale(const int *__restrict__ irp, const int *__restrict__ ja,
         if ((unsigned)c < (unsigned)N)
             v = v * r[c];
         else
-            atomicOr(flag, 1u);
+            atomicOr(flag, CSR_BAD_COLUMN);
     }
     out[q] = v;
 }
@@ -717,7 +644,7 @@ int csr_scale_dev(const spmv_csr_dev *A, const double *d_left,
     HIP_TRY(hipMemcpyAsync(S->irp, A->irp, ((size_t)A->M + 1) * sizeof(int),
                            hipMemcpyDeviceToDevice, s));
     if (A->NZ > 0) {
-        const dim3 grid((unsigned)add_ceil_div(A->NZ, AD_T));
+        const dim3 grid = grid_for(A->NZ, AD_T);
         HIP_TRY(hipMemcpyAsync(S->ja, A->ja, (size_t)A->NZ * sizeof(int),
                                hipMemcpyDeviceToDevice, s));
         HIP_TRY(hipMalloc((void **)&d_flag, sizeof(unsigned)));
@@ -735,8 +662,7 @@ int csr_scale_dev(const spmv_csr_dev *A, const double *d_left,
                                hipMemcpyDeviceToHost, s));
     }
     HIP_TRY(hipStreamSynchronize(s));
-    if (flag)
-        rc = -EDOM;
+    rc = csr_flags_errno(flag);
 fail:
     if (rc)
         (void)hipStreamSynchronize(s);

@@ -65,19 +65,9 @@
 #include <vector>
 
 #include "amg_plan.h"
-#include "hip_common.h"
-#include "transpose_plan.h"
+#include "csr_build.h"
 
 static_assert(AMG_T % WAVE == 0, "whole wavefronts");
-
-#define AMG_BAD_COLUMN 1u
-#define AMG_BAD_ORDER 2u
-
-static inline dim3 amg_dim(int64_t n) {
-    unsigned g = 1;
-    (void)amg_grid(n, &g); /* n <= 8 * INT32_MAX / 256: always a grid */
-    return dim3(g);
-}
 
 /* device scratch of one call: freed on every path */
 struct amg_scratch {
@@ -117,9 +107,9 @@ k_amg_check(int M, const int *__restrict__ irp, const int *__restrict__ ja,
     for (int64_t e = irp[i], end = irp[i + 1]; e < end; ++e) {
         const int j = ja[e];
         if ((unsigned)j >= (unsigned)M)
-            bad |= AMG_BAD_COLUMN;
+            bad |= CSR_BAD_COLUMN;
         if (j <= prev)
-            bad |= AMG_BAD_ORDER;
+            bad |= CSR_BAD_ORDER;
         prev = j;
         if (j == (int)i) {
             has_diag = true;
@@ -127,7 +117,7 @@ k_amg_check(int M, const int *__restrict__ irp, const int *__restrict__ ja,
         }
     }
     if (!has_diag)
-        bad |= AMG_BAD_ORDER;
+        bad |= CSR_BAD_ORDER;
     if (d)
         d[i] = dv;
     if (bad)
@@ -145,16 +135,13 @@ int amg_check_dev(const spmv_csr_dev *A, double *d_diag, hipStream_t s) {
     (void)hipGetLastError(); /* an earlier caller's unread error is not ours */
     HIP_TRY(scratch.get(&d_flag, 1));
     HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(unsigned), s));
-    hipLaunchKernelGGL(k_amg_check, amg_dim(A->M), dim3(AMG_T), 0, s, A->M,
-                       A->irp, A->ja, A->as, d_diag, d_flag);
+    hipLaunchKernelGGL(k_amg_check, grid_for(A->M, AMG_T), dim3(AMG_T), 0, s,
+                       A->M, A->irp, A->ja, A->as, d_diag, d_flag);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(&flag, d_flag, sizeof(unsigned),
                            hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if (flag & AMG_BAD_COLUMN)
-        rc = -EDOM;
-    else if (flag & AMG_BAD_ORDER)
-        rc = -EINVAL;
+    rc = csr_flags_errno(flag);
 fail:
     if (rc)
         (void)hipStreamSynchronize(s);
@@ -364,7 +351,8 @@ int amg_aggregate_dev(const spmv_csr_dev *A, double theta2, uint32_t seed,
         *agg2 = NULL, *single = NULL, *agg = NULL, *size = NULL;
     int rounds = 0, left = M, roots = 0, singles = 0, widest = 0;
     int cur = 0; /* key[cur] holds the keys */
-    const dim3 grid = amg_dim(M), grid1 = amg_dim((int64_t)M + 1), wg(AMG_T);
+    const dim3 grid = grid_for(M, AMG_T), wg(AMG_T);
+    const dim3 grid1 = grid_for((int64_t)M + 1, AMG_T);
     if (M == 0) {
         if (info)
             *info = got;
@@ -518,10 +506,10 @@ int amg_rho_dev(const spmv_csr_dev *A, double *d_w, double *rho,
     HIP_TRY(scratch.get(&d_rho, 2));
     d_flag = (unsigned *)(d_rho + 1);
     HIP_TRY(hipMemsetAsync(d_rho, 0, 2 * sizeof(unsigned long long), s));
-    hipLaunchKernelGGL(k_amg_check, amg_dim(A->M), dim3(AMG_T), 0, s, A->M,
-                       A->irp, A->ja, A->as, d_w, d_flag);
-    hipLaunchKernelGGL(k_amg_rho, amg_dim(A->M), dim3(AMG_T), 0, s, A->M,
-                       A->irp, A->as, d_w, d_rho);
+    hipLaunchKernelGGL(k_amg_check, grid_for(A->M, AMG_T), dim3(AMG_T), 0, s,
+                       A->M, A->irp, A->ja, A->as, d_w, d_flag);
+    hipLaunchKernelGGL(k_amg_rho, grid_for(A->M, AMG_T), dim3(AMG_T), 0, s,
+                       A->M, A->irp, A->as, d_w, d_rho);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(&bits, d_rho, sizeof bits, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -533,7 +521,8 @@ fail:
 }
 
 int amg_w_dev(int M, double omega, double *d_w, hipStream_t s) {
-    hipLaunchKernelGGL(k_amg_w, amg_dim(M), dim3(AMG_T), 0, s, M, omega, d_w);
+    hipLaunchKernelGGL(k_amg_w, grid_for(M, AMG_T), dim3(AMG_T), 0, s, M, omega,
+                       d_w);
     return hip_errno(hipGetLastError());
 }
 
@@ -552,8 +541,8 @@ k_amg_tent(int M, const int *__restrict__ agg, int *__restrict__ irp,
 }
 
 int amg_tentative_dev(int M, const int *d_agg, spmv_csr_dev *T, hipStream_t s) {
-    hipLaunchKernelGGL(k_amg_tent, amg_dim((int64_t)M + 1), dim3(AMG_T), 0, s,
-                       M, d_agg, T->irp, T->ja, T->as);
+    hipLaunchKernelGGL(k_amg_tent, grid_for((int64_t)M + 1, AMG_T), dim3(AMG_T),
+                       0, s, M, d_agg, T->irp, T->ja, T->as);
     return hip_errno(hipGetLastError());
 }
 
@@ -580,8 +569,8 @@ int amg_smooth_p_dev(spmv_csr_dev *AT, const int *d_agg, const double *d_w,
                      hipStream_t s) {
     if (AT->M == 0)
         return 0;
-    hipLaunchKernelGGL(k_amg_psmooth, amg_dim(AT->M), dim3(AMG_T), 0, s, AT->M,
-                       AT->irp, AT->ja, d_agg, d_w, AT->as);
+    hipLaunchKernelGGL(k_amg_psmooth, grid_for(AT->M, AMG_T), dim3(AMG_T), 0, s,
+                       AT->M, AT->irp, AT->ja, d_agg, d_w, AT->as);
     return hip_errno(hipGetLastError());
 }
 
@@ -632,8 +621,8 @@ k_amg_update(int64_t total, int k, const double *__restrict__ w,
 void amg_first_dev(int M, int k, const double *w, const double *b, int64_t ldb,
                    double *x, int64_t ldx, double *r, hipStream_t s) {
     const int64_t total = (int64_t)M * k;
-    hipLaunchKernelGGL(k_amg_first, amg_dim(total), dim3(AMG_T), 0, s, total, k,
-                       w, b, ldb, x, ldx, r);
+    hipLaunchKernelGGL(k_amg_first, grid_for(total, AMG_T), dim3(AMG_T), 0, s,
+                       total, k, w, b, ldb, x, ldx, r);
 }
 
 void amg_update_dev(int M, int k, int refill, const double *w, const double *b,
@@ -641,11 +630,11 @@ void amg_update_dev(int M, int k, int refill, const double *w, const double *b,
                     hipStream_t s) {
     const int64_t total = (int64_t)M * k;
     if (refill)
-        hipLaunchKernelGGL((k_amg_update<true>), amg_dim(total), dim3(AMG_T), 0,
-                           s, total, k, w, b, ldb, x, ldx, r);
+        hipLaunchKernelGGL((k_amg_update<true>), grid_for(total, AMG_T),
+                           dim3(AMG_T), 0, s, total, k, w, b, ldb, x, ldx, r);
     else
-        hipLaunchKernelGGL((k_amg_update<false>), amg_dim(total), dim3(AMG_T),
-                           0, s, total, k, w, b, ldb, x, ldx, r);
+        hipLaunchKernelGGL((k_amg_update<false>), grid_for(total, AMG_T),
+                           dim3(AMG_T), 0, s, total, k, w, b, ldb, x, ldx, r);
 }
 
 /* ------------------------------------------------------------------ */

@@ -52,8 +52,7 @@
 #include <string.h>
 #include <vector>
 
-#include "hip_common.h"
-#include "transpose_plan.h"
+#include "csr_build.h"
 
 #define CO_T 256 /* lanes of a workgroup */
 
@@ -67,10 +66,6 @@ __device__ __forceinline__ uint32_t co_fmix32(uint32_t h) {
     h *= 0xc2b2ae35u;
     h ^= h >> 16;
     return h;
-}
-
-static inline dim3 co_grid(int64_t n) {
-    return dim3((unsigned)transpose_ceil_div(n > 0 ? n : 1, CO_T));
 }
 
 /* ------------------------------------------------------------------ */
@@ -253,8 +248,8 @@ int csr_colour_dev(const spmv_csr_dev *A, uint32_t seed, int max_rounds,
             rc = -E2BIG;
             goto fail;
         }
-        hipLaunchKernelGGL(k_co_round, co_grid(M), dim3(CO_T), 0, s, M, seed,
-                           A->irp, A->ja, tirp, tja, buf[rounds & 1],
+        hipLaunchKernelGGL(k_co_round, grid_for(M, CO_T), dim3(CO_T), 0, s, M,
+                           seed, A->irp, A->ja, tirp, tja, buf[rounds & 1],
                            buf[(rounds + 1) & 1], counters + rounds % 3,
                            counters + (rounds + 1) % 3);
         HIP_TRY(hipGetLastError());
@@ -288,8 +283,8 @@ int csr_colour_dev(const spmv_csr_dev *A, uint32_t seed, int max_rounds,
         HIP_TRY(scratch.get(&iota, (int64_t)M + 1));
         HIP_TRY(scratch.get(&cptr, (int64_t)got.colours + 1));
         HIP_TRY(scratch.get(&order, M));
-        hipLaunchKernelGGL(k_co_iota, co_grid((int64_t)M + 1), dim3(CO_T), 0, s,
-                           M + 1, iota);
+        hipLaunchKernelGGL(k_co_iota, grid_for((int64_t)M + 1, CO_T),
+                           dim3(CO_T), 0, s, M + 1, iota);
         HIP_TRY(hipGetLastError());
         spmv_csr_dev L = co_view(M, got.colours, M, 4, iota, (int *)colour,
                                  buf[(rounds + 1) & 1]);
@@ -317,8 +312,8 @@ int csr_colour_dev(const spmv_csr_dev *A, uint32_t seed, int max_rounds,
             HIP_TRY(hipMemcpyAsync(d_colour, colour, (size_t)M * sizeof(int),
                                    hipMemcpyDeviceToDevice, s));
         if (d_new_of_old) {
-            hipLaunchKernelGGL(k_co_invert, co_grid(M), dim3(CO_T), 0, s, M,
-                               order, d_new_of_old);
+            hipLaunchKernelGGL(k_co_invert, grid_for(M, CO_T), dim3(CO_T), 0, s,
+                               M, order, d_new_of_old);
             HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipStreamSynchronize(s));
@@ -374,10 +369,10 @@ static int co_check_perm(const int *perm, int n, hipStream_t s) {
     HIP_TRY(scratch.get(&inv, n));
     HIP_TRY(scratch.get(&d_flag, 1));
     HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(unsigned), s));
-    hipLaunchKernelGGL(k_co_perm_scatter, co_grid(n), dim3(CO_T), 0, s, n,
+    hipLaunchKernelGGL(k_co_perm_scatter, grid_for(n, CO_T), dim3(CO_T), 0, s,
+                       n, perm, inv, d_flag);
+    hipLaunchKernelGGL(k_co_perm_verify, grid_for(n, CO_T), dim3(CO_T), 0, s, n,
                        perm, inv, d_flag);
-    hipLaunchKernelGGL(k_co_perm_verify, co_grid(n), dim3(CO_T), 0, s, n, perm,
-                       inv, d_flag);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(&flag, d_flag, sizeof(unsigned),
                            hipMemcpyDeviceToHost, s));
@@ -405,7 +400,7 @@ k_co_relabel(int64_t NZ, int n, const int *__restrict__ map, const int *src,
 }
 
 int csr_permute_dev(const spmv_csr_dev *A, const int *p, const int *q,
-                    ic0_alloc_fn alloc, spmv_csr_dev **out, hipStream_t s) {
+                    spmv_csr_dev **out, hipStream_t s) {
     int rc = 0;
     const int M = A->M, N = A->N, vb = A->value_bytes;
     const int64_t NZ = A->NZ;
@@ -426,8 +421,8 @@ int csr_permute_dev(const spmv_csr_dev *A, const int *p, const int *q,
     HIP_TRY(scratch.get(&tval, NZ * vb));
     if (q && NZ > 0) {
         HIP_TRY(scratch.get(&ja1, NZ));
-        hipLaunchKernelGGL(k_co_relabel, co_grid(NZ), dim3(CO_T), 0, s, NZ, N,
-                           q, A->ja, ja1);
+        hipLaunchKernelGGL(k_co_relabel, grid_for(NZ, CO_T), dim3(CO_T), 0, s,
+                           NZ, N, q, A->ja, ja1);
         HIP_TRY(hipGetLastError());
     }
     {
@@ -437,11 +432,11 @@ int csr_permute_dev(const spmv_csr_dev *A, const int *p, const int *q,
         if (rc)
             goto fail;
         if (p && NZ > 0) { /* T's columns are rows of A: all inside [0, M) */
-            hipLaunchKernelGGL(k_co_relabel, co_grid(NZ), dim3(CO_T), 0, s, NZ,
-                               M, p, tja, tja);
+            hipLaunchKernelGGL(k_co_relabel, grid_for(NZ, CO_T), dim3(CO_T), 0,
+                               s, NZ, M, p, tja, tja);
             HIP_TRY(hipGetLastError());
         }
-        rc = alloc(M, N, NZ, vb, &B);
+        rc = csr_alloc_dev(M, N, NZ, vb, &B);
         if (rc)
             goto fail;
         rc = csr_transpose_dev(&T, B, s);
@@ -484,10 +479,10 @@ int permute_vectors_dev(const int *p, int M, int k, int inverse,
                         int64_t ldout, hipStream_t s) {
     const int64_t total = (int64_t)M * k;
     if (inverse)
-        hipLaunchKernelGGL((k_co_vectors<true>), co_grid(total), dim3(CO_T), 0,
-                           s, total, k, p, in, ldin, out, ldout);
+        hipLaunchKernelGGL((k_co_vectors<true>), grid_for(total, CO_T),
+                           dim3(CO_T), 0, s, total, k, p, in, ldin, out, ldout);
     else
-        hipLaunchKernelGGL((k_co_vectors<false>), co_grid(total), dim3(CO_T), 0,
-                           s, total, k, p, in, ldin, out, ldout);
+        hipLaunchKernelGGL((k_co_vectors<false>), grid_for(total, CO_T),
+                           dim3(CO_T), 0, s, total, k, p, in, ldin, out, ldout);
     return hip_errno(hipGetLastError());
 }

@@ -22,6 +22,7 @@
 
 #include "add_plan.h"
 #include "amg_plan.h"
+#include "csr_build.h"
 #include "err.h"
 #include "hip_common.h"
 #include "hip_csr.h"
@@ -120,6 +121,12 @@ static bool live_has(const void *h) {
         if (!live_has(h))                                                     \
             return -EBADF; /* released, or never a handle */                  \
     } while (0)
+
+/* false after spmv_*_release_source(): what reads ja answers -ENODATA */
+static bool has_source(const spmv_csr_dev *A) { return A->ja || A->NZ == 0; }
+static bool has_source(const spmv_hll_dev *H) {
+    return H->ja || H->off16 || H->slots == 0;
+}
 
 /* the blocked path as a candidate: tune_blocked.h with panels.hip's
  * operations (the same template runs under ASan with mock copies) */
@@ -864,38 +871,8 @@ fail:
     return rc;
 }
 
-extern "C" {
-
-int spmv_dev_fill_synth(double *d_x, int64_t n, uint64_t seed, int64_t first,
-                        void *stream) {
-    if (n <= 0)
-        return 0;
-    hipLaunchKernelGGL(k_fill_x, dim3((unsigned)((n + 255) / 256)), dim3(256),
-                       0, (hipStream_t)stream, d_x, n, seed, first);
-    return hip_errno(hipGetLastError());
-}
-
-/* ------------------------------------------------------------------ */
-/* CSR handle                                                           */
-/* ------------------------------------------------------------------ */
-
-static void teardown(spmv_csr_dev *d) {
-    (void)hipFree(d->irp);
-    (void)hipFree(d->ja);
-    (void)hipFree(d->as);
-    (void)hipFree(d->as32);
-    (void)hipFree(d->rowblk);
-    (void)hipFree(d->rowblk_mode);
-    (void)hipFree(d->seg_partial);
-    (void)hipFree(d->seg_count);
-    (void)hipFree(d->long_rb);
-    panels_free(d->panels);
-    free(d->tune_log);
-    free(d);
-}
-
-static int csr_alloc_dev(int M, int N, int64_t NZ, int value_bytes,
-                         spmv_csr_dev **out) {
+int csr_alloc_dev(int M, int N, int64_t NZ, int value_bytes,
+                  spmv_csr_dev **out) {
     int rc = 0;
     spmv_csr_dev *d = (spmv_csr_dev *)calloc(1, sizeof *d);
     if (!d)
@@ -926,6 +903,82 @@ static int csr_alloc_dev(int M, int N, int64_t NZ, int value_bytes,
 fail:
     spmv_csr_release(d);
     return rc;
+}
+
+/* The tail of every operation that makes a new handle on the device.  rc:
+ * what making it answered; d: the handle, holding irp, ja and values when rc
+ * is 0 (NULL when it was never allocated).  Finishes it and publishes it to
+ * *out; on any failure it is released and *out is untouched */
+static int publish_csr_handle(int rc, spmv_csr_dev *d, spmv_csr_dev **out) {
+    if (!rc)
+        rc = finish_csr_handle(d, NULL);
+    if (rc) {
+        spmv_csr_release(d); /* NULL: ignored */
+        return rc;
+    }
+    *out = d;
+    return 0;
+}
+
+/* the one body of spmv_csr_ic0 and spmv_csr_ilu0: `factor` is ic0_factor_dev
+ * or ilu0_factor_dev, Info its record */
+template <typename Info>
+static int csr_factor(const spmv_csr_dev *A, double shift, int max_levels,
+                      int (*factor)(const spmv_csr_dev *, double, int, int,
+                                    spmv_csr_dev **, Info *, hipStream_t),
+                      spmv_csr_dev **out, Info *info) {
+    if (out)
+        *out = NULL; /* on ANY error, the argument checks included */
+    if (!A || !out || !(shift >= 0.0) || !std::isfinite(shift) ||
+        max_levels < 0)
+        return -EINVAL;
+    if (spmv_device_count() == 0)
+        return -ENODEV; /* no handle can be live: the more useful answer */
+    HANDLE_OK(A);
+    if (A->M != A->N)
+        return -EINVAL;
+    if (A->value_bytes != 8)
+        return -ENOTSUP;
+    if (!has_source(A))
+        return -ENODATA; /* spmv_csr_release_source() */
+    spmv_csr_dev *d = NULL;
+    Info got;
+    int rc = factor(A, shift, max_levels ? max_levels : TRSV_DEFAULT_MAX_LEVELS,
+                    g_csr_waves, &d, &got, 0);
+    rc = publish_csr_handle(rc, d, out);
+    if (!rc && info)
+        *info = got;
+    return rc;
+}
+
+extern "C" {
+
+int spmv_dev_fill_synth(double *d_x, int64_t n, uint64_t seed, int64_t first,
+                        void *stream) {
+    if (n <= 0)
+        return 0;
+    hipLaunchKernelGGL(k_fill_x, dim3((unsigned)((n + 255) / 256)), dim3(256),
+                       0, (hipStream_t)stream, d_x, n, seed, first);
+    return hip_errno(hipGetLastError());
+}
+
+/* ------------------------------------------------------------------ */
+/* CSR handle                                                           */
+/* ------------------------------------------------------------------ */
+
+static void teardown(spmv_csr_dev *d) {
+    (void)hipFree(d->irp);
+    (void)hipFree(d->ja);
+    (void)hipFree(d->as);
+    (void)hipFree(d->as32);
+    (void)hipFree(d->rowblk);
+    (void)hipFree(d->rowblk_mode);
+    (void)hipFree(d->seg_partial);
+    (void)hipFree(d->seg_count);
+    (void)hipFree(d->long_rb);
+    panels_free(d->panels);
+    free(d->tune_log);
+    free(d);
 }
 
 static int csr_upload(const sparse_csr *A, int value_bytes, spmv_csr_dev **out) {
@@ -975,7 +1028,7 @@ int spmv_csr_to_f32(const spmv_csr_dev *A, spmv_csr_dev **out) {
     HANDLE_OK(A);
     if (A->value_bytes == 4)
         return -EINVAL;
-    if (!A->ja && A->NZ > 0)
+    if (!has_source(A))
         return -ENODATA; /* spmv_csr_release_source() */
     spmv_csr_dev *d = NULL;
     unsigned *d_over = NULL, over = 0;
@@ -994,21 +1047,12 @@ int spmv_csr_to_f32(const spmv_csr_dev *A, spmv_csr_dev **out) {
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpy(&over, d_over, sizeof(unsigned),
                           hipMemcpyDeviceToHost));
-        if (over) {
+        if (over)
             rc = -ERANGE;
-            goto fail;
-        }
     }
-    rc = finish_csr_handle(d, NULL);
-    if (rc)
-        goto fail;
-    (void)hipFree(d_over);
-    *out = d;
-    return 0;
 fail:
     (void)hipFree(d_over);
-    spmv_csr_release(d);
-    return rc;
+    return publish_csr_handle(rc, d, out);
 }
 
 /* the geometry a transposition of N columns and NZ entries would use
@@ -1042,95 +1086,27 @@ int spmv_csr_transpose(const spmv_csr_dev *A, spmv_csr_dev **out) {
     if (spmv_device_count() == 0)
         return -ENODEV; /* no handle can be live: the more useful answer */
     HANDLE_OK(A);
-    if (!A->ja && A->NZ > 0)
+    if (!has_source(A))
         return -ENODATA; /* spmv_csr_release_source() */
     spmv_csr_dev *d = NULL;
     int rc = csr_alloc_dev(A->N, A->M, A->NZ, A->value_bytes, &d);
     if (rc)
         return rc;
-    rc = csr_transpose_dev(A, d, 0);
-    if (rc)
-        goto fail;
-    rc = finish_csr_handle(d, NULL);
-    if (rc)
-        goto fail;
-    *out = d;
-    return 0;
-fail:
-    spmv_csr_release(d);
-    return rc;
+    return publish_csr_handle(csr_transpose_dev(A, d, 0), d, out);
 }
 
 /* L of A ~ L L^T on A's lower triangle, a new M x M f64 handle
  * (ic0_kernels.hip) */
 int spmv_csr_ic0(const spmv_csr_dev *A, double shift, int max_levels,
                  spmv_csr_dev **out, spmv_ic0_info *info) {
-    if (out)
-        *out = NULL; /* on ANY error, the argument checks included */
-    if (!A || !out || !(shift >= 0.0) || !std::isfinite(shift) ||
-        max_levels < 0)
-        return -EINVAL;
-    if (spmv_device_count() == 0)
-        return -ENODEV; /* no handle can be live: the more useful answer */
-    HANDLE_OK(A);
-    if (A->M != A->N)
-        return -EINVAL;
-    if (A->value_bytes != 8)
-        return -ENOTSUP;
-    if (!A->ja && A->NZ > 0)
-        return -ENODATA; /* spmv_csr_release_source() */
-    spmv_csr_dev *d = NULL;
-    spmv_ic0_info got;
-    int rc = ic0_factor_dev(
-        A, shift, max_levels ? max_levels : TRSV_DEFAULT_MAX_LEVELS,
-        g_csr_waves, csr_alloc_dev, &d, &got, 0);
-    if (rc)
-        return rc;
-    rc = finish_csr_handle(d, NULL);
-    if (rc) {
-        spmv_csr_release(d);
-        return rc;
-    }
-    if (info)
-        *info = got;
-    *out = d;
-    return 0;
+    return csr_factor(A, shift, max_levels, ic0_factor_dev, out, info);
 }
 
 /* L and U of A ~ L U on A's pattern, a new M x M f64 handle
- * (ilu0_kernels.hip): the checks of spmv_csr_ic0, in its order */
+ * (ilu0_kernels.hip) */
 int spmv_csr_ilu0(const spmv_csr_dev *A, double shift, int max_levels,
                   spmv_csr_dev **out, spmv_ilu0_info *info) {
-    if (out)
-        *out = NULL; /* on ANY error, the argument checks included */
-    if (!A || !out || !(shift >= 0.0) || !std::isfinite(shift) ||
-        max_levels < 0)
-        return -EINVAL;
-    if (spmv_device_count() == 0)
-        return -ENODEV; /* no handle can be live: the more useful answer */
-    HANDLE_OK(A);
-    if (A->M != A->N)
-        return -EINVAL;
-    if (A->value_bytes != 8)
-        return -ENOTSUP;
-    if (!A->ja && A->NZ > 0)
-        return -ENODATA; /* spmv_csr_release_source() */
-    spmv_csr_dev *d = NULL;
-    spmv_ilu0_info got;
-    int rc = ilu0_factor_dev(
-        A, shift, max_levels ? max_levels : TRSV_DEFAULT_MAX_LEVELS,
-        g_csr_waves, csr_alloc_dev, &d, &got, 0);
-    if (rc)
-        return rc;
-    rc = finish_csr_handle(d, NULL);
-    if (rc) {
-        spmv_csr_release(d);
-        return rc;
-    }
-    if (info)
-        *info = got;
-    *out = d;
-    return 0;
+    return csr_factor(A, shift, max_levels, ilu0_factor_dev, out, info);
 }
 
 /* the constants of the sparse product (spgemm_plan.h); host arithmetic */
@@ -1171,22 +1147,15 @@ int spmv_csr_spgemm(const spmv_csr_dev *A, const spmv_csr_dev *B,
     HANDLE_OK(B);
     if (A->N != B->M)
         return -EINVAL;
-    if ((!A->ja && A->NZ > 0) || (!B->ja && B->NZ > 0))
+    if (!has_source(A) || !has_source(B))
         return -ENODATA; /* spmv_csr_release_source() */
     spmv_csr_dev *d = NULL;
     spmv_spgemm_info got;
-    int rc = csr_spgemm_dev(A, B, csr_alloc_dev, &d, &got, 0);
-    if (rc)
-        return rc;
-    rc = finish_csr_handle(d, NULL);
-    if (rc) {
-        spmv_csr_release(d);
-        return rc;
-    }
-    if (info)
+    int rc = csr_spgemm_dev(A, B, &d, &got, 0);
+    rc = publish_csr_handle(rc, d, out);
+    if (!rc && info)
         *info = got;
-    *out = d;
-    return 0;
+    return rc;
 }
 
 /* the constants of the sparse sum (add_plan.h); host arithmetic */
@@ -1233,24 +1202,18 @@ int spmv_csr_add(double alpha, const spmv_csr_dev *A, double beta,
     HANDLE_OK(B);
     if (A->M != B->M || A->N != B->N)
         return -EINVAL;
-    if ((!A->ja && A->NZ > 0) || (!B->ja && B->NZ > 0))
+    if (!has_source(A) || !has_source(B))
         return -ENODATA; /* spmv_csr_release_source() */
     spmv_csr_dev *d = NULL;
     spmv_add_info got;
-    int rc = csr_add_dev(alpha, A, beta, B, g_add_class, csr_alloc_dev, &d,
-                         &got, 0);
+    int rc = csr_add_dev(alpha, A, beta, B, g_add_class, &d, &got, 0);
+    const double t = csr_now_ms();
+    rc = publish_csr_handle(rc, d, out);
     if (rc)
         return rc;
-    const double t = csr_add_now_ms();
-    rc = finish_csr_handle(d, NULL);
-    if (rc) {
-        spmv_csr_release(d);
-        return rc;
-    }
-    csr_add_finish_ms(csr_add_now_ms() - t);
+    csr_add_finish_ms(csr_now_ms() - t);
     if (info)
         *info = got;
-    *out = d;
     return 0;
 }
 
@@ -1266,15 +1229,7 @@ int spmv_csr_from_diag(int M, const double *d_diag, spmv_csr_dev **out) {
     int rc = csr_alloc_dev(M, M, M, 8, &d);
     if (rc)
         return rc;
-    rc = csr_from_diag_dev(d_diag, d, 0);
-    if (!rc)
-        rc = finish_csr_handle(d, NULL);
-    if (rc) {
-        spmv_csr_release(d);
-        return rc;
-    }
-    *out = d;
-    return 0;
+    return publish_csr_handle(csr_from_diag_dev(d_diag, d, 0), d, out);
 }
 
 /* a new f64 handle with A's pattern and the values l_i a r_j */
@@ -1287,21 +1242,13 @@ int spmv_csr_scale(const spmv_csr_dev *A, const double *d_left,
     if (spmv_device_count() == 0)
         return -ENODEV; /* no handle can be live: the more useful answer */
     HANDLE_OK(A);
-    if (!A->ja && A->NZ > 0)
+    if (!has_source(A))
         return -ENODATA; /* spmv_csr_release_source() */
     spmv_csr_dev *d = NULL;
     int rc = csr_alloc_dev(A->M, A->N, A->NZ, 8, &d);
     if (rc)
         return rc;
-    rc = csr_scale_dev(A, d_left, d_right, d, 0);
-    if (!rc)
-        rc = finish_csr_handle(d, NULL);
-    if (rc) {
-        spmv_csr_release(d);
-        return rc;
-    }
-    *out = d;
-    return 0;
+    return publish_csr_handle(csr_scale_dev(A, d_left, d_right, d, 0), d, out);
 }
 
 /* PT (A P): the two products, the intermediate released */
@@ -1333,7 +1280,7 @@ int spmv_csr_symmetry(const spmv_csr_dev *A, int *out) {
     if (spmv_device_count() == 0)
         return -ENODEV;
     HANDLE_OK(A);
-    if (!A->ja && A->NZ > 0)
+    if (!has_source(A))
         return -ENODATA; /* spmv_csr_release_source() */
     if (A->M != A->N)
         return 0;
@@ -1367,7 +1314,7 @@ int spmv_csr_colour(const spmv_csr_dev *A, uint32_t seed, int max_rounds,
     HANDLE_OK(A);
     if (A->M != A->N)
         return -EINVAL;
-    if (!A->ja && A->NZ > 0)
+    if (!has_source(A))
         return -ENODATA; /* spmv_csr_release_source() */
     return csr_colour_dev(A, seed,
                           max_rounds ? max_rounds : COLOUR_DEFAULT_MAX_ROUNDS,
@@ -1383,20 +1330,11 @@ int spmv_csr_permute(const spmv_csr_dev *A, const int *d_row_new_of_old,
     if (spmv_device_count() == 0)
         return -ENODEV; /* no handle can be live: the more useful answer */
     HANDLE_OK(A);
-    if (!A->ja && A->NZ > 0)
+    if (!has_source(A))
         return -ENODATA; /* spmv_csr_release_source() */
     spmv_csr_dev *d = NULL;
-    int rc = csr_permute_dev(A, d_row_new_of_old, d_col_new_of_old,
-                             csr_alloc_dev, &d, 0);
-    if (rc)
-        return rc;
-    rc = finish_csr_handle(d, NULL);
-    if (rc) {
-        spmv_csr_release(d);
-        return rc;
-    }
-    *out = d;
-    return 0;
+    return publish_csr_handle(
+        csr_permute_dev(A, d_row_new_of_old, d_col_new_of_old, &d, 0), d, out);
 }
 
 int spmv_permute_vectors(const int *d_new_of_old, int M, int k, int inverse,
@@ -1465,7 +1403,7 @@ static int trsv_analyse(const spmv_csr_dev *A, int uplo, int unit,
     HANDLE_OK(A);
     if (A->M != A->N)
         return -EINVAL;
-    if (!A->ja && A->NZ > 0)
+    if (!has_source(A))
         return -ENODATA; /* spmv_csr_release_source() */
     spmv_trsv_plan *P = (spmv_trsv_plan *)calloc(1, sizeof *P);
     if (!P)
@@ -1716,7 +1654,7 @@ int spmv_csr_download(const spmv_csr_dev *A, sparse_csr **out) {
     HANDLE_OK(A);
     if (!out)
         return -EINVAL;
-    if (!A->ja && A->NZ > 0)
+    if (!has_source(A))
         return -ENODATA; /* spmv_csr_release_source() */
     if (A->NZ > INT32_MAX)
         return -EOVERFLOW;
@@ -1962,7 +1900,7 @@ static int hll_from_csr(const spmv_csr_dev *A, const V *A_as, int is_col_major,
     HANDLE_OK(A);
     if (!out)
         return -EINVAL;
-    if (!A->ja && A->NZ > 0)
+    if (!has_source(A))
         return -ENODATA;
     *out = NULL;
     const int M = A->M, nb = (M + 31) / 32;
@@ -2180,10 +2118,6 @@ int64_t spmv_hll_kernel_bytes(const spmv_hll_dev *H, int kernel) {
 /* ------------------------------------------------------------------ */
 
 /* where the two formats differ */
-static bool has_source(const spmv_csr_dev *A) { return A->ja || A->NZ == 0; }
-static bool has_source(const spmv_hll_dev *H) {
-    return H->ja || H->off16 || H->slots == 0;
-}
 /* compact handles (16-bit column offsets, spmv_hll_to_index16): HLL only */
 static bool is_compact(const spmv_csr_dev *) { return false; }
 static bool is_compact(const spmv_hll_dev *H) { return H->index_bytes == 2; }
@@ -2569,10 +2503,9 @@ static int amg_setup(const spmv_csr_dev *A0, double theta, int sweeps,
     int *d_agg = NULL;
     spmv_csr_dev *T = NULL;
     const spmv_csr_dev *A = A0;
-    const auto now = [] { return 1e3 * panels_ops::now_s(); };
-    double t = now();
+    double t = csr_now_ms();
     const auto lap = [&](int phase) {
-        const double n = now();
+        const double n = csr_now_ms();
         ph[phase] += n - t;
         t = n;
     };
@@ -2592,7 +2525,7 @@ static int amg_setup(const spmv_csr_dev *A0, double theta, int sweeps,
     for (int l = 0;; ++l) {
         amg_level &L = H->lv[l];
         spmv_aggregate_info ai;
-        spmv_csr_dev *C = NULL;
+        spmv_csr_dev *C = NULL, *raw = NULL; /* raw: T before it is finished */
         rows[l] = A->M;
         HIP_TRY(hipMalloc((void **)&L.w,
                           (size_t)(A->M > 0 ? A->M : 1) * sizeof(double)));
@@ -2620,12 +2553,10 @@ static int amg_setup(const spmv_csr_dev *A0, double theta, int sweeps,
         lap(1);
         if (ai.aggregates == A->M)
             break;
-        rc = csr_alloc_dev(A->M, ai.aggregates, A->M, 8, &T);
-        if (rc)
-            goto fail;
-        rc = amg_tentative_dev(A->M, d_agg, T, 0);
+        rc = csr_alloc_dev(A->M, ai.aggregates, A->M, 8, &raw);
         if (!rc)
-            rc = finish_csr_handle(T, NULL);
+            rc = amg_tentative_dev(A->M, d_agg, raw, 0);
+        rc = publish_csr_handle(rc, raw, &T);
         if (!rc)
             rc = spmv_csr_spgemm(A, T, &L.P, NULL);
         if (!rc)
@@ -3768,7 +3699,7 @@ int spmv_csr_aggregate(const spmv_csr_dev *A, double theta, uint32_t seed,
         return -EINVAL;
     if (A->value_bytes != 8)
         return -ENOTSUP;
-    if (!A->ja && A->NZ > 0)
+    if (!has_source(A))
         return -ENODATA; /* spmv_csr_release_source() */
     return amg_aggregate_dev(A, theta * theta, seed, amg_max_rounds(max_rounds),
                              d_agg, info, 0);
@@ -3791,7 +3722,7 @@ int spmv_csr_amg_setup(const spmv_csr_dev *A, double theta, int sweeps,
         return -EINVAL;
     if (A->value_bytes != 8)
         return -ENOTSUP;
-    if (!A->ja && A->NZ > 0)
+    if (!has_source(A))
         return -ENODATA; /* spmv_csr_release_source() */
     return amg_setup(A, theta, sweeps, coarse_sweeps, min_rows,
                      max_levels ? max_levels : 16, seed, kmax, out);

@@ -4,7 +4,7 @@
  * cg_kernels.hip, bicgstab_kernels.hip, cgls_kernels.hip, minres_kernels.hip,
  * diag_kernels.hip, transpose_kernels.hip, trsv_kernels.hip, ic0_kernels.hip,
  * ilu0_kernels.hip, spgemm_kernels.hip, add_kernels.hip, amg_kernels.hip,
- * panels.hip, mgpu.hip, and
+ * csr_build.hip, panels.hip, mgpu.hip, and
  * mat_ref.h on behalf of the first and the last).
  * Not installed.
  */
@@ -382,6 +382,28 @@ __device__ __forceinline__ double wave_ordered_sum(const double *part, int n,
     return s;
 }
 
+/* lanes of this wavefront below the caller whose bit is set in mask */
+__device__ __forceinline__ unsigned lanes_below(unsigned long long mask) {
+    return __builtin_amdgcn_mbcnt_hi(
+        (unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+}
+
+/* the wavefront's sum / maximum of v in lane 0 (all 64 lanes call) */
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+#pragma unroll
+    for (int d = WAVE / 2; d > 0; d >>= 1)
+        v += __shfl_down(v, d, WAVE);
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
+#pragma unroll
+    for (int d = WAVE / 2; d > 0; d >>= 1) {
+        const unsigned long long o = __shfl_down(v, d, WAVE);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
 /* Columns of hack block b (`rows` = its row count).  The slot count is 64-bit:
  * a hub block of 2^27 columns holds 2^32 slots, and `(unsigned)(off[b + 1] -
  * off[b])` -- a 32-bit division is cheaper -- silently halved such a block */
@@ -622,6 +644,12 @@ int gmres_solve(const cg_matrix *A, int k, const double *B, int64_t ldb,
 int csr_diag(const spmv_csr_dev *A, double *out, int invert, hipStream_t s);
 int hll_diag(const spmv_hll_dev *H, double *out, int invert, hipStream_t s);
 
+/* A new handle of the live table with irp, ja and values of value_bytes
+ * allocated and nothing in them (engine.hip).  Every device operation that
+ * makes a handle takes its result from here; on an error *out is untouched */
+int csr_alloc_dev(int M, int N, int64_t NZ, int value_bytes,
+                  spmv_csr_dev **out);
+
 /* T = A^T (transpose_kernels.hip; spmv_csr_transpose): T comes from
  * csr_alloc_dev(N, M, NZ, value type of A) and gets its irp, ja and values;
  * blocks; -EDOM when a column of A lies outside [0, N).  csr_equal_dev: two
@@ -630,9 +658,6 @@ int hll_diag(const spmv_hll_dev *H, double *out, int invert, hipStream_t s);
 int csr_transpose_dev(const spmv_csr_dev *A, spmv_csr_dev *T, hipStream_t s);
 int csr_equal_dev(const spmv_csr_dev *X, const spmv_csr_dev *Y, int *pattern,
                   int *values, hipStream_t s);
-/* exclusive scan of n ints in place; sums: transpose_scan_tiles(n) ints of
- * scratch (transpose_kernels.hip; the triangular analysis scans with it too) */
-void tr_scan(int *data, int64_t n, int *sums, hipStream_t s);
 
 /*
  * Level-scheduled triangular solve (trsv_kernels.hip; spmv_csr_trsv_analyse,
@@ -677,72 +702,62 @@ int trsv_solve_dev(const spmv_trsv_plan *P, int waves, int k, const double *B,
 /*
  * Zero-fill incomplete Cholesky (ic0_kernels.hip; spmv_csr_ic0).  The caller
  * has checked the handle (square, f64, with its source).  *out comes from
- * `alloc` (engine.hip: csr_alloc_dev) once the pattern passed its check and the
- * schedule is known, and holds irp, ja and the factor; the caller finishes it
- * as spmv_csr_transpose does.  waves 0 = each kernel's default.  Blocks; on an
- * error *out is untouched and everything is freed.
+ * csr_alloc_dev once the pattern passed its check and the schedule is known,
+ * and holds irp, ja and the factor; the caller finishes it (engine.hip,
+ * publish_csr_handle).  waves 0 = each kernel's default.  Blocks; on an error
+ * *out is untouched and everything is freed.
  */
-typedef int (*ic0_alloc_fn)(int M, int N, int64_t NZ, int value_bytes,
-                            spmv_csr_dev **out);
 int ic0_factor_dev(const spmv_csr_dev *A, double shift, int max_levels,
-                   int waves, ic0_alloc_fn alloc, spmv_csr_dev **out,
-                   spmv_ic0_info *info, hipStream_t s);
+                   int waves, spmv_csr_dev **out, spmv_ic0_info *info,
+                   hipStream_t s);
 /*
  * Zero-fill incomplete LU (ilu0_kernels.hip; spmv_csr_ilu0): the same
  * arrangement.  *out holds A's irp and ja and the factor, L strictly below the
  * diagonal (its unit diagonal implied), U on and above it.
  */
 int ilu0_factor_dev(const spmv_csr_dev *A, double shift, int max_levels,
-                    int waves, ic0_alloc_fn alloc, spmv_csr_dev **out,
-                    spmv_ilu0_info *info, hipStream_t s);
+                    int waves, spmv_csr_dev **out, spmv_ilu0_info *info,
+                    hipStream_t s);
 
 /*
  * Colouring and permutation (colour_kernels.hip; spmv_csr_colour,
  * spmv_csr_permute, spmv_permute_vectors).  The caller has checked the handle
  * (with its source; square for the colouring) and the arguments.  Both block,
  * free their scratch on every path and leave the caller's arrays / *out
- * untouched on an error.  csr_permute_dev takes *out from `alloc` once p and q
- * passed their checks; the caller finishes it as spmv_csr_transpose does.
+ * untouched on an error.  csr_permute_dev takes *out from csr_alloc_dev once p
+ * and q passed their checks; the caller finishes it.
  */
 int csr_colour_dev(const spmv_csr_dev *A, uint32_t seed, int max_rounds,
                    int *d_colour, int *d_new_of_old, spmv_colour_info *info,
                    hipStream_t s);
 int csr_permute_dev(const spmv_csr_dev *A, const int *p, const int *q,
-                    ic0_alloc_fn alloc, spmv_csr_dev **out, hipStream_t s);
+                    spmv_csr_dev **out, hipStream_t s);
 /*
  * C = A B (spgemm_kernels.hip; spmv_csr_spgemm).  The caller has checked the
- * handles (live, with their sources, A->N == B->M).  *out comes from `alloc`
- * once the entries of C are known and holds irp, ja and the values; the caller
- * finishes it as spmv_csr_transpose does.  Blocks; on an error *out and *info
- * are untouched and everything is freed.
+ * handles (live, with their sources, A->N == B->M).  *out comes from
+ * csr_alloc_dev once the entries of C are known and holds irp, ja and the
+ * values; the caller finishes it.  Blocks; on an error *out and *info are
+ * untouched and everything is freed.
  */
 int csr_spgemm_dev(const spmv_csr_dev *A, const spmv_csr_dev *B,
-                   ic0_alloc_fn alloc, spmv_csr_dev **out,
-                   spmv_spgemm_info *info, hipStream_t s);
+                   spmv_csr_dev **out, spmv_spgemm_info *info, hipStream_t s);
 /* host-clock ms of the last successful product of this process: checks and
  * bounds, lists and symbolic pass, scan + allocation + numeric pass, and the
  * part of the last two spent in the fallback's launches */
 void csr_spgemm_last_phases(double ms[4]);
-/* the product's device check of B, for the sum's two operands: *d_flags |= 1
- * for a column outside [0, B->N), |= 2 for a row that is not strictly
- * ascending; asynchronous */
-int csr_check_rows_dev(const spmv_csr_dev *B, unsigned long long *d_flags,
-                       hipStream_t s);
 /*
  * C = alpha A + beta B (add_kernels.hip; spmv_csr_add).  The caller has
  * checked the handles (live, with their sources, one shape) and the scalars.
- * mode: spmv_add_set_class.  *out comes from `alloc` once the entries of C are
- * known and holds irp, ja and the values; the caller finishes it as
- * spmv_csr_transpose does and reports the time of that with
- * csr_add_finish_ms.  Blocks; on an error *out and *info are untouched and
- * everything is freed.
+ * mode: spmv_add_set_class.  *out comes from csr_alloc_dev once the entries of
+ * C are known and holds irp, ja and the values; the caller finishes it and
+ * reports the time of that with csr_add_finish_ms.  Blocks; on an error *out
+ * and *info are untouched and everything is freed.
  */
 int csr_add_dev(double alpha, const spmv_csr_dev *A, double beta,
-                const spmv_csr_dev *B, int mode, ic0_alloc_fn alloc,
-                spmv_csr_dev **out, spmv_add_info *info, hipStream_t s);
+                const spmv_csr_dev *B, int mode, spmv_csr_dev **out,
+                spmv_add_info *info, hipStream_t s);
 void csr_add_last_phases(double ms[3]);
 void csr_add_finish_ms(double ms);
-double csr_add_now_ms(void);
 /* the companions: D (M x M, M entries, f64, allocated) gets the arrays of
  * diag(d) (d NULL: the identity); S (A's shape and entry count, f64,
  * allocated) gets A's irp and ja and the scaled values, -EDOM when d_right is

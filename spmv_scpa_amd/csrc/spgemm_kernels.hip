@@ -10,20 +10,17 @@
  * own (this file is compiled with contraction off: no fused multiply-add).
  *
  * The geometry (size classes, tables, LDS, scratch, batches) is
- * spgemm_plan.h's.  The launches, in order -- the kernel boundary is the only
+ * spgemm_plan.h's; the steps every builder of a handle shares are
+ * csr_build.h's.  The launches, in order -- the kernel boundary is the only
  * ordering between workgroups, nothing waits on another workgroup:
  *
- *   k_sg_check_b   one lane per entry of B: column inside [0, N), and above
- *                  its left neighbour in the same row
+ *   csr_check_rows_dev (B)
  *   k_sg_bound     one lane per row of A: ub[r], A's columns inside [0, K),
  *                  and the totals (integer atomics: a SUM, a MAXIMUM and a
  *                  COUNT do not depend on the order of arrival)
- *   k_sg_fill      the rows of each class, listed.  The order inside a list
- *                  comes from an atomic cursor and may differ from run to
- *                  run; nothing of C depends on it: a list only says which
- *                  team serves which row
+ *   csr_lists_dev  the rows of each class (sg_class of ub[r]), listed
  *   k_sg_rows<.., false>, k_sg_fb_count      symbolic: distinct columns per row
- *   k_sg_total, the exclusive scan of the transposition      C's IRP
+ *   csr_total_dev, csr_alloc_scanned_dev     C's IRP
  *   k_sg_rows<.., true>, k_sg_fb_rows        numeric: JA and AS of C
  *
  * Classes 0..2 (k_sg_rows): a team of lanes owns the row.  The columns go into
@@ -49,13 +46,10 @@
  * outside its range is skipped here (and refused by the launcher before
  * anything is allocated for C), so nothing is ever written out of bounds.
  */
-#include <algorithm>
 #include <string.h>
-#include <time.h>
 
-#include "hip_common.h"
+#include "csr_build.h"
 #include "spgemm_plan.h"
-#include "transpose_plan.h"
 
 /* every product and every sum is rounded on its own */
 #pragma clang fp contract(off)
@@ -87,56 +81,15 @@ __device__ __forceinline__ int sg_class(int64_t ub) {
                                      : 3;
 }
 
-__device__ __forceinline__ unsigned sg_lanes_below(sg_u64 mask) {
-    return __builtin_amdgcn_mbcnt_hi(
-        (unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
-
-__device__ __forceinline__ sg_u64 sg_wave_sum(sg_u64 v) {
-#pragma unroll
-    for (int d = WAVE / 2; d > 0; d >>= 1)
-        v += __shfl_down(v, d, WAVE);
-    return v; /* lane 0 */
-}
+/* the class of a row, for csr_lists_dev */
+struct sg_row_class {
+    const int64_t *ub;
+    __device__ int operator()(int64_t r) const { return sg_class(ub[r]); }
+};
 
 /* ------------------------------------------------------------------ */
-/* checks, bounds, lists                                                */
+/* bounds                                                               */
 /* ------------------------------------------------------------------ */
-
-__global__ void __launch_bounds__(SG_T)
-k_sg_check_b(const int *__restrict__ irp, const int *__restrict__ ja, int K,
-             int64_t NZ, int N, sg_u64 *__restrict__ head) {
-    const int64_t q = (int64_t)blockIdx.x * SG_T + threadIdx.x;
-    if (q >= NZ)
-        return;
-    const int c = ja[q];
-    unsigned f = (unsigned)c < (unsigned)N ? 0u : 1u;
-    int lo = 0, hi = K; /* irp[lo] <= q < irp[hi] */
-    while (hi - lo > 1) {
-        const int mid = lo + (hi - lo) / 2;
-        if (irp[mid] <= q)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    if (q > irp[lo] && ja[q - 1] >= c)
-        f |= 2u;
-    if (f)
-        atomicOr(head + SG_FLAGS, (sg_u64)f);
-}
-
-/* *d_flags |= 1: a column of B outside [0, B->N); |= 2: a row of B that is not
- * strictly ascending.  Asynchronous; the sum checks both its operands with it
- * (add_kernels.hip) */
-int csr_check_rows_dev(const spmv_csr_dev *B, unsigned long long *d_flags,
-                       hipStream_t s) {
-    if (B->NZ > 0)
-        hipLaunchKernelGGL(k_sg_check_b,
-                           dim3((unsigned)spgemm_ceil_div(B->NZ, SG_T)),
-                           dim3(SG_T), 0, s, B->irp, B->ja, B->M, B->NZ, B->N,
-                           d_flags + SG_FLAGS);
-    return hip_errno(hipGetLastError());
-}
 
 __global__ void __launch_bounds__(SG_T)
 k_sg_bound(int M, int K, const int *__restrict__ irp_a,
@@ -165,13 +118,8 @@ k_sg_bound(int M, int K, const int *__restrict__ irp_a,
         if (mask && lane == __ffsll((long long)mask) - 1)
             atomicAdd(head + SG_ROWS + c, (sg_u64)__popcll(mask));
     }
-    sg_u64 most = (sg_u64)u;
-#pragma unroll
-    for (int d = WAVE / 2; d > 0; d >>= 1) {
-        const sg_u64 o = __shfl_down(most, d, WAVE);
-        most = o > most ? o : most;
-    }
-    const sg_u64 sum = sg_wave_sum((sg_u64)u);
+    const sg_u64 most = wave_max((sg_u64)u);
+    const sg_u64 sum = wave_sum((sg_u64)u);
     const sg_u64 anybad = __ballot(bad);
     if (lane == 0) {
         if (sum)
@@ -181,40 +129,6 @@ k_sg_bound(int M, int K, const int *__restrict__ irp_a,
         if (anybad)
             atomicOr(head + SG_FLAGS, (sg_u64)1);
     }
-}
-
-/* the cursors start at the classes' first places (set by the host) */
-__global__ void __launch_bounds__(SG_T)
-k_sg_fill(int M, const int64_t *__restrict__ ub, sg_u64 *__restrict__ head,
-          int *__restrict__ list) {
-    const int64_t r = (int64_t)blockIdx.x * SG_T + threadIdx.x;
-    const int lane = threadIdx.x & (WAVE - 1);
-    const int cls = r < M ? sg_class(ub[r]) : -1;
-#pragma unroll
-    for (int c = 0; c < SPGEMM_CLASSES; ++c) {
-        const sg_u64 mask = __ballot(cls == c);
-        if (!mask) /* wavefront-uniform */
-            continue;
-        const int leader = __ffsll((long long)mask) - 1;
-        sg_u64 base = 0;
-        if (lane == leader)
-            base = atomicAdd(head + SG_CURSOR + c, (sg_u64)__popcll(mask));
-        base = __shfl(base, leader, WAVE);
-        if (cls == c) /* base + rank < M: the classes' counts sum to M */
-            list[base + sg_lanes_below(mask)] = (int)r;
-    }
-}
-
-__global__ void __launch_bounds__(SG_T)
-k_sg_total(const int *__restrict__ count, int M, sg_u64 *__restrict__ head) {
-    const int64_t first = (int64_t)blockIdx.x * SG_T + threadIdx.x;
-    const int64_t stride = (int64_t)gridDim.x * SG_T;
-    sg_u64 n = 0;
-    for (int64_t r = first; r < M; r += stride)
-        n += (sg_u64)count[r];
-    n = sg_wave_sum(n);
-    if ((threadIdx.x & (WAVE - 1)) == 0 && n)
-        atomicAdd(head + SG_NZ, n);
 }
 
 /* ------------------------------------------------------------------ */
@@ -427,7 +341,7 @@ k_sg_fb_count(const int *__restrict__ list, const int *__restrict__ irp_a,
             mine[w] = 0u;
         }
     }
-    n = (int)sg_wave_sum((sg_u64)n);
+    n = (int)wave_sum((sg_u64)n);
     if (lane == 0 && n)
         atomicAdd(&total, n);
     __syncthreads();
@@ -538,12 +452,6 @@ void csr_spgemm_last_phases(double ms[4]) {
         ms[i] = g_sg_phase_ms[i];
 }
 
-static double sg_now_ms(void) {
-    struct timespec t;
-    clock_gettime(CLOCK_MONOTONIC, &t);
-    return 1e3 * (double)t.tv_sec + 1e-6 * (double)t.tv_nsec;
-}
-
 struct sg_args {
     const spmv_csr_dev *A, *B;
     const int *list;
@@ -611,13 +519,12 @@ static int sg_numeric(const sg_args &g, const int64_t *first,
     return hip_errno(hipGetLastError());
 }
 
-/* *out (M x N, f64, from `alloc` once the entries of C are known) gets its
+/* *out (M x N, f64, allocated once the entries of C are known) gets its
  * irp, ja and values.  Blocks.  -EDOM: a column outside its range; -EINVAL: a
  * row of B that is not strictly ascending; -EOVERFLOW: more than INT32_MAX
  * entries.  On an error *out is untouched and everything is freed. */
 int csr_spgemm_dev(const spmv_csr_dev *A, const spmv_csr_dev *B,
-                   ic0_alloc_fn alloc, spmv_csr_dev **out,
-                   spmv_spgemm_info *info, hipStream_t s) {
+                   spmv_csr_dev **out, spmv_spgemm_info *info, hipStream_t s) {
     int rc = 0;
     const int M = A->M, K = A->N, N = B->N;
     spgemm_plan pl;
@@ -634,10 +541,9 @@ int csr_spgemm_dev(const spmv_csr_dev *A, const spmv_csr_dev *B,
     unsigned *bits = NULL;
     int64_t nz = 0;
     sg_args g;
-    double t0 = sg_now_ms(), t1 = 0, t2 = 0;
+    double t0 = csr_now_ms(), t1 = 0, t2 = 0;
     float fb_sym = 0.f, fb_num = 0.f;
     const dim3 block(SG_T);
-    const dim3 row_grid((unsigned)spgemm_ceil_div(M, SG_T));
     rc = spgemm_plan_make(M, K, N, &pl);
     if (rc)
         return rc;
@@ -652,24 +558,19 @@ int csr_spgemm_dev(const spmv_csr_dev *A, const spmv_csr_dev *B,
     HIP_TRY(hipMemsetAsync(head, 0, SPGEMM_HEAD_WORDS * 8, s));
     HIP_TRY(hipMemsetAsync(count, 0, ((size_t)M + 1) * sizeof(int), s));
     /* 1. the checks and the bounds */
-    rc = csr_check_rows_dev(B, head, s);
+    rc = csr_check_rows_dev(B, head + SG_FLAGS, s);
     if (rc)
         goto fail;
     if (M > 0)
-        hipLaunchKernelGGL(k_sg_bound, row_grid, block, 0, s, M, K, A->irp,
-                           A->ja, B->irp, ub, head);
+        hipLaunchKernelGGL(k_sg_bound, grid_for(M, SG_T), block, 0, s, M, K,
+                           A->irp, A->ja, B->irp, ub, head);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(h, head, sizeof h, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    t1 = sg_now_ms();
-    if (h[SG_FLAGS] & 1u) {
-        rc = -EDOM;
+    t1 = csr_now_ms();
+    rc = csr_flags_errno(h[SG_FLAGS]);
+    if (rc)
         goto fail;
-    }
-    if (h[SG_FLAGS] & 2u) {
-        rc = -EINVAL;
-        goto fail;
-    }
     /* 2. the lists of the classes, one after the other */
     for (int c = 0, at = 0; c < SPGEMM_CLASSES; ++c) {
         rows[c] = (int64_t)h[SG_ROWS + c];
@@ -684,8 +585,8 @@ int csr_spgemm_dev(const spmv_csr_dev *A, const spmv_csr_dev *B,
     if (M > 0) {
         HIP_TRY(hipMemcpyAsync(head + SG_CURSOR, cursor, sizeof cursor,
                                hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_sg_fill, row_grid, block, 0, s, M, ub, head,
-                           list);
+        csr_lists_dev<SPGEMM_CLASSES>(M, sg_row_class{ub}, head + SG_CURSOR,
+                                      list, s);
     }
     g.A = A;
     g.B = B;
@@ -722,42 +623,26 @@ int csr_spgemm_dev(const spmv_csr_dev *A, const spmv_csr_dev *B,
         HIP_TRY(hipEventRecord(scratch.ev[1], s));
     }
     /* 4. C's IRP, and the one thing that can still refuse the product */
-    if (M > 0)
-        hipLaunchKernelGGL(k_sg_total,
-                           dim3((unsigned)std::min<int64_t>(
-                               4096, spgemm_ceil_div(M, SG_T))),
-                           block, 0, s, count, M, head);
-    HIP_TRY(hipGetLastError());
+    rc = csr_total_dev(count, M, head + SG_NZ, s);
+    if (rc)
+        goto fail;
     HIP_TRY(hipMemcpyAsync(h, head, sizeof h, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    t2 = sg_now_ms();
+    t2 = csr_now_ms();
     nz = (int64_t)h[SG_NZ];
     rc = spgemm_nz_guard(nz);
+    if (!rc)
+        rc = csr_alloc_scanned_dev(M, N, nz, count, sums, NULL, &Cm, s);
     if (rc)
         goto fail;
-    tr_scan(count, (int64_t)M + 1, sums, s);
-    HIP_TRY(hipGetLastError());
-    rc = alloc(M, N, nz, 8, &Cm);
-    if (rc)
-        goto fail;
-    HIP_TRY(hipMemcpyAsync(Cm->irp, count, ((size_t)M + 1) * sizeof(int),
-                           hipMemcpyDeviceToDevice, s));
     /* 5. numeric */
     g.irp_c = Cm->irp;
     g.ja_c = Cm->ja;
     g.as_c = Cm->as;
-    if (A->value_bytes == 4 && B->value_bytes == 4)
-        rc = sg_numeric<float, float>(g, first, rows, fb, acc, bits, scratch.ev,
-                                        s);
-    else if (A->value_bytes == 4)
-        rc = sg_numeric<float, double>(g, first, rows, fb, acc, bits, scratch.ev,
-                                        s);
-    else if (B->value_bytes == 4)
-        rc = sg_numeric<double, float>(g, first, rows, fb, acc, bits, scratch.ev,
-                                        s);
-    else
-        rc = sg_numeric<double, double>(g, first, rows, fb, acc, bits, scratch.ev,
-                                        s);
+    rc = csr_value_types(A, B, [&](auto va, auto vb) {
+        return sg_numeric<decltype(va), decltype(vb)>(g, first, rows, fb, acc,
+                                                      bits, scratch.ev, s);
+    });
     if (rc)
         goto fail;
     HIP_TRY(hipStreamSynchronize(s));
@@ -767,7 +652,7 @@ int csr_spgemm_dev(const spmv_csr_dev *A, const spmv_csr_dev *B,
     }
     g_sg_phase_ms[0] = t1 - t0;
     g_sg_phase_ms[1] = t2 - t1;
-    g_sg_phase_ms[2] = sg_now_ms() - t2;
+    g_sg_phase_ms[2] = csr_now_ms() - t2;
     g_sg_phase_ms[3] = (double)fb_sym + (double)fb_num;
     if (info) {
         info->products = (int64_t)h[SG_PRODUCTS];

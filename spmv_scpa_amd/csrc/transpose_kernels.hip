@@ -12,8 +12,9 @@
  *   k_tr_hist     workgroup w counts the digits of its tile into
  *                 counter[digit * workgroups + w] (LDS integer atomics: a
  *                 COUNT does not depend on the order of arrival)
- *   scan          exclusive scan over the flattened counters (three launches,
- *                 the same three that turn the column counts into T's IRP)
+ *   scan          exclusive scan over the flattened counters (tr_scan of
+ *                 csr_build.hip, which also turns the column counts into T's
+ *                 IRP)
  *   k_tr_scatter  a key goes to counter[digit][w] + its stable rank among the
  *                 equal digits of the tile.  The tile is walked in strips of
  *                 one key per lane, in order; inside a wavefront the rank is
@@ -35,128 +36,17 @@
  * Index arithmetic that can reach NZ or 2^digit_bits * workgroups is 64-bit;
  * positions and counts fit 32 bits because IRP is `int`.
  */
-#include "hip_common.h"
-#include "transpose_plan.h"
+#include "csr_build.h"
 
 #define TR_T TRANSPOSE_THREADS
 #define TR_WAVES (TR_T / WAVE)
 #define TR_RADIX TRANSPOSE_RADIX
 #define TR_BITS TRANSPOSE_DIGIT_BITS
-#define TR_SCAN_U TRANSPOSE_SCAN_PER_THREAD
-#define TR_SUMS_T 1024 /* threads of the single workgroup of k_tr_scan_sums */
 
 static_assert(TR_T == TR_RADIX, "k_tr_scatter: one thread per digit");
 
 __device__ __forceinline__ unsigned tr_digit(unsigned key, int shift) {
     return (key >> shift) & (TR_RADIX - 1);
-}
-
-/* lanes of this wavefront below the caller whose bit is set in mask */
-__device__ __forceinline__ unsigned tr_lanes_below(unsigned long long mask) {
-    return __builtin_amdgcn_mbcnt_hi(
-        (unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
-
-/* inclusive scan of v over the wavefront */
-__device__ __forceinline__ int tr_wave_scan(int v, int lane) {
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        const int t = __shfl_up(v, d, WAVE);
-        if (lane >= d)
-            v += t;
-    }
-    return v;
-}
-
-/* ------------------------------------------------------------------ */
-/* exclusive scan of n ints, in place                                   */
-/* ------------------------------------------------------------------ */
-
-/* tile b = ints [b * TRANSPOSE_SCAN_TILE, ...): scanned on its own,
- * sums[b] = its total */
-__global__ void __launch_bounds__(TR_T)
-k_tr_scan_local(int *__restrict__ data, int64_t n, int *__restrict__ sums) {
-    __shared__ int wsum[TR_WAVES];
-    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    const int64_t base =
-        (int64_t)blockIdx.x * TRANSPOSE_SCAN_TILE + (int64_t)tid * TR_SCAN_U;
-    int v[TR_SCAN_U];
-    int run = 0;
-#pragma unroll
-    for (int u = 0; u < TR_SCAN_U; ++u) {
-        const int t = base + u < n ? data[base + u] : 0;
-        v[u] = run;
-        run += t;
-    }
-    const int incl = tr_wave_scan(run, lane);
-    if (lane == WAVE - 1)
-        wsum[wave] = incl;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < TR_WAVES; ++w) {
-        before += w < wave ? wsum[w] : 0;
-        total += wsum[w];
-    }
-    const int excl = before + incl - run;
-#pragma unroll
-    for (int u = 0; u < TR_SCAN_U; ++u)
-        if (base + u < n)
-            data[base + u] = v[u] + excl;
-    if (tid == 0)
-        sums[blockIdx.x] = total;
-}
-
-/* the m tile sums, scanned in place by ONE workgroup that carries its total
- * from chunk to chunk */
-__global__ void __launch_bounds__(TR_SUMS_T)
-k_tr_scan_sums(int *__restrict__ sums, int64_t m) {
-    __shared__ int wsum[TR_SUMS_T / WAVE];
-    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-    int carry = 0;
-    for (int64_t b = 0; b < m; b += TR_SUMS_T) { /* workgroup-uniform */
-        const int64_t i = b + tid;
-        const int x = i < m ? sums[i] : 0;
-        const int incl = tr_wave_scan(x, lane);
-        if (lane == WAVE - 1)
-            wsum[wave] = incl;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < TR_SUMS_T / WAVE; ++w) {
-            before += w < wave ? wsum[w] : 0;
-            total += wsum[w];
-        }
-        if (i < m)
-            sums[i] = carry + before + incl - x;
-        carry += total;
-        __syncthreads(); /* wsum is rewritten by the next chunk */
-    }
-}
-
-__global__ void __launch_bounds__(TR_T)
-k_tr_scan_add(int *__restrict__ data, int64_t n, const int *__restrict__ sums) {
-    const int64_t base = (int64_t)blockIdx.x * TRANSPOSE_SCAN_TILE +
-                         (int64_t)threadIdx.x * TR_SCAN_U;
-    const int add = sums[blockIdx.x];
-#pragma unroll
-    for (int u = 0; u < TR_SCAN_U; ++u)
-        if (base + u < n)
-            data[base + u] += add;
-}
-
-void tr_scan(int *data, int64_t n, int *sums, hipStream_t s) {
-    const int64_t tiles = transpose_scan_tiles(n);
-    if (tiles == 0)
-        return;
-    hipLaunchKernelGGL(k_tr_scan_local, dim3((unsigned)tiles), dim3(TR_T), 0, s,
-                       data, n, sums);
-    if (tiles == 1)
-        return; /* one tile: its local scan is the scan */
-    hipLaunchKernelGGL(k_tr_scan_sums, dim3(1), dim3(TR_SUMS_T), 0, s, sums,
-                       tiles);
-    hipLaunchKernelGGL(k_tr_scan_add, dim3((unsigned)tiles), dim3(TR_T), 0, s,
-                       data, n, sums);
 }
 
 /* ------------------------------------------------------------------ */
@@ -175,7 +65,7 @@ k_tr_colcount(const int *__restrict__ ja, int64_t NZ, int N,
     if ((unsigned)c < (unsigned)N)
         atomicAdd(cnt + c, 1);
     else
-        atomicOr(flag, 1u);
+        atomicOr(flag, CSR_BAD_COLUMN);
 }
 
 /* FIRST: the keys are A's JA; else the .x of the pairs */
@@ -241,7 +131,7 @@ k_tr_scatter(const int *__restrict__ ja, const uint2 *__restrict__ src,
             const unsigned long long bal = __ballot(bit);
             mask &= bit ? bal : ~bal;
         }
-        const unsigned rank = tr_lanes_below(mask);
+        const unsigned rank = lanes_below(mask);
         if (valid && rank == 0)
             wcnt[wave][d] = (unsigned)__popcll(mask);
         __syncthreads();
@@ -396,8 +286,7 @@ int csr_transpose_dev(const spmv_csr_dev *A, spmv_csr_dev *T, hipStream_t s) {
                                hipMemcpyDeviceToHost, s));
     }
     HIP_TRY(hipStreamSynchronize(s));
-    if (flag)
-        rc = -EDOM;
+    rc = csr_flags_errno(flag);
 fail:
     if (rc) /* nothing of ours is left running when the scratch is freed */
         (void)hipStreamSynchronize(s);

@@ -51,8 +51,7 @@
 #include <string.h>
 #include <vector>
 
-#include "hip_common.h"
-#include "transpose_plan.h"
+#include "csr_build.h"
 #include "trsv_plan.h"
 
 #define TV_T 256 /* lanes of an analysis workgroup */
@@ -97,7 +96,7 @@ k_trsv_count(int M, int upper, const int *__restrict__ irp,
     cnt[i] = n;
     diag[i] = d;
     if (bad)
-        atomicOr(flag, 1u);
+        atomicOr(flag, CSR_BAD_COLUMN);
     if (d == 0.0)
         atomicAdd(zero_diag, 1ull); /* a COUNT: any order of arrival */
 }
@@ -230,10 +229,6 @@ static hipError_t trsv_keep(spmv_trsv_plan *P, T **out, int64_t count,
     return e;
 }
 
-static inline dim3 tv_grid(int64_t n) {
-    return dim3((unsigned)transpose_ceil_div(n > 0 ? n : 1, TV_T));
-}
-
 void trsv_free_dev(spmv_trsv_plan *P) {
     (void)hipFree(P->level);
     (void)hipFree(P->order);
@@ -310,23 +305,23 @@ int trsv_analyse_dev(const spmv_csr_dev *A, int uplo, int unit, int max_levels,
     HIP_TRY(hipMemsetAsync(counters, 0, (size_t)z.counters * sizeof(int), s));
     HIP_TRY(hipMemsetAsync(d_zero, 0, sizeof(unsigned long long), s));
     if (A->value_bytes == 4)
-        hipLaunchKernelGGL((k_trsv_count<float>), tv_grid(M), dim3(TV_T), 0, s,
-                           M, uplo, A->irp, A->ja, A->as32, cnt, P->diag,
+        hipLaunchKernelGGL((k_trsv_count<float>), grid_for(M, TV_T), dim3(TV_T),
+                           0, s, M, uplo, A->irp, A->ja, A->as32, cnt, P->diag,
                            (unsigned *)(counters + 3), d_zero);
     else
-        hipLaunchKernelGGL((k_trsv_count<double>), tv_grid(M), dim3(TV_T), 0, s,
-                           M, uplo, A->irp, A->ja, A->as, cnt, P->diag,
-                           (unsigned *)(counters + 3), d_zero);
+        hipLaunchKernelGGL((k_trsv_count<double>), grid_for(M, TV_T),
+                           dim3(TV_T), 0, s, M, uplo, A->irp, A->ja, A->as, cnt,
+                           P->diag, (unsigned *)(counters + 3), d_zero);
     tr_scan(cnt, z.cnt, sums, s);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(&snz, cnt + M, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(head, counters, sizeof head, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(&zero, d_zero, sizeof zero, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if (head[3]) {
-        rc = -EDOM; /* a column outside [0, M): nothing was written for it */
+    /* a column outside [0, M): nothing was written for it */
+    rc = csr_flags_errno((unsigned)head[3]);
+    if (rc)
         goto fail;
-    }
     if (snz < 0 || snz > A->NZ) {
         rc = -EIO;
         goto fail;
@@ -340,8 +335,8 @@ int trsv_analyse_dev(const spmv_csr_dev *A, int uplo, int unit, int max_levels,
     HIP_TRY(trsv_keep(P, (char **)&P->as, z.sja, (size_t)A->value_bytes));
     HIP_TRY(scratch.get(&sja, z.sja));
     HIP_TRY(scratch.get(&spos, z.spos));
-    hipLaunchKernelGGL(k_trsv_fill, tv_grid(M), dim3(TV_T), 0, s, M, uplo,
-                       A->irp, A->ja, cnt, sja, spos);
+    hipLaunchKernelGGL(k_trsv_fill, grid_for(M, TV_T), dim3(TV_T), 0, s, M,
+                       uplo, A->irp, A->ja, cnt, sja, spos);
     HIP_TRY(hipGetLastError());
     if (sweeps) { /* one level of M rows, the identity order, cnt is rowptr */
         (void)hipFree(P->level_ptr);
@@ -363,8 +358,8 @@ int trsv_analyse_dev(const spmv_csr_dev *A, int uplo, int unit, int max_levels,
                                hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(P->rowptr, cnt, ((size_t)M + 1) * sizeof(int),
                                hipMemcpyDeviceToDevice, s));
-        hipLaunchKernelGGL(k_trsv_natural, tv_grid(M), dim3(TV_T), 0, s, M,
-                           P->order, P->level);
+        hipLaunchKernelGGL(k_trsv_natural, grid_for(M, TV_T), dim3(TV_T), 0, s,
+                           M, P->order, P->level);
         goto gather;
     }
     HIP_TRY(scratch.get(&succ_ptr, z.succ_ptr));
@@ -394,8 +389,9 @@ int trsv_analyse_dev(const spmv_csr_dev *A, int uplo, int unit, int max_levels,
             goto fail;
     }
     /* Kahn: one launch and one read-back per level */
-    hipLaunchKernelGGL(k_trsv_kahn_init, tv_grid((int64_t)M + 1), dim3(TV_T), 0,
-                       s, M, cnt, indeg, P->level, iota, frontier, counters);
+    hipLaunchKernelGGL(k_trsv_kahn_init, grid_for((int64_t)M + 1, TV_T),
+                       dim3(TV_T), 0, s, M, cnt, indeg, P->level, iota,
+                       frontier, counters);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(&nf, counters, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -411,8 +407,8 @@ int trsv_analyse_dev(const spmv_csr_dev *A, int uplo, int unit, int max_levels,
         placed += nf;
         int *const from = frontier + (int64_t)(levels & 1) * M;
         int *const to = frontier + (int64_t)((levels + 1) & 1) * M;
-        hipLaunchKernelGGL(k_trsv_kahn_step, tv_grid(nf), dim3(TV_T), 0, s, M,
-                           from, nf, succ_ptr, succ, indeg, P->level,
+        hipLaunchKernelGGL(k_trsv_kahn_step, grid_for(nf, TV_T), dim3(TV_T), 0,
+                           s, M, from, nf, succ_ptr, succ, indeg, P->level,
                            levels + 1, to, counters + (levels + 1) % 3,
                            counters + (levels + 2) % 3);
         HIP_TRY(hipGetLastError());
@@ -456,18 +452,18 @@ int trsv_analyse_dev(const spmv_csr_dev *A, int uplo, int unit, int max_levels,
     }
     /* the copy: rows of one level contiguous */
     HIP_TRY(hipMemsetAsync(P->rowptr + M, 0, sizeof(int), s));
-    hipLaunchKernelGGL(k_trsv_newcnt, tv_grid(M), dim3(TV_T), 0, s, M, P->order,
-                       cnt, P->rowptr);
+    hipLaunchKernelGGL(k_trsv_newcnt, grid_for(M, TV_T), dim3(TV_T), 0, s, M,
+                       P->order, cnt, P->rowptr);
     tr_scan(P->rowptr, (int64_t)M + 1, sums, s);
 gather:
     if (A->value_bytes == 4)
-        hipLaunchKernelGGL((k_trsv_gather<uint32_t>), tv_grid(M), dim3(TV_T), 0,
-                           s, M, P->order, cnt, sja, spos,
+        hipLaunchKernelGGL((k_trsv_gather<uint32_t>), grid_for(M, TV_T),
+                           dim3(TV_T), 0, s, M, P->order, cnt, sja, spos,
                            (const uint32_t *)A->as32, P->rowptr, P->ja,
                            (uint32_t *)P->as);
     else
-        hipLaunchKernelGGL((k_trsv_gather<uint64_t>), tv_grid(M), dim3(TV_T), 0,
-                           s, M, P->order, cnt, sja, spos,
+        hipLaunchKernelGGL((k_trsv_gather<uint64_t>), grid_for(M, TV_T),
+                           dim3(TV_T), 0, s, M, P->order, cnt, sja, spos,
                            (const uint64_t *)A->as, P->rowptr, P->ja,
                            (uint64_t *)P->as);
     HIP_TRY(hipGetLastError());

@@ -17,6 +17,7 @@ most 2^-24 * sum_j |a_ij x_j|, plus the parity bound.
 Every test runs under a time limit of its own (LIMIT_S): a test that exceeds
 it ends the whole process, so nothing else is started on the device.
 """
+import ctypes as C
 import errno
 import faulthandler
 import glob
@@ -349,6 +350,30 @@ def test_a_finite_value_that_overflows_fp32_is_erange_and_leaks_nothing():
         S.hll_free(Hh)
     assert S._lib.spmv_live_handles() == live
     assert S.live_objects() == [d64]
+    # every refusal of to_f32 leaves *out NULL and no handle behind: the one
+    # that comes after the result was allocated, a handle that is none, an
+    # f32 operand, a released source
+    As = S.csr_from_arrays(
+        "small", *_tiny([[(0, 1.0)], [(1, 2.0)], [(2, 3.0)]] * 20))
+    small = S.CsrDevice.upload(As)
+    narrow = small.to_f32()
+    try:
+        S.set_panel_schedule("chain")
+        small.build_panels(0)
+        small.release_source()
+    finally:
+        S.set_panel_schedule("sweep")
+    junk = C.cast(C.create_string_buffer(512), C.c_void_p)
+    before = S._lib.spmv_live_handles()
+    for err, h in ((errno.ERANGE, d64.h), (errno.EBADF, junk),
+                   (errno.EINVAL, narrow.h), (errno.ENODATA, small.h)):
+        out = C.c_void_p(1234)
+        assert S._lib.spmv_csr_to_f32(h, C.byref(out)) == -err, err
+        assert out.value is None
+        assert S._lib.spmv_live_handles() == before
+    narrow.release()
+    small.release()
+    S.csr_free(As)
     # the largest finite fp32 and a value that rounds DOWN to it still fit
     AS2 = AS.copy()
     AS2[AS2 == 1e39] = float(np.finfo(np.float32).max) * (1.0 + 2.0 ** -26)

@@ -411,22 +411,32 @@ def test_every_refusal_in_its_order_creates_nothing():
                   np.array([1, 4, 4], np.int32), np.ones(3)))
     refused(dA.h, dup.h, errno.EINVAL)
     refused(dup.h, dup.h, errno.EINVAL)
+    # the companions: a refusal leaves *out NULL and no handle behind, also
+    # the one that comes after the result was allocated (scale's -EDOM)
+    d_v = S.DevBuffer.from_numpy(np.ones(20))
+    before = S._lib.spmv_live_handles()
+    for err, args in (
+            (errno.EBADF, (junk, d_v.ptr, None)),
+            (errno.EINVAL, (dA.h, None, None)),
+            (errno.ENODATA, (gone.h, d_v.ptr, None)),
+            (errno.EDOM, (bad.h, None, d_v.ptr)),
+            (errno.EDOM, (both.h, d_v.ptr, d_v.ptr))):
+        out = C.c_void_p(1234)
+        assert S._lib.spmv_csr_scale(*args, C.byref(out)) == -err, (err, args)
+        assert out.value is None
+        assert S._lib.spmv_live_handles() == before
+    out = C.c_void_p(1234)
+    assert S._lib.spmv_csr_from_diag(-1, d_v.ptr,
+                                     C.byref(out)) == -errno.EINVAL
+    assert out.value is None and S._lib.spmv_live_handles() == before
+    assert S._lib.spmv_csr_from_diag(3, d_v.ptr, None) == -errno.EINVAL
+    assert S._lib.spmv_live_handles() == before
+    d_v.free()
     for h in (dup, unsorted, both, bad, gone, tall, other):
         h.release()
     assert S._lib.spmv_live_handles() == live
     with pytest.raises(TypeError):
         dA.add(B)
-    # the companions
-    out = C.c_void_p(1234)
-    d_v = S.DevBuffer.from_numpy(np.ones(20))
-    assert S._lib.spmv_csr_scale(junk, d_v.ptr, None,
-                                 C.byref(out)) == -errno.EBADF
-    assert out.value is None
-    out = C.c_void_p(1234)
-    assert S._lib.spmv_csr_scale(dA.h, None, None,
-                                 C.byref(out)) == -errno.EINVAL
-    assert out.value is None and S._lib.spmv_live_handles() == live
-    d_v.free()
     # the operands are unchanged, and a released one is refused
     assert same(arrays(dA), A[2:]) and same(arrays(dB), B[2:])
     for h in (dB, dA):

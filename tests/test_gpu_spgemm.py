@@ -306,6 +306,24 @@ def test_errors_in_order_create_nothing():
     assert S._lib.spmv_csr_galerkin(dA.h, dA.h, None, C.byref(out),
                                     None) == -errno.EINVAL
     assert out.value is None and S._lib.spmv_live_handles() == live
+    # ... from each of them: a handle that is none as A, as P and as P^T, a
+    # released source as P, a P^T of the wrong shape (the third and the last
+    # after A P was made: it is released)
+    dBT = dB.transpose()
+    live += 1
+    for err, args in ((errno.EBADF, (junk, dB.h, None)),
+                      (errno.EBADF, (dA.h, junk, None)),
+                      (errno.EBADF, (dA.h, dB.h, junk)),
+                      (errno.ENODATA, (dA.h, gone.h, None)),
+                      (errno.ENODATA, (dA.h, gone.h, dBT.h)),
+                      (errno.EINVAL, (dA.h, dB.h, dB.h))):
+        out = C.c_void_p(1234)
+        assert S._lib.spmv_csr_galerkin(*args, C.byref(out),
+                                        C.byref(info)) == -err, (err, args)
+        assert out.value is None and info.nz == -77
+        assert S._lib.spmv_live_handles() == live
+    dBT.release()
+    live -= 1
     with pytest.raises(TypeError):
         dA.matmul(B)
     # the operands are unchanged, and a released one is refused

@@ -363,6 +363,13 @@ def test_ownership_and_error_paths():
     sym = C.c_int(7)
     assert S._lib.spmv_csr_symmetry(junk, C.byref(sym)) == -errno.EBADF
     assert sym.value == 0 and S._lib.spmv_live_handles() == live
+    # ... but for a column outside [0, N), found after T was allocated
+    far = upload((3, 3, np.array([0, 1, 3, 4], np.int32),
+                  np.array([0, 1, 5, 2], np.int32), np.ones(4)))
+    out = C.c_void_p(1234)
+    assert S._lib.spmv_csr_transpose(far.h, C.byref(out)) == -errno.EDOM
+    assert out.value is None and S._lib.spmv_live_handles() == live + 1
+    far.release()
     T = d.transpose()
     assert S._lib.spmv_live_handles() == live + 1
     assert same(arrays(d), before)  # A is unchanged
